@@ -1,6 +1,6 @@
 """Benchmark of the MI355X metric-evaluation hot path (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 A "step" = one fused pass of the deterministic suite (MSE + RMSE + MAE + Bias +
 ACC for the 13 predefined slice regions of scripts/evaluate.py:345-374) over a
@@ -63,7 +63,9 @@ skips it and quotes profiles/ instead).
 shard).
 
 Prints ONE JSON line (rank 0): the compact contract line (< 4 kB).  The full
-record of every leg goes to bench_detail.json beside this file.
+record of every leg goes to bench_detail.json beside this file.  With
+`--dump-outputs DIR` the headline's results (its last timed step's metrics and
+the running mean over the K timed steps) are written to DIR as .npy files.
 """
 from __future__ import annotations
 
@@ -313,7 +315,21 @@ def parse_args():
   ap.add_argument('--spectrum-units', type=int, default=SPECTRUM_UNITS,
                   help='units of 13 x 721 x 1440 per launch of the spectrum '
                        'workloads')
-  return ap.parse_args()
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='after the timed steps of the headline, write what its '
+                       'last timed step handed the caller to DIR/<name>.npy '
+                       '(float64): step_metrics = the per-chunk metrics of '
+                       'that step, [metric, region, unit * level]; total / '
+                       'count / mean = the running init-time mean over the '
+                       'timed steps, [metric * region, level].  Inputs are '
+                       'seeded, so two builds can be compared output for '
+                       'output (deterministic workload only)')
+  args = ap.parse_args()
+  if args.dump_outputs and (args.workload != 'deterministic' or
+                            args.variants_only or args.traffic_probe):
+    ap.error('--dump-outputs needs the deterministic headline (no --workload, '
+             '--variants-only or --traffic-probe)')
+  return args
 
 
 def self_launch(args) -> int:
@@ -543,6 +559,8 @@ def main():
     torch.cuda.synchronize()
     return
 
+  last_region = []  # the last timed region's [sum, count, ...] + means
+
   def timed_region(step_fn, n_steps, accumulators):
     """The contract's bracket: barrier + synchronize on both sides, exactly
     n_steps steps and the path's one all-reduce inside; returns (max-over-ranks
@@ -570,6 +588,7 @@ def main():
         off += sh.numel()
     for s_, c_ in zip(accumulators[0::2], accumulators[1::2]):
       means.append(s_ / c_)
+    last_region[:] = accumulators + means
     torch.cuda.synchronize()
     own = time.perf_counter() - t0
     if ddp:
@@ -591,6 +610,18 @@ def main():
   dt, own_dt, gpu_ms = timed_region(lambda i: step(args.warmup + i, True),
                                     args.steps, [total, count])
   rank_ms = per_rank(own_dt / args.steps * 1e3)
+  if args.dump_outputs:
+    # what the last timed step handed its caller, copied before any later
+    # loop reuses the suites' buffers and the accumulators
+    n_last = all_tables[args.warmup + args.steps - 1][1] if args.steps else 0
+    dump = {'total': last_region[0], 'count': last_region[1],
+            'mean': last_region[2]}
+    if n_last:
+      dump['step_metrics'] = suites[n_last].metrics
+    dump = {k: v.detach().to('cpu', torch.float64).numpy().copy()
+            for k, v in dump.items()}
+    if rank == 0:
+      dump_outputs(args.dump_outputs, dump)
 
   # ---- K1's duration: HIP events around the kernel alone, on the launch
   # stream, over the same table sets as the timed steps, in a loop of its own
@@ -833,6 +864,20 @@ def main():
   if ddp:
     dist.barrier()
     dist.destroy_process_group()
+
+
+DUMP_LIMIT = 64 << 20  # bytes: the whole of --dump-outputs
+
+
+def dump_outputs(directory: str, arrays: dict) -> None:
+  """Writes every array as DIR/<name>.npy (float32 / float64 only)."""
+  size = sum(a.nbytes for a in arrays.values())
+  if size > DUMP_LIMIT:
+    raise SystemExit(f'--dump-outputs: {size} bytes > {DUMP_LIMIT}')
+  os.makedirs(directory, exist_ok=True)
+  for name, a in arrays.items():
+    assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+    np.save(os.path.join(directory, name + '.npy'), a)
 
 
 DETAIL_FILE = 'bench_detail.json'

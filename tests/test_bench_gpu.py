@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -187,3 +188,34 @@ def test_detail_run_carries_every_instantiation():
     assert v['kernel_ms'] > 0 and 0 < v['frac'] < 1
   assert 'error' not in detail['k3_variants'], detail['k3_variants']
   assert 'error' not in detail['tier2_variants'], detail['tier2_variants']
+
+
+def test_dump_outputs_are_the_headline_results_and_reproducible(tmp_path):
+  """`--dump-outputs DIR`: the last timed step's metrics and the running mean
+  of the K timed steps as float64 .npy files; the inputs are seeded, so two
+  runs with the same arguments write the same numbers."""
+  def run(directory):
+    out = subprocess.run(
+        [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1',
+         '--steps', '3', '--warmup', '1', '--units', '2', '--pool', '4',
+         '--ramp-ms', '0', '--no-cpu-baseline', '--no-full-suite', '--no-api',
+         '--no-secondary', '--no-pcie', '--no-pmc',
+         '--dump-outputs', str(directory)],
+        env=_clean_env(), cwd=ROOT, capture_output=True, text=True,
+        timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line['steps'] == 3 and line['ms_per_step'] > 0
+    return {n: np.load(directory / (n + '.npy'))
+            for n in ('step_metrics', 'total', 'count', 'mean')}
+
+  a, b = run(tmp_path / 'a'), run(tmp_path / 'b')
+  n_region = 13
+  assert a['step_metrics'].shape == (5, n_region, 2 * 13)
+  assert a['total'].shape == a['count'].shape == a['mean'].shape == (
+      5 * n_region, 13)
+  for name, x in a.items():
+    assert x.dtype == np.float64 and np.isfinite(x).all(), name
+    np.testing.assert_allclose(b[name], x, rtol=1e-12, atol=0, err_msg=name)
+  np.testing.assert_array_equal(a['mean'], a['total'] / a['count'])
+  assert (a['count'] == 3 * 2).all()  # K steps x units, per (metric, level)

@@ -111,8 +111,7 @@ int wb2_num_slots(int mode, int skipna);
 
 /* Columns one wavefront covers (64 lanes x 16-byte vectors whenever n_col holds
  * one vector: rows of any length and element-aligned base pointers take the wide
- * loads -- `aligned16` only matters with WB2HIP_UNALIGNED_VEC=0, the rule of
- * rounds 1-3: one column per lane unless everything is 16-byte aligned);
+ * loads -- `aligned16` does not change the width);
  * n_ctile = ceil(n_col / wb2_tile_cols(...)). */
 int wb2_tile_cols(int dtype, int n_col, int aligned16);
 /* The same for a given instantiation: an instantiation may cover fewer columns

@@ -53,8 +53,7 @@ if [ "$2" != quick ]; then
   timeout 600 python tools/k3_variants.py > $OUT/${R}_k3_variants.json 2>/dev/null
   timeout 600 python tools/tier2_variants.py > $OUT/${R}_tier2_variants.json 2>/dev/null
   ( for th in 4 8 16; do WB2HIP_COPY_THREADS=$th timeout 120 python tools/upload_sweep.py 2>/dev/null | tail -1; done
-    for slots in 4 8; do WB2HIP_STAGE_SLOTS=$slots timeout 120 python tools/upload_sweep.py 2>/dev/null | tail -1; done
-    for ds in 2 3; do WB2HIP_DMA_STREAMS=$ds timeout 120 python tools/upload_sweep.py 2>/dev/null | tail -1; done ) > $OUT/${R}_upload_sweep.txt
+    for slots in 4 8; do WB2HIP_STAGE_SLOTS=$slots timeout 120 python tools/upload_sweep.py 2>/dev/null | tail -1; done ) > $OUT/${R}_upload_sweep.txt
 fi
 python tools/kernel_table.py $R > $OUT/${R}_kernel_table.md 2>/dev/null || true
 ls -la $OUT

@@ -1,5 +1,5 @@
 """Rate of the pageable-host -> HBM uploader alone (csrc/staging.cpp) for the
-calling environment's WB2HIP_COPY_THREADS / WB2HIP_STAGE_MEMCPY: one official
+calling environment's WB2HIP_COPY_THREADS: one official
 chunk's 13 variables (353 MB) uploaded back to back.
 
   WB2HIP_COPY_THREADS=16 python tools/upload_sweep.py
@@ -45,7 +45,6 @@ def main():
   dp = time.perf_counter() - t0
   print(json.dumps({
       'copy_threads': feeder.copy_threads(),
-      'plain_memcpy': os.environ.get('WB2HIP_STAGE_MEMCPY') == '1',
       'slice_MiB': feeder._SLICE_BYTES >> 20, 'slots': feeder._RING_SLOTS,
       'pageable_GBps': reps * nbytes / dt / 1e9,
       'pinned_GBps': reps * nbytes / dp / 1e9}))

@@ -25,12 +25,10 @@
 //      stream beside the big one and join before step 3;
 //   3. one wb2_gather_accumulate[_rows] per sink (eval config).
 #include "common.hpp"
-#include "suite_streams.hpp"
 #include "trace.hpp"
 #include "wb2hip.h"
 
 #include <chrono>
-#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <vector>
@@ -98,11 +96,6 @@ struct Program {
   hipStream_t side[kSide] = {};
   hipEvent_t fork = nullptr, join[kSide] = {};
   bool any_side = false;
-  // the pair kernel of a launch with wind-vector pairs beside its
-  // per-variable kernel (WB2HIP_PAIR_STREAM=1; default: behind it)
-  hipStream_t pair_stream = nullptr;
-  hipEvent_t pair_join = nullptr;
-  bool any_pairs = false;
   // host seconds spent in replay, by phase (wb2_program_stats): waiting for a
   // ring slot, filling the table, the copy, the launches, the sinks
   double spent[5] = {};
@@ -130,11 +123,6 @@ int release(Program* p) {
     }
     if (p->join[i]) (void)hipEventDestroy(p->join[i]);
   }
-  if (p->pair_stream) {
-    (void)hipStreamSynchronize(p->pair_stream);
-    (void)hipStreamDestroy(p->pair_stream);
-  }
-  if (p->pair_join) (void)hipEventDestroy(p->pair_join);
   if (p->fork) (void)hipEventDestroy(p->fork);
   if (p->copy_stream) (void)hipStreamDestroy(p->copy_stream);
   delete p;
@@ -199,7 +187,6 @@ int wb2_program_add_launch(void* program, const wb2_plan_tables* plan, int mode,
   la.table_offset = p->table_len;
   p->table_len += (long long)n;
   p->any_side = p->any_side || la.side;
-  p->any_pairs = p->any_pairs || (la.n_pair > 0 && !la.side);
   p->launches.push_back(std::move(la));
   return 0;
 }
@@ -342,19 +329,6 @@ int wb2_program_finalize(void* program, double* arena, int32_t n_ptrs,
     }
     WB2_HIP_OK(hipEventCreateWithFlags(&p->fork, hipEventDisableTiming));
   }
-  // measured (profiles/r06_round_log.md): beside each other the two kernels
-  // gain 2 % in 24-chunk windows and lose 5 % chunk by chunk -- off unless
-  // WB2HIP_PAIR_STREAM=1
-  static const bool pair_stream_on = [] {
-    const char* e = getenv("WB2HIP_PAIR_STREAM");
-    return e && e[0] == '1';
-  }();
-  if (p->any_pairs && pair_stream_on) {
-    WB2_HIP_OK(hipStreamCreateWithFlags(&p->pair_stream, hipStreamNonBlocking));
-    WB2_HIP_OK(hipEventCreateWithFlags(&p->pair_join, hipEventDisableTiming));
-    if (!p->fork)
-      WB2_HIP_OK(hipEventCreateWithFlags(&p->fork, hipEventDisableTiming));
-  }
   p->finalized = true;
   return 0;
 }
@@ -443,11 +417,10 @@ int wb2_program_replay(void* program, const int64_t* ptrs, int32_t n_ptrs,
     if (la.n_pair > 0) {
       const long long n_det =
           (long long)WB2_NMETRIC * la.plan.n_region * la.n_outer;
-      hipStream_t ps = ls == s ? p->pair_stream : nullptr;
-      return det_wind_suite_step_streams(
+      return wb2_det_wind_suite_step(
           &la.plan, la.mode, la.dtype, la.skipna, nullptr, slabs, aligned16,
           la.n_outer, la.n_pair, la.partials, la.wind_partials, metrics,
-          metrics + n_det, ls, ps, ps ? p->pair_join : nullptr);
+          metrics + n_det, ls);
     }
     return wb2_det_suite_step(&la.plan, la.mode, la.dtype, la.skipna, nullptr,
                               slabs, aligned16, la.n_outer, la.partials,
@@ -455,9 +428,8 @@ int wb2_program_replay(void* program, const int64_t* ptrs, int32_t n_ptrs,
                               ls);
   };
   int n_side = 0;
-  if (p->any_side || p->pair_stream) WB2_HIP_OK(hipEventRecord(p->fork, s));
-  if (p->pair_stream) WB2_HIP_OK(hipStreamWaitEvent(p->pair_stream, p->fork, 0));
   if (p->any_side) {
+    WB2_HIP_OK(hipEventRecord(p->fork, s));
     for (size_t li = 0; li < p->launches.size(); ++li) {
       const Launch& la = p->launches[li];
       if (!la.side) continue;

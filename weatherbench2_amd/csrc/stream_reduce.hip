@@ -26,11 +26,9 @@
 #include "trace.hpp"
 #include "reduce_common.hpp"
 #include "gauss_math.hpp"
-#include "suite_streams.hpp"
 #include "wb2hip.h"
 
 #include <atomic>
-#include <cstdlib>
 #include <type_traits>
 
 namespace wb2 {
@@ -349,9 +347,6 @@ __device__ __forceinline__ bool eval_slots(
 #ifndef WB2_NT_LOADS
 #define WB2_NT_LOADS 1
 #endif
-#ifndef WB2_K1_RING_DEFAULT
-#define WB2_K1_RING_DEFAULT 0   // rows per wave in flight of the ring form
-#endif
 #ifndef WB2_GAUSS_GROUP
 // Gaussian modes: points of a lane's load evaluated as one straight-line block
 // (2: two dependent fp64 chains interleaved at 114 VGPRs; 4 costs a wave per SIMD)
@@ -401,54 +396,6 @@ __device__ __forceinline__ void load_wf(const WB2_GLOBAL FT* p,
   for (int e = 0; e < VEC; ++e) v[e] = (double)x[e];
 }
 
-// LDS-DMA (gfx950 `global_load_lds_dwordx4`): 16 bytes per lane straight from
-// global memory into LDS at M0 + 16 * lane, no VGPR in between.  `row` is the
-// wave-uniform row pointer (an SGPR pair), `voff` the lane's byte offset in the
-// row, `lds_dst` the wave-uniform LDS byte address of the 1 KiB destination.
-// hipcc does not count these loads (inline asm): the ring kernel waits for
-// them itself (ring_wait).
-template <bool NT>
-__device__ __forceinline__ void glds16(unsigned long long row, unsigned voff,
-                                       unsigned lds_dst) {
-  unsigned keep;
-  if constexpr (NT) {
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %2 nt\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(row), "s"(lds_dst)
-        : "memory");
-  } else {
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %2\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(row), "s"(lds_dst)
-        : "memory");
-  }
-}
-// s_waitcnt vmcnt(n) for a wave-uniform n in [0, 23]
-__device__ __forceinline__ void ring_wait(int n) {
-  switch (n) {
-#define WB2_RING_WAIT(N) \
-  case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-    WB2_RING_WAIT(0) WB2_RING_WAIT(1) WB2_RING_WAIT(2) WB2_RING_WAIT(3)
-    WB2_RING_WAIT(4) WB2_RING_WAIT(5) WB2_RING_WAIT(6) WB2_RING_WAIT(7)
-    WB2_RING_WAIT(8) WB2_RING_WAIT(9) WB2_RING_WAIT(10) WB2_RING_WAIT(11)
-    WB2_RING_WAIT(12) WB2_RING_WAIT(13) WB2_RING_WAIT(14) WB2_RING_WAIT(15)
-    WB2_RING_WAIT(16) WB2_RING_WAIT(17) WB2_RING_WAIT(18) WB2_RING_WAIT(19)
-    WB2_RING_WAIT(20) WB2_RING_WAIT(21) WB2_RING_WAIT(22) WB2_RING_WAIT(23)
-#undef WB2_RING_WAIT
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-}
-
 // Geometry.  Workgroups are dealt to the 8 XCDs round-robin by their linear
 // index, and the chunks of a slab differ in size (bands cut them at region
 // boundaries, the last one is short, the padding to a multiple of 8 is empty).
@@ -474,19 +421,8 @@ __device__ __forceinline__ void ring_wait(int n) {
 // lane are in flight before the first one is consumed.  The prologue is written
 // branch-free on purpose: every scalar (table / slab-index) load is issued
 // before the first wait, instead of one dependent round trip per table.
-//
-// RING > 0 (float32, 4 columns per lane, point-op modes, no skipna): the rows
-// of the chunk come through a ring of RING row stages per wave in LDS, filled
-// by LDS-DMA -- row r + RING is requested when row r has been read out of its
-// stage, so RING rows of NIN (+ 1: the float32 weight field) x 1 KiB per wave
-// are in flight ALL the time and none of them holds a VGPR.  The batch form
-// has its U rows in flight only while it waits for them (then it computes with
-// nothing outstanding), and what it may keep in flight is bounded by registers:
-// the land-mask instantiation (157 VGPRs, 3 waves per SIMD) has 72 KB per CU
-// outstanding at best.  Same loads per lane, same arithmetic in the same order:
-// the same bits.
 template <typename T, int VEC, int MODE, bool SKIPNA, bool WF,
-          bool SG = false, typename FT = double, int RING = 0>
+          bool SG = false, typename FT = double>
 __global__ void __launch_bounds__(512)
     stream_partials_kernel(const StreamParams p) {
   using M = ModeTraits<MODE, SKIPNA>;
@@ -619,10 +555,6 @@ __global__ void __launch_bounds__(512)
         // out of the sum: clearing the high dword (sign, exponent, top of the
         // mantissa) of the float64 slot does that in ONE 32-bit AND instead
         // of the two v_cndmask of a 64-bit select.
-#ifdef WB2_DIAG_WF_NOFMA   // timing diagnostic only: the field is loaded, not used
-        acc[1][e][0] += wfe;
-        return;
-#endif
         const bool inside = wfe > 0.0;
         const unsigned long long keep = inside ? ~0ull : 0x00000000ffffffffull;
         const double w2 = wr * wfe;
@@ -738,11 +670,7 @@ __global__ void __launch_bounds__(512)
           load_vec<T, VEC>(at(base[i] + (long long)(r + u) * p.n_col),
                            bt.v[u][i]);
         if constexpr (WF) {
-#ifdef WB2_DIAG_WF_SAMEROW   // timing diagnostic only: every row reads field row 0
-          load_wf<VEC, FT>(at_wf(wfp + (long long)(u) * p.n_col), bt.wf[u]);
-#else
           load_wf<VEC, FT>(at_wf(wfp + (long long)(r + u) * p.n_col), bt.wf[u]);
-#endif
         } else {
 #pragma unroll
           for (int e = 0; e < VEC; ++e) bt.wf[u][e] = 1.0;
@@ -763,70 +691,6 @@ __global__ void __launch_bounds__(512)
                 MODE == WB2_MODE_SEEPS ? bt.ax[u] : nullptr);
     };
     int r = 0;
-    if constexpr (RING > 0) {
-      static_assert(sizeof(T) == 4 && VEC == 4 && POINT_OPS && !SKIPNA && !SG,
-                    "ring kernel: float32 x 4 columns, point-op modes");
-      static_assert(!WF || sizeof(FT) == 4, "ring kernel: float32 field");
-      constexpr int NSLOT = NIN + (WF ? 1 : 0);
-      static_assert((RING - 1) * NSLOT <= 23, "ring_wait covers 0..23");
-      extern __shared__ __attribute__((aligned(16))) char ring_lds[];
-      typedef __attribute__((address_space(3))) char* LdsPtr;
-      typedef T V4 __attribute__((ext_vector_type(4)));
-      const LdsPtr mine = (LdsPtr)ring_lds + wave * (RING * NSLOT * 1024);
-      const unsigned mine_addr = (unsigned)(unsigned long long)mine;
-      const unsigned voff = (unsigned)colb * 4u;
-      auto request = [&](int row) {   // wave-uniform row < nrow
-        const unsigned dst = mine_addr + (unsigned)(row % RING) * (NSLOT * 1024);
-#pragma unroll
-        for (int i = 0; i < NIN; ++i)
-          glds16<WB2_NT_LOADS != 0>(
-              reinterpret_cast<unsigned long long>(
-                  base[i] + (long long)row * p.n_col),
-              voff, dst + i * 1024);
-        if constexpr (WF)
-          glds16<false>(reinterpret_cast<unsigned long long>(
-                            wfp + (long long)row * p.n_col),
-                        voff, dst + NIN * 1024);
-      };
-      int requested = nrow < RING ? nrow : RING;
-      for (int q = 0; q < requested; ++q) request(q);
-#pragma clang loop unroll(disable)
-      for (; r < nrow; ++r) {
-        // rows r + 1 .. requested - 1 may still be on their way
-        ring_wait((requested - r - 1) * NSLOT);
-        const LdsPtr st = mine + (r % RING) * (NSLOT * 1024) + lane * 16;
-        T v[NIN][VEC];
-        double wf[VEC];
-#pragma unroll
-        for (int i = 0; i < NIN; ++i) {
-          const V4 x = *reinterpret_cast<
-              const __attribute__((address_space(3))) V4*>(st + i * 1024);
-#pragma unroll
-          for (int e = 0; e < VEC; ++e) v[i][e] = x[e];
-        }
-        if constexpr (WF) {
-          const V4 x = *reinterpret_cast<
-              const __attribute__((address_space(3))) V4*>(st + NIN * 1024);
-#pragma unroll
-          for (int e = 0; e < VEC; ++e) wf[e] = (double)x[e];
-        } else {
-#pragma unroll
-          for (int e = 0; e < VEC; ++e) wf[e] = 1.0;
-        }
-        // the row weight by a scalar load of our own (behind the asm memory
-        // clobbers hipcc turns wrp[r] into a VECTOR load and waits vmcnt(0)
-        // for it: the ring would drain every row)
-        double wr;
-        asm volatile("s_load_dwordx2 %0, %1, 0x0"
-                     : "=s"(wr)
-                     : "s"(wrp + r)
-                     : "memory");
-        // the stage (and wr) in registers before its next row is requested
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(wr) : : "memory");
-        if (requested < nrow) request(requested++);
-        consume(v, wf, wr, nullptr);
-      }
-    }
 #pragma clang loop unroll(disable)
     for (; r + U <= nrow; r += U) {
       Batch bt;
@@ -896,26 +760,6 @@ __global__ void __launch_bounds__(512)
 // Slabs: the launch's slab list ends with the u slabs, then the v slabs, of its
 // n_pair pairs (pair k: slabs first + k and first + n_pair + k); wind partials
 // are [n_pair][n_chunk][nwf][n_ts][KW].
-#ifndef WB2_PAIR_U
-#define WB2_PAIR_U WB2_U_ROWS   // rows per batch of the pair kernel
-#endif
-#ifndef WB2_PAIR_WAVES
-#define WB2_PAIR_WAVES 0        // > 0: waves per SIMD the register budget is cut to
-#endif
-#ifndef WB2_PAIR_RELOAD
-// 1: no LDS hand-off and no barrier -- the v wave loads the u slab's forecast
-// and truth itself (the u wave of the same workgroup streams them at about the
-// same time: L2 / L1 hits, no HBM traffic of their own if the caches hold) and
-// forms du^2 with the u wave's arithmetic.  The two waves run free.
-#define WB2_PAIR_RELOAD 0
-#endif
-#if WB2_PAIR_WAVES > 0
-#define WB2_PAIR_OCCUPANCY \
-  __attribute__((amdgpu_waves_per_eu(WB2_PAIR_WAVES, WB2_PAIR_WAVES)))
-#else
-#define WB2_PAIR_OCCUPANCY
-#endif
-
 struct PairParams {
   double* wind_partials;
   long long first;
@@ -924,14 +768,14 @@ struct PairParams {
 
 template <typename T, int VEC, bool ACC, bool SKIPNA, bool WF,
           typename FT = double>
-__global__ void __launch_bounds__(128) WB2_PAIR_OCCUPANCY
+__global__ void __launch_bounds__(128)
     stream_pair_kernel(const StreamParams p, const PairParams pp) {
   constexpr int MODE = ACC ? WB2_MODE_DET_ACC : WB2_MODE_DET;
   using M = ModeTraits<MODE, SKIPNA>;
   using Ops = PointOps<MODE>;
   using MW = ModeTraits<WB2_MODE_WIND, SKIPNA>;
   constexpr int NIN = M::NIN, KD = M::K, KW = MW::K, NWF = WF ? 2 : 1;
-  constexpr int U = WB2_PAIR_U;
+  constexpr int U = WB2_U_ROWS;
   constexpr int TILE = kWave * VEC;
   constexpr bool PAIRS = WB2_PACK_PAIRS && sizeof(T) == 4 && VEC % 2 == 0;
   typedef T VT __attribute__((ext_vector_type(VEC)));
@@ -968,21 +812,6 @@ __global__ void __launch_bounds__(128) WB2_PAIR_OCCUPANCY
     base[i] = reinterpret_cast<const T*>(static_cast<const char*>(p.in[i]) +
                                          slab_idx[i] * p.slab_step_bytes) +
               (long long)row0 * p.n_col;
-#if WB2_PAIR_RELOAD
-  // the u slab's forecast and truth, for the v wave
-  const T* ubase[2];
-  {
-    const long long ou = pp.first + pair;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const long long su = p.slab[i] ? p.slab[i][ou] : ou;
-      ubase[i] = reinterpret_cast<const T*>(
-                     static_cast<const char*>(p.in[i]) +
-                     su * p.slab_step_bytes) +
-                 (long long)row0 * p.n_col;
-    }
-  }
-#endif
   const FT* wfp = WF ? static_cast<const FT*>(p.wfield) +
                            (long long)row0 * p.n_col
                      : nullptr;
@@ -1113,16 +942,12 @@ __global__ void __launch_bounds__(128) WB2_PAIR_OCCUPANCY
     for (int u = 0; u < N; ++u) {
       T sq[VEC];
       consume(std::false_type{}, acc, accw, v[u], wf[u], wr[u], sq);
-#if !WB2_PAIR_RELOAD
       VT out;
 #pragma unroll
       for (int e = 0; e < VEC; ++e) out[e] = sq[e];
       handoff[buf][u][lane] = out;
-#endif
     }
-#if !WB2_PAIR_RELOAD
     __syncthreads();
-#endif
   };
   auto batch_v = [&](auto n_c, int r, int buf) {
     constexpr int N = decltype(n_c)::value;
@@ -1130,42 +955,6 @@ __global__ void __launch_bounds__(128) WB2_PAIR_OCCUPANCY
     double wf[N][VEC], wr[N];
 #pragma unroll
     for (int u = 0; u < N; ++u) load_row(r + u, v[u], wf[u], wr[u]);
-#if WB2_PAIR_RELOAD
-    T uu[N][2][VEC];
-#pragma unroll
-    for (int u = 0; u < N; ++u)
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-        load_vec<T, VEC>(at(ubase[i] + (long long)(r + u) * p.n_col),
-                         uu[u][i]);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int u = 0; u < N; ++u) {
-      T sq[VEC];
-      if constexpr (PAIRS) {   // the u wave's own arithmetic (packed)
-        typedef T V2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-        for (int e = 0; e < VEC; e += 2) {
-          V2 a, b;
-          a[0] = uu[u][0][e];
-          a[1] = uu[u][0][e + 1];
-          b[0] = uu[u][1][e];
-          b[1] = uu[u][1][e + 1];
-          const V2 d = a - b;
-          const V2 q = d * d;
-          sq[e] = q[0];
-          sq[e + 1] = q[1];
-        }
-      } else {
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-          const T d = uu[u][0][e] - uu[u][1][e];
-          sq[e] = d * d;
-        }
-      }
-      consume(std::true_type{}, acc, accw, v[u], wf[u], wr[u], sq);
-    }
-#else
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();
 #pragma unroll
@@ -1176,7 +965,6 @@ __global__ void __launch_bounds__(128) WB2_PAIR_OCCUPANCY
       for (int e = 0; e < VEC; ++e) sq[e] = theirs[e];
       consume(std::true_type{}, acc, accw, v[u], wf[u], wr[u], sq);
     }
-#endif
   };
   int r = 0, it = 0;
   if (role == 0) {
@@ -1575,48 +1363,8 @@ bool field_f32_supported(int dtype, int mode) {
                               mode == WB2_MODE_WIND);
 }
 
-// The ring form of K1 (stream_partials_kernel<..., RING>): WB2HIP_K1_RING = rows
-// per wave in flight (0 = the batch form), WB2HIP_K1_RING_WAVES = waves per
-// workgroup (0 = as the batch form).
-// (read at every launch: tests and A/B runs switch inside one process)
-int ring_depth() {
-  const char* e = getenv("WB2HIP_K1_RING");
-  const int v = e ? atoi(e) : WB2_K1_RING_DEFAULT;
-  return v < 2 ? 0 : (v > 5 ? 5 : v);
-}
-int ring_waves() {
-  const char* e = getenv("WB2HIP_K1_RING_WAVES");
-  const int v = e ? atoi(e) : 0;
-  return v < 1 ? 0 : (v > 8 ? 8 : v);
-}
-
-template <typename T, int VEC, int MODE, bool SKIPNA, bool WF, typename FT,
-          int RING>
-int launch_ring(const StreamParams& p, dim3 grid, int threads,
-                hipStream_t stream) {
-  constexpr int NSLOT = ModeTraits<MODE, SKIPNA>::NIN + (WF ? 1 : 0);
-  const size_t lds = (size_t)(threads / kWave) * RING * NSLOT * 1024;
-  auto kern = stream_partials_kernel<T, VEC, MODE, SKIPNA, WF, false, FT, RING>;
-  static const hipError_t attr = hipFuncSetAttribute(
-      reinterpret_cast<const void*>(kern),
-      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  WB2_HIP_OK(attr);
-  hipLaunchKernelGGL(kern, grid, dim3(threads), lds, stream, p);
-  WB2_HIP_OK(hipGetLastError());
-  return 0;
-}
-
 template <typename T, int VEC, int MODE, bool SKIPNA, bool WF>
 int launch_stream(const StreamParams& p, int threads, hipStream_t stream) {
-  constexpr bool HAS_RING = std::is_same<T, float>::value && VEC == 4 &&
-                            !SKIPNA &&
-                            (MODE == WB2_MODE_DET || MODE == WB2_MODE_DET_ACC);
-  const bool ring = HAS_RING && ring_depth() > 0 && !p.unaligned &&
-                    (!WF || p.wfield_f32);
-  if (ring && ring_waves() > 0) {
-    const int tiles = p.n_ctile;
-    threads = (ring_waves() < tiles ? ring_waves() : tiles) * kWave;
-  }
   const int nwave = threads / kWave;
   const int n_tblk = (p.n_ctile + nwave - 1) / nwave;
   const long long gy = p.n_outer < 32768 ? p.n_outer : 32768;
@@ -1632,35 +1380,12 @@ int launch_stream(const StreamParams& p, int threads, hipStream_t stream) {
                           (MODE == WB2_MODE_DET || MODE == WB2_MODE_DET_ACC ||
                            MODE == WB2_MODE_WIND);
   if constexpr (HAS_SG) {
-    static const bool sg_on = [] {  // WB2HIP_SGPR_UNALIGNED=0: A/B runs
-      const char* e = getenv("WB2HIP_SGPR_UNALIGNED");
-      return !(e && e[0] == '0');
-    }();
-    if (p.unaligned && sg_on) {
+    if (p.unaligned) {
       hipLaunchKernelGGL(
           (stream_partials_kernel<T, VEC, MODE, SKIPNA, WF, true>), grid,
           dim3(threads), 0, stream, p);
       WB2_HIP_OK(hipGetLastError());
       return 0;
-    }
-  }
-  if constexpr (HAS_RING) {
-    if (ring) {
-      using FT = typename std::conditional<WF, float, double>::type;
-      switch (ring_depth()) {
-        case 2:
-          return launch_ring<T, VEC, MODE, SKIPNA, WF, FT, 2>(p, grid, threads,
-                                                              stream);
-        case 3:
-          return launch_ring<T, VEC, MODE, SKIPNA, WF, FT, 3>(p, grid, threads,
-                                                              stream);
-        case 4:
-          return launch_ring<T, VEC, MODE, SKIPNA, WF, FT, 4>(p, grid, threads,
-                                                              stream);
-        default:
-          return launch_ring<T, VEC, MODE, SKIPNA, WF, FT, 5>(p, grid, threads,
-                                                              stream);
-      }
     }
   }
   if constexpr (field_f32_supported<T, MODE>() && WF) {
@@ -1718,20 +1443,12 @@ int launch_stream_mode(const StreamParams& p, int mode, int vec, bool skipna,
 // Columns per lane.  Wide loads need neither 16-byte alignment nor n_col % w ==
 // 0 (the kernel's loads are element-aligned, its last lane shifts back): rows of
 // 721 latitudes -- the lon-lat layout of the WeatherBench 2 Zarr stores -- run
-// at the same width as rows of 1440 longitudes.  WB2HIP_UNALIGNED_VEC=0 brings
-// back the round-1..3 rule (one column per lane unless everything is aligned),
-// for A/B measurements.
-int vec_width(int mode, int dtype, bool skipna, bool wf, int n_col,
-              bool aligned16) {
-  static const bool unaligned_ok = [] {
-    const char* e = getenv("WB2HIP_UNALIGNED_VEC");
-    return !(e && e[0] == '0');
-  }();
+// at the same width as rows of 1440 longitudes.
+int vec_width(int mode, int dtype, bool skipna, bool wf, int n_col) {
   int w = dtype == WB2_F32 ? WB2_F32_VEC : 2;
   if (dtype == WB2_F32 && mode == WB2_MODE_DET_ACC && (skipna || wf))
     w = WB2_F32_VEC_HEAVY;
-  if (unaligned_ok) return n_col >= w ? w : 1;
-  return (aligned16 && n_col % w == 0) ? w : 1;
+  return n_col >= w ? w : 1;
 }
 
 // SpatialSEEPS (metrics.py:418-509): the per-point score of mode SEEPS as a
@@ -1872,8 +1589,7 @@ int stream_partials_impl(int mode, int dtype, int skipna, const void* const* in,
   }
   p.slab_step_bytes = by_addr ? 1 : (long long)n_row * n_col * elem;
   if (wfield) aligned = aligned && reinterpret_cast<uintptr_t>(wfield) % 16 == 0;
-  const int vec = vec_width(mode, dtype, skipna != 0, wfield != nullptr, n_col,
-                            aligned);
+  const int vec = vec_width(mode, dtype, skipna != 0, wfield != nullptr, n_col);
   const int threads = threads_for(n_col, vec);
   p.unaligned = !aligned || ((long long)n_col * elem) % 16 != 0;
   p.w_row = w_row;
@@ -1940,15 +1656,14 @@ int launch_pairs_flags(const StreamParams& p, const PairParams& pp, bool skipna,
   return 0;
 }
 
-bool pairs_supported(int mode, int dtype, bool skipna, bool wf, int n_col,
-                     bool aligned16) {
+bool pairs_supported(int mode, int dtype, bool skipna, bool wf, int n_col) {
   if (mode != WB2_MODE_DET && mode != WB2_MODE_DET_ACC) return false;
   if (dtype != WB2_F32 && dtype != WB2_F64) return false;
   // the pair kernel exists at the per-variable kernel's full width only (its
   // partials share the tile geometry with the per-variable and WIND passes)
   const int w = dtype == WB2_F32 ? 4 : 2;
-  return vec_width(mode, dtype, skipna, wf, n_col, aligned16) == w &&
-         vec_width(WB2_MODE_WIND, dtype, skipna, wf, n_col, aligned16) == w;
+  return vec_width(mode, dtype, skipna, wf, n_col) == w &&
+         vec_width(WB2_MODE_WIND, dtype, skipna, wf, n_col) == w;
 }
 
 int stream_pairs_impl(int mode, int dtype, int skipna, const void* const* in,
@@ -1959,8 +1674,7 @@ int stream_pairs_impl(int mode, int dtype, int skipna, const void* const* in,
                       const int32_t* chunk_row0, const int32_t* chunk_nrow,
                       int32_t n_chunk, int32_t n_ctile, const int32_t* seg_col0,
                       const int32_t* seg_eoff, int32_t n_seg, int32_t n_ts,
-                      double* partials, double* wind_partials, void* stream,
-                      void* pair_stream = nullptr, void* join_event = nullptr) {
+                      double* partials, double* wind_partials, void* stream) {
   WB2_REQUIRE(n_pair >= 0 && 2 * n_pair <= n_outer,
               "n_pair=%lld does not fit n_outer=%lld", (long long)n_pair,
               (long long)n_outer);
@@ -1985,7 +1699,6 @@ int stream_pairs_impl(int mode, int dtype, int skipna, const void* const* in,
   const bool by_addr = in == nullptr;
   const int nin = mode_nin(mode);
   const long long elem = dtype == WB2_F32 ? 4 : 8;
-  bool aligned = by_addr ? addr_aligned16 != 0 : true;
   StreamParams p{};
   for (int i = 0; i < nin; ++i) {
     if (by_addr) {
@@ -1996,11 +1709,8 @@ int stream_pairs_impl(int mode, int dtype, int skipna, const void* const* in,
     WB2_REQUIRE(in[i] != nullptr, "input %d is null", i);
     p.in[i] = in[i];
     p.slab[i] = slab ? reinterpret_cast<const long long*>(slab[i]) : nullptr;
-    aligned = aligned && (reinterpret_cast<uintptr_t>(in[i]) % 16 == 0);
   }
-  if (wfield) aligned = aligned && reinterpret_cast<uintptr_t>(wfield) % 16 == 0;
-  WB2_REQUIRE(pairs_supported(mode, dtype, skipna != 0, wfield != nullptr, n_col,
-                              aligned),
+  WB2_REQUIRE(pairs_supported(mode, dtype, skipna != 0, wfield != nullptr, n_col),
               "no pair kernel for this launch (n_col=%d too narrow for the "
               "wide loads): ask wb2_pairs_supported first", n_col);
   const int vec = dtype == WB2_F32 ? 4 : 2;
@@ -2031,11 +1741,7 @@ int stream_pairs_impl(int mode, int dtype, int skipna, const void* const* in,
   pp.wind_partials = wind_partials;
   pp.first = n_single;
   pp.n_pair = n_pair;
-  // `pair_stream`: the pair kernel beside the per-variable kernel (their
-  // tails overlap); the caller has ordered pair_stream behind whatever made
-  // the inputs, `stream` waits for `join_event` before anything reads the
-  // pairs' partials
-  hipStream_t s = static_cast<hipStream_t>(pair_stream ? pair_stream : stream);
+  hipStream_t s = static_cast<hipStream_t>(stream);
   const bool acc = mode == WB2_MODE_DET_ACC;
   if (dtype == WB2_F32)
     rc = acc ? launch_pairs_flags<float, 4, true>(p, pp, skipna != 0,
@@ -2047,12 +1753,7 @@ int stream_pairs_impl(int mode, int dtype, int skipna, const void* const* in,
                                                    wfield != nullptr, s)
              : launch_pairs_flags<double, 2, false>(p, pp, skipna != 0,
                                                     wfield != nullptr, s);
-  if (rc != 0 || !pair_stream) return rc;
-  WB2_REQUIRE(join_event != nullptr, "a pair stream needs a join event");
-  WB2_HIP_OK(hipEventRecord(static_cast<hipEvent_t>(join_event), s));
-  WB2_HIP_OK(hipStreamWaitEvent(static_cast<hipStream_t>(stream),
-                                static_cast<hipEvent_t>(join_event), 0));
-  return 0;
+  return rc;
 }
 
 }  // namespace
@@ -2081,7 +1782,7 @@ int wb2_tile_cols_ex(int mode, int dtype, int skipna, int has_wfield, int n_col,
                      int aligned16) {
   if (dtype != WB2_F32 && dtype != WB2_F64) return wb2::fail("bad dtype");
   return wb2::kWave * wb2::vec_width(mode, dtype, skipna != 0, has_wfield != 0,
-                                     n_col, aligned16 != 0);
+                                     n_col);
 }
 
 int wb2_stream_partials(int mode, int dtype, int skipna,
@@ -2147,8 +1848,7 @@ int wb2_stream_partials_addr(int mode, int dtype, int skipna,
 
 int wb2_pairs_supported(int mode, int dtype, int skipna, int has_wfield,
                         int n_col, int aligned16) {
-  return wb2::pairs_supported(mode, dtype, skipna != 0, has_wfield != 0, n_col,
-                              aligned16 != 0)
+  return wb2::pairs_supported(mode, dtype, skipna != 0, has_wfield != 0, n_col)
              ? 1
              : 0;
 }
@@ -2264,11 +1964,7 @@ int combine_det_and_wind(const wb2_plan_tables& t, int mode, int skipna,
       t.band_chunk0, t.n_band, t.coef_band, t.coef_seg, t.region_wf,
       t.region_wsum, t.n_region, nullptr, wind_metrics, &lds_b);
   const size_t lds = lds_a > lds_b ? lds_a : lds_b;
-  static const bool fused = [] {  // WB2HIP_FUSED_FOLDS=0: A/B runs
-    const char* e = getenv("WB2HIP_FUSED_FOLDS");
-    return !(e && e[0] == '0');
-  }();
-  if (!fused || lds > 64 * 1024 || n_outer <= 0 || n_pair <= 0 ||
+  if (lds > 64 * 1024 || n_outer <= 0 || n_pair <= 0 ||
       n_outer + n_pair >= (1ll << 31) || !partials || !wind_partials ||
       !metrics || !wind_metrics || !t.seg_eoff || !t.band_chunk0 ||
       !t.coef_band || !t.coef_seg || !t.region_wf || !t.region_wsum ||
@@ -2457,22 +2153,7 @@ int wb2_det_wind_suite_step(const wb2_plan_tables* plan, int mode, int dtype,
                             double* wind_partials, double* metrics,
                             double* wind_metrics, void* stream) {
   WB2_TRACE();
-  return wb2::det_wind_suite_step_streams(
-      plan, mode, dtype, skipna, in, slab, aligned16, n_outer, n_pair, partials,
-      wind_partials, metrics, wind_metrics, stream, nullptr, nullptr);
-}
-
-}  // extern "C"
-
-namespace wb2 {
-int det_wind_suite_step_streams(const wb2_plan_tables* plan, int mode,
-                                int dtype, int skipna, const void* const* in,
-                                const int64_t* const* slab, int aligned16,
-                                int64_t n_outer, int64_t n_pair,
-                                double* partials, double* wind_partials,
-                                double* metrics, double* wind_metrics,
-                                void* stream, void* pair_stream,
-                                void* join_event) {
+  using namespace wb2;
   WB2_REQUIRE(plan != nullptr, "null plan");
   WB2_EMPTY_OK(n_outer);
   WB2_REQUIRE(in != nullptr || slab != nullptr, "null pointer argument");
@@ -2484,14 +2165,11 @@ int det_wind_suite_step_streams(const wb2_plan_tables* plan, int mode,
                              t.wfield, t.wfield_dtype, t.chunk_row0,
                              t.chunk_nrow, t.n_chunk, t.n_ctile, t.seg_col0,
                              t.seg_eoff, t.n_seg, t.n_ts, partials,
-                             wind_partials, stream, pair_stream, join_event);
+                             wind_partials, stream);
   if (rc != 0) return rc;
   return combine_det_and_wind(t, mode, skipna, partials, n_outer, wind_partials,
                               n_pair, metrics, wind_metrics, stream);
 }
-}  // namespace wb2
-
-extern "C" {
 
 int wb2_gather_accumulate(const double* arena, const int32_t* src,
                           const uint8_t* round32, int64_t n_out, int64_t n_time,

@@ -16,19 +16,18 @@ keep every point's |w x| above 1e-8 * sum|w x| (bounded values, no exact
 zeros): one dropped or double-counted point fails that tolerance, which each
 case proves on the reference itself.
 """
-import math
-
 import numpy as np
 import pytest
 
 from oracle import metrics_np as om
 from oracle.named import DS, NA
+from tests import geometry_reference as gr
 from tests import helpers
 from tests import stream_geometry_cases as sg
 
 pytestmark = pytest.mark.gpu
 
-SUM_RTOL = 1e-12
+SUM_RTOL = gr.SUM_RTOL
 N_POOL = 3
 TABLE = (2, 0, 2, 1)  # permutes and repeats the pool's slabs
 
@@ -48,24 +47,6 @@ def lib():
 
 
 # ---- the reference ----------------------------------------------------------
-def region_weights(region, lat, lon, layout):
-  """Per-point weights of `region` as a slab [n_row, n_col] of `layout`:
-  latitude weights times Region.apply's weights, scattered back to the points
-  the region selected (a point selected twice counts twice)."""
-  n_lat, n_lon = len(lat), len(lon)
-  idx = NA(np.arange(n_lat * n_lon, dtype=np.float64).reshape(n_lat, n_lon),
-           ('latitude', 'longitude'))
-  ds = DS({'idx': idx}, {'latitude': lat, 'longitude': lon})
-  sub, w = region.apply(ds, om.get_lat_weights(lat))
-  where = sub['idx'].transpose('latitude', 'longitude').data
-  wfull = (w * (sub['idx'] * 0.0 + 1.0)).transpose('latitude',
-                                                    'longitude').data
-  out = np.zeros(n_lat * n_lon)
-  np.add.at(out, where.astype(np.int64).ravel(), wfull.ravel())
-  out = out.reshape(n_lat, n_lon)
-  return out if layout == 'latlon' else np.ascontiguousarray(out.T)
-
-
 def point_slots(mode, skipna, ins):
   """The K per-point values of PointOps<MODE> (stream_reduce.hip), float64."""
   def keep(q):
@@ -91,25 +72,6 @@ def point_slots(mode, skipna, ins):
   return out + [kept[0][1], kept[2][1], kept[3][1], kept[4][1]]
 
 
-def ref_sums(weights, slots):
-  """(sums, sums of |w x|) [n_outer, n_region, K] and the regions' weight
-  sums [n_region], all with math.fsum."""
-  n_outer, k = slots[0].shape[0], len(slots)
-  sums = np.zeros((n_outer, len(weights), k))
-  mags = np.zeros_like(sums)
-  wsum = np.zeros(len(weights))
-  for r, w in enumerate(weights):
-    m = w != 0
-    wm = w[m]
-    wsum[r] = math.fsum(wm.tolist())
-    for j in range(k):
-      for o in range(n_outer):
-        p = wm * slots[j][o][m]
-        sums[o, r, j] = math.fsum(p.tolist())
-        mags[o, r, j] = math.fsum(np.abs(p).tolist())
-  return sums, mags, wsum
-
-
 def ref_metrics(mode, skipna, sums, wsum):
   """K2's metrics [MSE, RMSE, MAE, Bias, ACC][n_region][n_outer]."""
   def den(x):
@@ -131,17 +93,6 @@ def ref_metrics(mode, skipna, sums, wsum):
       dp, df, dt = ((den(s[:, j]) if skipna else den(w)) for j in (7, 8, 9))
       out[4] = (s[:, 3] / dp) / np.sqrt((s[:, 4] / df) * (s[:, 5] / dt))
   return out
-
-
-def assert_sums(got, want, mags, tag):
-  tol = SUM_RTOL * mags
-  bad = np.abs(got - want) > tol
-  if bad.any():
-    o, r, k = np.argwhere(bad)[0]
-    raise AssertionError(
-        f'{tag}: {int(bad.sum())} sums off, first (outer {o}, region {r}, '
-        f'slot {k}): got {got[o, r, k]!r} want {want[o, r, k]!r} '
-        f'tol {tol[o, r, k]:.3g}')
 
 
 def assert_metrics(got, want, names, tag):
@@ -169,22 +120,10 @@ def prove_tolerance(res, weights, slots, sums, mags, o):
   last column twice, would fail SUM_RTOL: shown on the reference (global
   region, outer slab `o`, whose row 0 has no NaN) for every slot that cannot
   cancel."""
-  n = res.n_col
-  tile = 64 * sg.launch_vec(res)
   sign_free = [j for j in range(len(slots))
                if res.case.mode == 'wind' or j != 0]
-  perturbed = []
-  if n > tile:
-    w = weights[0].copy()
-    w[:, tile] = 0.0
-    perturbed.append(('drop column T', w))
-  w = weights[0].copy()
-  w[:, n - 1] *= 2.0
-  perturbed.append(('last column twice', w))
-  for what, w in perturbed:
-    s, _, _ = ref_sums([w], [x[o:o + 1] for x in slots])
-    off = np.abs(s[0, 0, sign_free] - sums[o, 0, sign_free])
-    assert (off > SUM_RTOL * mags[o, 0, sign_free]).all(), (what, off)
+  gr.prove_tolerance(weights, slots, sums, mags, o,
+                     64 * sg.launch_vec(res), sign_free)
 
 
 # ---- data -------------------------------------------------------------------
@@ -290,13 +229,13 @@ def run_k1(res, pl, ins, dev):
 
 
 def all_weights(res):
-  return [region_weights(r, res.lat, res.lon, res.case.layout)
+  return [gr.region_weights(r, res.lat, res.lon, res.case.layout)
           for r in res.regions.values()]
 
 
 def reference(res, ins, outer, weights):
   slots = point_slots(res.case.mode, res.case.skipna, [x[outer] for x in ins])
-  sums, mags, wsum = ref_sums(weights, slots)
+  sums, mags, wsum = gr.ref_sums(weights, slots)
   return slots, sums, mags, wsum
 
 
@@ -316,7 +255,7 @@ def test_stream_reduce_geometry(dev, lib, case):
   slots, sums, mags, wsum = reference(res, ins, outer, weights)
   prove_tolerance(res, weights, slots, sums, mags, int(np.argmax(outer == 0)))
   tag = f'{case.id} n_col={res.n_col} T={res.tile}'
-  assert_sums(got_s.cpu().numpy(), sums, mags, tag)
+  gr.assert_sums(got_s.cpu().numpy(), sums, mags, tag)
   want_m = ref_metrics(case.mode, case.skipna, sums, wsum)
   assert_metrics(got_m.cpu().numpy(), want_m, list(res.regions), tag)
   if case.skipna and 'one_col' in res.regions and 2 in outer:
@@ -373,7 +312,7 @@ def test_suite_steps_geometry(dev, lib, case):
   u, v = table[-2], table[-1]
   wslots = point_slots('wind', case.skipna, [
       ins[0][u:u + 1], ins[1][u:u + 1], ins[0][v:v + 1], ins[1][v:v + 1]])
-  wsums, _, _ = ref_sums(weights, wslots)
+  wsums, _, _ = gr.ref_sums(weights, wslots)
   want_w = ref_metrics('wind', case.skipna, wsums, wsum)
   assert_metrics(np.concatenate([got_wind[:2].cpu().numpy(), want_w[2:]]),
                  want_w, names, 'PairSuiteStep wind ' + tag)

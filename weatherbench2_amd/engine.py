@@ -1001,9 +1001,10 @@ def ensemble_threshold_reduce(plan: ReductionPlan, ens: torch.Tensor,
                               member_stride: int, n_member: int, ens_slab,
                               truth: torch.Tensor, truth_slab,
                               thr: torch.Tensor, thr_slab, n_outer: int,
-                              skipna: bool):
+                              skipna: bool, want_sums: bool = False):
   """Exceedance-count kernel + region fold: metrics[4, n_region, n_outer] =
-  (Brier, debiased Brier, ignorance, RPS part)."""
+  (Brier, debiased Brier, ignorance, RPS part).  With `want_sums`: (metrics,
+  the raw region sums [n_outer, n_region, K])."""
   lib = _lib.load()
   dev = plan.device
   dtype = ens.dtype
@@ -1030,13 +1031,15 @@ def ensemble_threshold_reduce(plan: ReductionPlan, ens: torch.Tensor,
       _lib.ptr(partials), stream), 'wb2_ens_threshold_partials')
   metrics = torch.empty((_lib.GENERIC_KQ[mode], plan.n_region, n_outer),
                         dtype=torch.float64, device=dev)
+  sums = (torch.empty((n_outer, plan.n_region, k), dtype=torch.float64,
+                      device=dev) if want_sums else None)
   _lib.check(lib.wb2_det_combine(
       mode, int(skipna), _lib.ptr(partials), n_outer, plan.n_chunk, plan.nwf,
       plan.n_seg, _lib.ptr(seg_eoff), n_ts, _lib.ptr(plan.band_chunk0),
       plan.n_band, _lib.ptr(plan.coef_band), _lib.ptr(plan.coef_seg),
       _lib.ptr(plan.region_wf), _lib.ptr(plan.region_wsum), plan.n_region,
-      None, _lib.ptr(metrics), stream), 'wb2_det_combine')
-  return metrics
+      _lib.ptr(sums), _lib.ptr(metrics), stream), 'wb2_det_combine')
+  return (metrics, sums) if want_sums else metrics
 
 
 RANK_MEAN_MAX_BINS = 256  # wb2_rank_histogram_mean: 64 x n_bins counts in LDS

@@ -1,6 +1,7 @@
 """Benchmark of the MI355X metric-evaluation hot path (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+                  [--full [--detail]]
 
 A "step" = one fused pass of the deterministic suite (MSE + RMSE + MAE + Bias +
 ACC for the 13 predefined slice regions of scripts/evaluate.py:345-374) over a
@@ -18,7 +19,14 @@ accumulators at the end (evaluation.py:740-744's xbeam.Mean).  Launched by
 one rank; WITHOUT that environment `--gpus N` spawns the N ranks itself.
 
 `value` is always the deterministic suite (so the N = 1, 2, 4, 8 values form one
-scaling curve); the same JSON line carries, measured in the same process:
+scaling curve).  A plain run does only what `value` needs: it sets up, warms
+up, times the K steps, writes --dump-outputs and prints the line, whose
+`roofline` then carries the algorithmic bytes and `step_frac` alone.  With
+`--full` the same JSON line also carries, measured in the same process:
+  roofline        K1's kernel time from HIP events (a sampling loop of its own)
+                  and the fraction of the HBM peak it reaches;
+  unramped        the same K steps started from an idle queue;
+  config1_full_job  N = 1: the whole configs[1] job (2920 units) in one region;
   full_suite      BASELINE configs[4]: deterministic + probabilistic (50-member
                   K3) suites over the same number of units per step, sharded
                   the same way, both [sum, count] sets all-reduced;
@@ -56,14 +64,16 @@ and on one GPU (N = 1), each with its own `roofline`:
   cpu_baseline    the NumPy oracle on this box's host cores;
 and `roofline.traffic` is collected LIVE: rocprofv3 --pmc FETCH_SIZE /
 WRITE_SIZE around the benched K1 launch (tools/live_traffic.py; --no-pmc
-skips it and quotes profiles/ instead).
+skips it and quotes profiles/ instead).  variants, k3_variants and
+tier2_variants run only with `--detail`, which implies `--full`; each --no-*
+switch skips one leg of a --full run.
 
 `--total-units N` switches to STRONG scaling (BASELINE configs[4] literally:
 2920 units, contiguous shards over the ranks, K = the steps of the largest
 shard).
 
-Prints ONE JSON line (rank 0): the compact contract line (< 4 kB).  The full
-record of every leg goes to bench_detail.json beside this file.  With
+Prints ONE JSON line (rank 0): the compact contract line (< 4 kB).  With
+--full the record of every leg goes to bench_detail.json beside this file.  With
 `--dump-outputs DIR` the headline's results (its last timed step's metrics and
 the running mean over the K timed steps) are written to DIR as .npy files.
 """
@@ -254,6 +264,12 @@ def parse_args():
                   help='distinct units resident in HBM per input')
   ap.add_argument('--rows-per-chunk', type=int, default=0,
                   help='0 = plan.auto_rows_per_chunk (32 at the default batch)')
+  ap.add_argument('--full', action='store_true',
+                  help='after the headline, also run every other leg (kernel '
+                       'time and roofline, the other BASELINE configs, API, '
+                       'PCIe, CPU baseline, live PMC traffic) and write '
+                       'bench_detail.json; a plain run measures the headline '
+                       'alone')
   ap.add_argument('--no-cpu-baseline', action='store_true')
   ap.add_argument('--no-full-suite', action='store_true',
                   help='skip the configs[4] (deterministic + probabilistic) leg')
@@ -261,7 +277,7 @@ def parse_args():
                   help='skip the drop-in API leg (N = 1 only)')
   ap.add_argument('--pcie', action='store_true',
                   help='(kept for compatibility: the pcie_inclusive leg is part '
-                       'of the default N = 1 line now)')
+                       'of the --full N = 1 line now)')
   ap.add_argument('--no-pcie', action='store_true',
                   help='skip the pcie_inclusive leg (N = 1 only)')
   ap.add_argument('--no-secondary', action='store_true',
@@ -278,9 +294,9 @@ def parse_args():
                   help='also run every other instantiation against its own '
                        'roofline (K1 / K3 / tier-2 variants, all window sizes '
                        'of the official-chunk leg, live traffic of every '
-                       'benched kernel): minutes of GPU time; the record goes '
-                       'to bench_detail.json, the last stdout line stays the '
-                       'compact contract line')
+                       'benched kernel): minutes of GPU time; implies --full; '
+                       'the record goes to bench_detail.json, the last stdout '
+                       'line stays the compact contract line')
   ap.add_argument('--print-detail', action='store_true',
                   help='also print the full record (bench_detail.json) on a '
                        'line BEFORE the contract line')
@@ -325,6 +341,7 @@ def parse_args():
                        'seeded, so two builds can be compared output for '
                        'output (deterministic workload only)')
   args = ap.parse_args()
+  args.full = args.full or args.detail
   if args.dump_outputs and (args.workload != 'deterministic' or
                             args.variants_only or args.traffic_probe):
     ap.error('--dump-outputs needs the deterministic headline (no --workload, '
@@ -623,21 +640,7 @@ def main():
     if rank == 0:
       dump_outputs(args.dump_outputs, dump)
 
-  # ---- K1's duration: HIP events around the kernel alone, on the launch
-  # stream, over the same table sets as the timed steps, in a loop of its own
-  # right behind the timed region (queue kept full by a short un-evented lead-in)
-  n_samp = min(args.steps, 24)
-  for i in range(min(8, args.steps)):
-    step(args.warmup + i)
-  for i in range(n_samp):
-    sampled_step(args.warmup + i)
-  torch.cuda.synchronize()
-  k1_ms = [a.elapsed_time(b) for a, b in k1_timer.pairs]
-  if os.environ.get('WB2_BENCH_TRACE'):  # per-launch durations (diagnostics)
-    print('k1_ms', ' '.join(f'{x:.3f}' for x in k1_ms), file=sys.stderr)
-  k1_avg_s = (float(np.mean(k1_ms)) if k1_ms else float('nan')) / 1e3
   pts_step = units * PTS_PER_UNIT
-  achieved = pts_step * BYTES_PER_PT / k1_avg_s / 1e9
   job_pts = (args.total_units * PTS_PER_UNIT if strong
              else world * pts_step * args.steps)
   out = {
@@ -672,30 +675,56 @@ def main():
           'collectives': ({
               'time_mean_allreduce ([sum,count], in every timed region)':
                   'rccl' if backend == 'nccl' else f'{backend} via host copies',
-              'map_allreduce': 'rccl' if backend == 'nccl' else
-                               f'{backend} via host copies',
               'timing max-over-ranks / barriers':
                   'rccl' if backend == 'nccl' else backend} if ddp else None),
       },
       'roofline': {
           'bound': 'hbm', 'kernel': 'stream_partials_kernel<float,4,DET_ACC>',
-          'achieved': achieved, 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
-          'frac': achieved / HBM_PEAK_GBPS,
-          'frac_of_measured_copy_6290': achieved / 6290.0,
-          'kernel_ms': k1_avg_s * 1e3,
-          'kernel_ms_samples': len(k1_ms),
-          'kernel_ms_from': ('HIP events around K1 alone on the launch stream, '
-                             f'{len(k1_ms)} launches of the timed table sets in '
-                             'a loop right behind the timed region'),
+          'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
           'algorithmic_bytes_per_launch': pts_step * BYTES_PER_PT,
           # whole-step view: algorithmic bytes / the timed ms_per_step (K1 + K2
           # + accumulate + whatever the host adds) against the same peak
           'step_frac': (pts_step * BYTES_PER_PT / (dt / args.steps) / 1e9 /
                         HBM_PEAK_GBPS) if not strong else None,
-          # HBM bytes per launch from PMC counters: collected below, live
-          'traffic': None,
       },
   }
+
+  def finish():
+    if rank == 0:
+      emit(out, args)
+    if ddp:
+      dist.barrier()
+      dist.destroy_process_group()
+
+  if not args.full:  # every figure below takes GPU runs of its own
+    finish()
+    return
+
+  # ---- K1's duration: HIP events around the kernel alone, on the launch
+  # stream, over the same table sets as the timed steps, in a loop of its own
+  # right behind the timed region (queue kept full by a short un-evented lead-in)
+  n_samp = min(args.steps, 24)
+  for i in range(min(8, args.steps)):
+    step(args.warmup + i)
+  for i in range(n_samp):
+    sampled_step(args.warmup + i)
+  torch.cuda.synchronize()
+  k1_ms = [a.elapsed_time(b) for a, b in k1_timer.pairs]
+  if os.environ.get('WB2_BENCH_TRACE'):  # per-launch durations (diagnostics)
+    print('k1_ms', ' '.join(f'{x:.3f}' for x in k1_ms), file=sys.stderr)
+  k1_avg_s = (float(np.mean(k1_ms)) if k1_ms else float('nan')) / 1e3
+  achieved = pts_step * BYTES_PER_PT / k1_avg_s / 1e9
+  out['roofline'].update({
+      'achieved': achieved, 'frac': achieved / HBM_PEAK_GBPS,
+      'frac_of_measured_copy_6290': achieved / 6290.0,
+      'kernel_ms': k1_avg_s * 1e3,
+      'kernel_ms_samples': len(k1_ms),
+      'kernel_ms_from': ('HIP events around K1 alone on the launch stream, '
+                         f'{len(k1_ms)} launches of the timed table sets in '
+                         'a loop right behind the timed region'),
+      # HBM bytes per launch from PMC counters: collected below, live
+      'traffic': None,
+  })
 
   # ---- the un-ramped figure: the same K steps right after an idle queue ------
   torch.cuda.synchronize()
@@ -757,6 +786,8 @@ def main():
                                    timed_region, per_rank, world, rank)
   if ddp:
     out['map_allreduce'] = map_allreduce(dev, all_reduce, world, backend)
+    out['ranks']['collectives']['map_allreduce'] = (
+        'rccl' if backend == 'nccl' else f'{backend} via host copies')
   if solo and not args.no_api:
     leg('api', api_leg, dev, regions, units)
     # ---- the boundary at the reference's PRODUCTION chunking: init_time=1,
@@ -860,10 +891,7 @@ def main():
             'sample': (f'NumPy oracle in-process, {one["units"]} unit(s) in '
                        f'{one["seconds"]:.1f} s (the multi-process leg failed: '
                        f'{type(e).__name__}: {e})')}
-    emit(out, args)
-  if ddp:
-    dist.barrier()
-    dist.destroy_process_group()
+  finish()
 
 
 DUMP_LIMIT = 64 << 20  # bytes: the whole of --dump-outputs
@@ -890,7 +918,7 @@ def _pick(d, *keys):
 
 def compact(out: dict) -> dict:
   """The CONTRACT line: the headline with its roofline and cpu_baseline, and
-  one-number summaries of the other legs.  Everything else lives in
+  one-number summaries of the other legs (--full).  Everything else lives in
   bench_detail.json (printed on the line before)."""
   line = _pick(out, 'metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup',
                'ms_per_step', 'gpu_ms_per_step', 'higher_is_better', 'scaling',
@@ -908,7 +936,8 @@ def compact(out: dict) -> dict:
                                  'value_1core', 'logical_cores')
     line['cpu_baseline']['sample'] = cb.get('sample_short') or str(
         cb.get('sample', ''))[:200]
-  line['unramped'] = _pick(out.get('unramped', {}), 'value', 'ms_per_step')
+  if 'unramped' in out:
+    line['unramped'] = _pick(out['unramped'], 'value', 'ms_per_step')
   if 'config1_full_job' in out:
     line['config1_full_job'] = _pick(out['config1_full_job'], 'value', 'units',
                                      'steps', 'ms', 'vs_headline', 'error')
@@ -991,25 +1020,24 @@ def compact(out: dict) -> dict:
   errors = [k for k, v in out.items() if isinstance(v, dict) and 'error' in v]
   if errors:
     line['errors'] = errors
-  line['detail'] = DETAIL_FILE
   return line
 
 
 def emit(out: dict, args) -> None:
-  """Writes the full record to bench_detail.json (repo root, and gpurun_out/
-  when that exists) and prints the contract line -- ONE JSON object of less
-  than LINE_LIMIT bytes, the last (by default the only) stdout line."""
+  """Prints the contract line -- ONE JSON object of less than LINE_LIMIT bytes,
+  the last (by default the only) stdout line; with --full the full record goes
+  to bench_detail.json beside this file first."""
   detail = json.dumps(out)
-  for d in (ROOT, os.path.join(ROOT, 'gpurun_out')):
-    if os.path.isdir(d):
-      try:
-        with open(os.path.join(d, DETAIL_FILE), 'w') as f:
-          f.write(detail + '\n')
-      except OSError:
-        pass
+  line = compact(out)
+  if args.full:
+    try:
+      with open(os.path.join(ROOT, DETAIL_FILE), 'w') as f:
+        f.write(detail + '\n')
+      line['detail'] = DETAIL_FILE
+    except OSError:
+      pass
   if args.print_detail:
     print('bench_detail ' + detail)
-  line = compact(out)
   text = json.dumps(line)
   if len(text) >= LINE_LIMIT:  # shed the optional summaries, never the contract
     for key in ('pcie_inclusive', 'api', 'unramped', 'api_probabilistic',

@@ -23,8 +23,8 @@ def test_self_launched_two_ranks_on_one_gpu():
   out = subprocess.run(
       [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps',
        '3', '--warmup', '1', '--units', '2', '--pool', '4', '--ramp-ms', '0',
-       '--no-cpu-baseline'], env=env, cwd=ROOT, capture_output=True, text=True,
-      timeout=900)
+       '--full', '--no-cpu-baseline'], env=env, cwd=ROOT, capture_output=True,
+      text=True, timeout=900)
   assert out.returncode == 0, out.stderr[-2000:]
   line = json.loads(out.stdout.strip().splitlines()[-1])
   assert line['n_gpus'] == 2 and line['steps'] == 3 and line['warmup'] == 1
@@ -56,8 +56,8 @@ def test_torchrun_single_rank_uses_rccl():
        '--nproc-per-node', '1', '--master-addr', '127.0.0.1', '--master-port',
        str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3',
        '--warmup', '1', '--units', '2', '--pool', '4', '--ramp-ms', '0',
-       '--no-cpu-baseline', '--no-api', '--no-secondary', '--no-pcie',
-       '--no-pmc'], env=env, cwd=ROOT, capture_output=True,
+       '--full', '--no-cpu-baseline', '--no-api', '--no-secondary',
+       '--no-pcie', '--no-pmc'], env=env, cwd=ROOT, capture_output=True,
       text=True, timeout=900)
   assert out.returncode == 0, out.stderr[-2000:]
   line = json.loads([l for l in out.stdout.strip().splitlines()
@@ -81,7 +81,7 @@ def test_strong_scaling_shards_a_fixed_number_of_units():
   out = subprocess.run(
       [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2',
        '--total-units', '5', '--warmup', '1', '--units', '2', '--pool', '4',
-       '--ramp-ms', '0', '--no-cpu-baseline'], env=env, cwd=ROOT,
+       '--ramp-ms', '0', '--full', '--no-cpu-baseline'], env=env, cwd=ROOT,
       capture_output=True, text=True, timeout=900)
   assert out.returncode == 0, out.stderr[-2000:]
   line = json.loads(out.stdout.strip().splitlines()[-1])
@@ -104,16 +104,16 @@ def _clean_env():
 
 
 def test_contract_line_is_one_small_json_object():
-  """The driver's exact command shape (`python3 bench.py --gpus 1 --steps K
-  --warmup W`, every leg on, few steps): the LAST stdout line is one JSON
-  object of less than 4 kB that carries the contract's keys, `roofline` and
-  `cpu_baseline`; everything else is in bench_detail.json beside bench.py."""
+  """The full run (`python3 bench.py --gpus 1 --steps K --warmup W --full`,
+  every leg on, few steps): the LAST stdout line is one JSON object of less
+  than 4 kB that carries the contract's keys, `roofline` and `cpu_baseline`;
+  everything else is in bench_detail.json beside bench.py."""
   detail_path = os.path.join(ROOT, 'bench_detail.json')
   if os.path.exists(detail_path):
     os.remove(detail_path)
   out = subprocess.run(
       [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1',
-       '--steps', '8', '--warmup', '2'],
+       '--steps', '8', '--warmup', '2', '--full'],
       env=_clean_env(), cwd=ROOT, capture_output=True, text=True, timeout=1500)
   assert out.returncode == 0, out.stderr[-2000:]
   lines = out.stdout.strip().splitlines()
@@ -165,6 +165,37 @@ def test_contract_line_is_one_small_json_object():
       'all_inputs_over_pcie']['value']
   # the step is one C-ABI call: its timed ms tracks the kernel
   assert line['ms_per_step'] < 1.5 * roof['kernel_ms'] + 0.1
+
+
+def test_plain_run_is_the_headline_alone():
+  """`python3 bench.py --gpus 1 --steps K --warmup W` without --full: the one
+  line carries the headline and nothing that takes a run of its own (no other
+  leg, no K1 event timing), and no bench_detail.json is written."""
+  detail_path = os.path.join(ROOT, 'bench_detail.json')
+  if os.path.exists(detail_path):
+    os.remove(detail_path)
+  out = subprocess.run(
+      [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1',
+       '--steps', '8', '--warmup', '2'],
+      env=_clean_env(), cwd=ROOT, capture_output=True, text=True, timeout=900)
+  assert out.returncode == 0, out.stderr[-2000:]
+  line = json.loads(out.stdout.strip().splitlines()[-1])
+  assert line['metric'] == 'grid-point-evals/sec (721x1440x13)'
+  assert line['unit'] == 'grid-point-evals/s' and line['higher_is_better']
+  assert line['dtype'] == 'f32 (elementwise) + f64 (sums)'
+  assert line['n_gpus'] == 1 and line['steps'] == 8 and line['warmup'] == 2
+  pts = 16 * 13 * 721 * 1440 * 8
+  assert abs(line['value'] - pts / (line['ms_per_step'] * 8e-3)) < 1e-6 * line[
+      'value']
+  roof = line['roofline']
+  assert roof['algorithmic_bytes_per_launch'] == 16 * 13 * 721 * 1440 * 12
+  assert 0 < roof['step_frac'] < 1
+  assert 'kernel_ms' not in roof and 'traffic' not in roof
+  for key in ('cpu_baseline', 'unramped', 'config1_full_job', 'full_suite',
+              'ensemble', 'spectrum', 'api', 'api_official_chunk',
+              'api_probabilistic', 'pcie_inclusive', 'detail', 'errors'):
+    assert key not in line, key
+  assert not os.path.exists(detail_path)
 
 
 def test_detail_run_carries_every_instantiation():

@@ -31,7 +31,7 @@ def test_bench_two_ranks_over_rccl():
     env.pop(k, None)
   out = subprocess.run(
       [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps',
-       '5', '--warmup', '2', '--no-secondary', '--no-cpu-baseline'],
+       '5', '--warmup', '2', '--full', '--no-secondary', '--no-cpu-baseline'],
       env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
   assert out.returncode == 0, out.stderr[-2000:]
   line = json.loads(out.stdout.strip().splitlines()[-1])
@@ -60,7 +60,8 @@ def test_strong_scaling_2920_units_over_two_ranks():
     env.pop(k, None)
   out = subprocess.run(
       [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2',
-       '--total-units', '2920', '--warmup', '3', '--no-cpu-baseline'],
+       '--total-units', '2920', '--warmup', '3', '--full',
+       '--no-cpu-baseline'],
       env=env, cwd=ROOT, capture_output=True, text=True, timeout=1500)
   assert out.returncode == 0, out.stderr[-2000:]
   last = out.stdout.strip().splitlines()[-1]

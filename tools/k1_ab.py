@@ -3,7 +3,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for rep in range(2):
   for lib in sorted(glob.glob(os.path.join(ROOT, 'build', 'variants', 'k1_*.so'))):
     env = dict(os.environ, WB2HIP_LIB=lib)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--no-cpu-baseline', '--steps', '20'],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--no-cpu-baseline', '--steps', '20'],
                        env=env, capture_output=True, text=True)
     try:
       d = json.loads(r.stdout.strip().splitlines()[-1])

@@ -1,7 +1,7 @@
 # The evidence of a round, collected on the GPU box into gpurun_out/profiles_rNN/
 # (copy what is to be judged into profiles/):
 #   bash tools/round_profile.sh r05 [quick]
-# * the contract line of the default command (what the driver runs) and its
+# * the contract line of the full run (--full, every leg) and its
 #   bench_detail.json; the same with --detail (every variant set);
 # * rocprofv3 --kernel-trace --stats summaries of the default command and of
 #   every workload (the average kernel durations the rooflines must agree
@@ -13,7 +13,7 @@ cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/profiles_$R
 mkdir -p $OUT
 export TMPDIR=/tmp
-( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${R}_bench_default_line.json 2> $OUT/bench.err ) 2>&1 | grep real
+( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/${R}_bench_default_line.json 2> $OUT/bench.err ) 2>&1 | grep real
 cp bench_detail.json $OUT/${R}_bench_detail_default.json
 ( time timeout 1500 python bench.py --detail > $OUT/${R}_bench_detail_line.json 2>> $OUT/bench.err ) 2>&1 | grep real
 cp bench_detail.json $OUT/${R}_bench_detail.json
@@ -26,7 +26,7 @@ stats() {  # name, command...
   rm -rf /tmp/prof_$name
 }
 B=$GRAFT_REPO_ROOT/bench.py
-stats default python $B --no-pmc --no-cpu-baseline
+stats default python $B --full --no-pmc --no-cpu-baseline
 if [ "$2" != quick ]; then
   stats deterministic python $B --no-pmc --no-cpu-baseline --no-secondary --no-api --no-pcie --no-full-suite
   for w in ensemble spectrum spectrum_materialized spectrum_mean spectrum_materialized_f64 spectrum_mean_f64; do

@@ -158,11 +158,11 @@ def test_fused_kernel_time_mean(n_lon, skipna):
 @pytest.mark.parametrize('skipna', [True, False])
 @pytest.mark.parametrize('n_lon,n_lev', [(1440, 13), (1440, 5), (256, 13)])
 def test_fused_time_mean_tail_is_bit_identical(n_lon, n_lev, skipna):
-  """More output rows than resident waves: the last partial round of the time
-  mean is taken apart into single transforms and averaged by a second kernel
-  (spectrum_fused.hip launch_time_mean).  Whether or not the split applies on
-  this device, every output row must be BIT-identical to the time-ordered fp64
-  sum of the materialised spectra divided by the count."""
+  """More output rows than resident waves, so that the last round of the
+  fused time mean keeps only part of the waves busy.  Every output row must be
+  BIT-identical to the time-ordered fp64 sum of the materialised spectra
+  divided by the count: the fused kernel computes each row's spectra exactly
+  as the materialising one does and adds them in time order."""
   import torch
   from weatherbench2_amd import engine
   dev = torch.device('cuda')

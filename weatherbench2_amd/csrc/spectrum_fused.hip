@@ -260,7 +260,9 @@ __global__ void __launch_bounds__(64 * WB2_FFT_NWAVE)
   Task next_task = task_of(orow_first < rows_out ? orow_first : 0);
   for (long long orow_i = orow_first; orow_i < rows_out; orow_i += stride) {
     double sum1[NIT], sum2[NIT];
-    int cnt[NIT];  // TIME + skipna: valid spectra, bin k (low half) / N2 - k
+    // TIME: valid spectra, bin k (low 16 bits) / N2 - k (high 16 bits);
+    // unsigned, so that 65535 samples in the high half stay positive
+    unsigned cnt[NIT];
 #pragma unroll
     for (int i = 0; i < NIT; ++i) {
       sum1[i] = sum2[i] = 0.0;
@@ -352,7 +354,7 @@ __global__ void __launch_bounds__(64 * WB2_FFT_NWAVE)
               const bool k2 = !(p.skipna && is_nan(v2));
               sum1[i] += k1 ? v1 : 0.0;
               sum2[i] += k2 ? v2 : 0.0;
-              cnt[i] += (k1 ? 1 : 0) + (k2 ? 0x10000 : 0);
+              cnt[i] += (k1 ? 1u : 0u) + (k2 ? 0x10000u : 0u);
             } else if constexpr (MODE == LATSEG) {
               sum1[i] += v1;
               sum2[i] += v2;

@@ -945,9 +945,12 @@ def zonal_spectrum_lat_mean(x: torch.Tensor, circumference: torch.Tensor,
   out_shape = tuple(x.shape[:-2]) + (n_bins,)
   if n_seg == 0 or x.data_ptr() % 16:
     spec = zonal_spectrum(x, circumference, n_lat)
-    total, _, count = axis_moments(spec.reshape(n_field, n_lat, n_bins), n_field,
-                                   n_lat, n_bins, w, False)
-    return (total / count).reshape(out_shape)
+    total, _, _ = axis_moments(spec.reshape(n_field, n_lat, n_bins), n_field,
+                               n_lat, n_bins, w, False)
+    # the count of axis_moments is n_lat: divide by the weights' sum instead
+    if weight_sum is not None:
+      return (total / float(weight_sum)).reshape(out_shape)
+    return (total / w.sum()).reshape(out_shape)
   if row_weight is None:
     row_weight = (w * circumference.to(torch.float64)).contiguous()
   # without a host-side sum the normalisation stays on the device (no sync):
@@ -1167,10 +1170,12 @@ def seeps_map(inputs: t.Sequence[torch.Tensor],
 
 def axis_moments(x: torch.Tensor, n_lead: int, n_red: int, n_tail: int,
                  w_red: t.Optional[torch.Tensor], skipna: bool,
-                 want_sq: bool = False, w_repeat: int = 1):
+                 want_sq: bool = False, w_repeat: int = 1,
+                 n_split: t.Optional[int] = None):
   """wb2_axis_moments on a contiguous [n_lead, n_red, n_tail] view of `x`:
   (sum, sumsq or None, count) as float64 tensors of n_lead * n_tail.  `w_red`
-  holds n_red / w_repeat weights, each shared by w_repeat consecutive r."""
+  holds n_red / w_repeat weights, each shared by w_repeat consecutive r.
+  `n_split` slices of the reduced axis (None: wb2_axis_moments_splits)."""
   lib = _lib.load()
   dev = x.device
   if x.dtype not in _DTYPES or not x.is_contiguous():
@@ -1181,8 +1186,9 @@ def axis_moments(x: torch.Tensor, n_lead: int, n_red: int, n_tail: int,
                             or w_red.numel() * w_repeat != n_red):
     raise ValueError('w_red must be float64[n_red / w_repeat]')
   n_out = n_lead * n_tail
-  n_split = lib.wb2_axis_moments_splits(n_lead, n_red, n_tail,
-                                        w_repeat if w_red is not None else 1)
+  if n_split is None:
+    n_split = lib.wb2_axis_moments_splits(n_lead, n_red, n_tail,
+                                          w_repeat if w_red is not None else 1)
   work = torch.empty((3 * n_split * max(n_out, 1),), dtype=torch.float64,
                      device=dev)
   total = torch.empty((n_out,), dtype=torch.float64, device=dev)

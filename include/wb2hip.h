@@ -742,10 +742,12 @@ int wb2_energy_score(int dtype, int skipna, const void* ens,
  *   Outputs are [n_outer][n_point].
  * wb2_spatial_accumulate: the temporal mean of those maps (Metric.compute
  *   :117-138; xbeam.Mean evaluation.py:740-744) without materialising them:
- *   adds, for every (rest, point), the sum over the chunk's n_time steps of
- *   d, d^2, |d| (d = forecast - truth in the input dtype) to
- *   sum[3][n_rest][n_point] (order bias, mse, mae) and, when skipna, the number
- *   of non-NaN terms to count[3][n_rest][n_point].  Slab of (time i, rest j) =
+ *   adds, for every (rest, point), the chunk's n_time steps of d, d^2, |d|
+ *   (d = forecast - truth in the input dtype) to sum[3][n_rest][n_point]
+ *   (order bias, mse, mae) and, when skipna, the number of non-NaN terms to
+ *   count[3][n_rest][n_point].  The sums CONTINUE from the accumulators value
+ *   by value (sum = ((sum + v_0) + v_1) ...), as in
+ *   wb2_spatial_accumulate_addr.  Slab of (time i, rest j) =
  *   table[i * n_rest + j] (identity when NULL).
  * wb2_spatial_accumulate_addr: the same for EVERY variable of a chunk (or of a
  *   window of chunks) in one launch, into accumulators that are separate

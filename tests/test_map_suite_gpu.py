@@ -113,12 +113,22 @@ def test_a_subset_of_the_maps_in_another_order(monkeypatch):
 
 
 def test_float64_inputs_and_the_unaligned_layout(monkeypatch):
-  """float64 chunks on a grid whose slabs are not 16-byte multiples (19 x 37
-  float64 is, 19 x 37 float32 is not: both run, the second without vector
-  loads)."""
-  from weatherbench2_amd import evaluation
-  for dtype in (np.float64, np.float32):
-    _, _, gf, gt, cfg = _setup(n_init=3, n_lead=2, n_lat=19, n_lon=37,
+  """float64 chunks on 19 x 36 (684 points, 5 472-byte slabs: an even point
+  count on 16-byte slabs, so the suite's launch takes the two-wide vector
+  path) and on 19 x 37 (703 points, 5 624 bytes: the scalar path), and
+  float32 on 19 x 37 (2 812 bytes: the scalar path too)."""
+  from weatherbench2_amd import _lib, evaluation
+  lib = _lib.load()
+  real = lib.wb2_spatial_accumulate_addr
+  aligned = []
+
+  def spy(*args):
+    aligned.append(args[2])
+    return real(*args)
+  monkeypatch.setattr(lib, 'wb2_spatial_accumulate_addr', spy)
+  for dtype, n_lon, vector in ((np.float64, 36, 1), (np.float64, 37, 0),
+                               (np.float32, 37, 0)):
+    _, _, gf, gt, cfg = _setup(n_init=3, n_lead=2, n_lat=19, n_lon=n_lon,
                                dtype=dtype)
     chunks = oc.chunk_pairs(gf, gt)
     monkeypatch.setenv('WB2HIP_CHUNK_PROGRAM', '0')
@@ -126,10 +136,12 @@ def test_float64_inputs_and_the_unaligned_layout(monkeypatch):
                                       batch_chunks=1)
     monkeypatch.setenv('WB2HIP_CHUNK_PROGRAM', '1')
     calls = _count_runs(monkeypatch)
+    del aligned[:]
     got = evaluation.evaluate_chunks(chunks, cfg, False, prefetch=0,
                                      batch_chunks=2)
     _same(got, want)
     assert calls
+    assert aligned and set(aligned) == {vector}, (dtype, n_lon, aligned)
 
 
 @pytest.mark.parametrize('skipna', [False, True])

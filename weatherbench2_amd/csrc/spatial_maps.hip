@@ -108,12 +108,18 @@ __global__ void __launch_bounds__(256)
   if (q >= p.n_point) return;
   const long long j = blockIdx.y + (long long)blockIdx.z * gridDim.y;
   if (j >= p.n_rest) return;
+  const long long plane = p.n_rest * p.n_point;
+  const long long off = j * p.n_point + q;
+  // the sums continue from the accumulators, value by value in time order
+  // (as in spatial_accumulate_addr_kernel): how many steps one call brings
+  // does not change a bit
   double s[3][VEC], c[VEC];
 #pragma unroll
-  for (int e = 0; e < VEC; ++e) {
-    s[0][e] = s[1][e] = s[2][e] = 0.0;
-    c[e] = 0.0;
-  }
+  for (int m = 0; m < 3; ++m)
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) s[m][e] = p.sum[m * plane + off + e];
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) c[e] = 0.0;
   constexpr int U = 4;  // time steps in flight (8 x 16 B per thread)
   long long i = 0;
   auto body = [&](const T (&f)[VEC], const T (&t)[VEC]) {
@@ -153,12 +159,10 @@ __global__ void __launch_bounds__(256)
                        slab(p.t_slab, i) * p.n_point + q, t);
     body(f, t);
   }
-  const long long plane = p.n_rest * p.n_point;
-  const long long off = j * p.n_point + q;
 #pragma unroll
   for (int m = 0; m < 3; ++m)
 #pragma unroll
-    for (int e = 0; e < VEC; ++e) p.sum[m * plane + off + e] += s[m][e];
+    for (int e = 0; e < VEC; ++e) p.sum[m * plane + off + e] = s[m][e];
   if constexpr (SKIPNA) {
 #pragma unroll
     for (int m = 0; m < 3; ++m)  // same NaN pattern for d, d^2, |d|

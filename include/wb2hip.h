@@ -937,6 +937,75 @@ int wb2_comm_destroy(void* comm);
 int wb2_time_mean_allreduce(double* sum, double* count, int64_t n, void* comm,
                             void* stream);
 
+/*
+ * K8: derived variables materialised as one more field of a chunk
+ * (weatherbench2/derived_variables.py).  Streaming maps; slab o of an input is
+ * `base + table[o] * slab elements` (identity when the table is NULL), so that
+ * strided views, gathers and the variables of a chunk are read where they lie.
+ *
+ * wb2_derived_pointwise
+ *   WB2_POINT_WIND_SPEED         out = sqrt(a * a + b * b), three correctly
+ *     rounded operations in `dtype` (WindSpeed :76-99; out_dtype == dtype):
+ *     bit-identical to NumPy.
+ *   WB2_POINT_RELATIVE_HUMIDITY  a = temperature (K), b = specific humidity,
+ *     slab_scalar[o] (DEV, n_slab values of out_dtype) = pressure (hPa) of slab
+ *     o (RelativeHumidity :433-468).  The vapour-pressure and mixing-ratio
+ *     terms are evaluated in `dtype`, everything the pressure enters in
+ *     out_dtype = the dtype NumPy gives (input op pressure coordinate).
+ *   out is [n_slab][n_point] of out_dtype.
+ */
+#define WB2_POINT_WIND_SPEED 0
+#define WB2_POINT_RELATIVE_HUMIDITY 1
+int wb2_derived_pointwise(int mode, int dtype, int out_dtype, const void* a,
+                          const int64_t* a_slab, const void* b,
+                          const int64_t* b_slab, const void* slab_scalar,
+                          int64_t n_slab, int64_t n_point, void* out,
+                          void* stream);
+
+/*
+ * wb2_derived_stencil: the horizontal derivatives _d_dx / _d_dy (:102-121) of
+ * (n_row, n_col) slabs and what the reference combines them into.
+ *   inputs[0]  DEV the field differentiated along longitude
+ *   inputs[1]  DEV the field differentiated along latitude
+ *   inputs[2], inputs[3]  DEV u and v, read pointwise (WB2_STENCIL_AGEO_* only)
+ *   slabs      HOST array of 4 DEV int64[n_slab] tables (or NULL / NULL entries)
+ *   lat_rows   != 0: rows are latitudes (…, latitude, longitude); 0: columns are
+ *   row_coef, col_coef  DEV double[4][n]: a, b, c, den of np.gradient(f, x,
+ *     edge_order=1) along the axis.  Where the axis is uniform (np.diff(x)
+ *     exactly constant; *_uniform != 0) and at both ends of any axis
+ *       g[i] = dtype(double(f[min(i+1, n-1)] - f[max(i-1, 0)]) / den[i])
+ *     (the difference formed in `dtype`), elsewhere
+ *       g[i] = dtype(a[i] f[i-1] + b[i] f[i] + c[i] f[i+1])   (in double).
+ *   lat_cos, lat_coriolis  DEV double[n_lat]: cos(lat) and 2 Omega sin(lat)
+ *     (the latter for the geostrophic modes only).  d/dx is
+ *     g_lon / cos / m_per_deg, 0.0 where cos <= 1e-6 (_zero_poles); d/dy is
+ *     g_lat / m_per_deg in `dtype`.  Division by a zero Coriolis parameter is
+ *     NOT hidden: the equator row is +-inf / NaN like the reference's.
+ *   out  DEV double[n_slab][n_row][n_col].
+ * Both axes need at least two points (np.gradient).
+ * wb2_derived_stencil_geometry: columns per workgroup tile and rows per row
+ * chunk of that kernel (wide != 0: 16-byte loads; rows that are a multiple of
+ * 16 / sizeof(dtype) long and 16-byte aligned buffers).
+ */
+#define WB2_STENCIL_DIVERGENCE 0  /* d/dx in0 + d/dy in1   :124-125 */
+#define WB2_STENCIL_VORTICITY 1   /* d/dx in0 - d/dy in1   :128-129 */
+#define WB2_STENCIL_GEO_U 2       /* -d/dy in1 / f         :231-244 */
+#define WB2_STENCIL_GEO_V 3       /* +d/dx in0 / f */
+#define WB2_STENCIL_GEO_SPEED 4
+#define WB2_STENCIL_AGEO_U 5      /* u - u_geo             :313-338 */
+#define WB2_STENCIL_AGEO_V 6
+#define WB2_STENCIL_AGEO_SPEED 7
+int wb2_derived_stencil(int mode, int dtype, int lat_rows,
+                        const void* const* inputs,
+                        const int64_t* const* slabs, int64_t n_slab,
+                        int32_t n_row, int32_t n_col, const double* row_coef,
+                        int row_uniform, const double* col_coef,
+                        int col_uniform, const double* lat_cos,
+                        const double* lat_coriolis, double m_per_deg,
+                        double* out, void* stream);
+int wb2_derived_stencil_geometry(int dtype, int wide, int32_t* tile_cols,
+                                 int32_t* chunk_rows);
+
 #ifdef __cplusplus
 }
 #endif

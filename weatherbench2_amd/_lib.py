@@ -177,6 +177,13 @@ _SIGNATURES = {
     'wb2_comm_init_rank': (_int, [_vp, _i32, _i32, _c.POINTER(_vp)]),
     'wb2_comm_destroy': (_int, [_vp]),
     'wb2_time_mean_allreduce': (_int, [_vp, _vp, _i64, _vp, _vp]),
+    'wb2_derived_pointwise': (_int, [_int, _int, _int, _vp, _vp, _vp, _vp, _vp,
+                                     _i64, _i64, _vp, _vp]),
+    'wb2_derived_stencil': (_int, [
+        _int, _int, _int, _c.POINTER(_vp), _c.POINTER(_vp), _i64, _i32, _i32,
+        _vp, _int, _vp, _int, _vp, _vp, _c.c_double, _vp, _vp]),
+    'wb2_derived_stencil_geometry': (_int, [_int, _int, _c.POINTER(_i32),
+                                            _c.POINTER(_i32)]),
 }
 
 _lib = None

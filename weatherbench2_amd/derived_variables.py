@@ -1,13 +1,30 @@
 """GPU derived variables with the reference's `DerivedVariable` protocol.
 
-Only `ZonalEnergySpectrum` is on the hot path (weatherbench2/
-derived_variables.py:531-626, driven by scripts/compute_zonal_energy_spectrum.py);
-the other derived variables are stencil/scan ops computed before the metric
-loop and stay on the host.
+Every class of weatherbench2/derived_variables.py that acts inside one
+`init_time=1,lead_time=1` chunk on single fields or horizontal neighbours is
+here, with the reference's names, dataclass fields and defaults, and is
+computed by a HIP kernel (csrc/derived_fields.hip):
+
+  pointwise           WindSpeed, RelativeHumidity
+  horizontal stencil  WindDivergence, WindVorticity, GeostrophicWindSpeed,
+                      U/VComponentOfGeostrophicWind, AgeostrophicWindSpeed,
+                      U/VComponentOfAgeostrophicWind
+
+They MATERIALISE their result as one more field of the chunk, in the dtype the
+reference's NumPy expression gives; `evaluation.evaluate_chunks` computes them
+once per chunk where the chunk enters the window, so that chunk programs and
+windows treat them as ordinary variables.
+`ZonalEnergySpectrum` (derived_variables.py:531-626, driven by
+scripts/compute_zonal_energy_spectrum.py) is the spectral one.
+
+Not here: the level-column classes (TotalColumnWater,
+IntegratedWaterTransport, LapseRate, VerticalVelocity, EddyKineticEnergy) and
+the two precipitation accumulations, which act along lead time.
 """
 from __future__ import annotations
 
 import dataclasses
+import threading
 import typing as t
 
 import numpy as np
@@ -15,6 +32,7 @@ import torch
 
 from weatherbench2_amd import engine
 from weatherbench2_amd import feeder
+from weatherbench2_amd import plan as plan_lib
 from weatherbench2_amd import xarray_lite as xl
 
 EARTH_RADIUS_M = 1000 * (6357 + 6378) / 2  # schema.py:59
@@ -134,6 +152,425 @@ class ZonalEnergySpectrum(DerivedVariable):
       result = xl.DataArray(np.ascontiguousarray(result.data), ref_dims,
                             coords, self.variable_name)
     return result
+
+
+# ---------------------------------------------------------------------------
+# Materialising derived variables (csrc/derived_fields.hip)
+# ---------------------------------------------------------------------------
+def _on_device(data) -> bool:
+  if isinstance(data, xl.SlabGather):
+    data = data.base
+  elif isinstance(data, xl.SlabConcat):
+    data = data.bases[0]
+  return isinstance(data, torch.Tensor) and data.is_cuda
+
+
+def _float_dtype(*dtypes) -> torch.dtype:
+  """float32 if every input is float32, float64 otherwise (integers square
+  to integers and take their root in float64)."""
+  as_np = [np.dtype(str(d).replace('torch.', '')) if isinstance(d, torch.dtype)
+           else np.dtype(d) for d in dtypes]
+  return torch.float32 if all(d == np.float32 for d in as_np) else torch.float64
+
+
+def _coord_values(dataset: xl.Dataset, name: str) -> np.ndarray:
+  c = dataset.coords[name]
+  return np.asarray(c.values if isinstance(c, xl.DataArray) else c)
+
+
+def _stride_table(x: torch.Tensor, n_inner: int):
+  """Slab table of a strided view whose inner blocks (the last `n_inner` dims)
+  are contiguous and whose outer strides are whole blocks; None otherwise."""
+  n_outer = x.dim() - n_inner
+  inner, expect = 1, 1
+  for n, s in zip(reversed(x.shape[n_outer:]), reversed(x.stride()[n_outer:])):
+    if n != 1 and s != expect:
+      return None
+    expect *= n
+    inner *= n
+  if inner == 0 or any(s < 0 or s % inner for s in x.stride()[:n_outer]):
+    return None
+  table = np.zeros(tuple(x.shape[:n_outer]), dtype=np.int64)
+  for ax, (n, s) in enumerate(zip(x.shape[:n_outer], x.stride()[:n_outer])):
+    shape = [1] * n_outer
+    shape[ax] = n
+    table = table + (np.arange(n, dtype=np.int64) * (s // inner)).reshape(shape)
+  return table.ravel()
+
+
+def _operand(da: xl.DataArray, order: tuple, device, dtype: torch.dtype,
+             n_inner: int):
+  """(device tensor, slab table or None) of `da` with its dims in `order`:
+  read where it lies when its blocks of the last `n_inner` dims are intact (a
+  contiguous tensor, a strided view of whole blocks, a gather over a resident
+  base), copied otherwise."""
+  if da.dims != tuple(order):
+    da = da.transpose(*order)
+  data = da.data
+  if (isinstance(data, xl.SlabGather) and n_inner == 2
+      and isinstance(data.base, torch.Tensor) and data.base.is_cuda
+      and data.base.dtype == dtype and data.base.is_contiguous()
+      and not data.has_missing):
+    return data.base, data.index.ravel()
+  if isinstance(data, (xl.SlabGather, xl.SlabConcat)):
+    data = data.materialize(device)
+  if isinstance(data, torch.Tensor) and data.device == device:
+    ten = data if data.dtype == dtype else data.to(dtype)
+  else:
+    ten = engine.as_device_tensor(data, device)
+    ten = ten if ten.dtype == dtype else ten.to(dtype)
+  if ten.is_contiguous():
+    return ten, None
+  table = _stride_table(ten, n_inner)
+  if table is None:
+    return ten.contiguous(), None
+  return ten, table
+
+
+def _table_tensor(table, device):
+  return None if table is None else engine.upload_table(table, device)
+
+
+def _result_coords(dataset: xl.Dataset, dims: tuple) -> dict:
+  return {k: v for k, v in dataset.coords.items()
+          if (set(v.dims) <= set(dims) if isinstance(v, xl.DataArray)
+              else k in dims)}
+
+
+@dataclasses.dataclass
+class _MaterializedVariable(DerivedVariable):
+  """A derived variable that one kernel launch writes as a field of its own.
+
+  `compute` follows the protocol (xarray in, xarray out; lite in, lite out; a
+  device result for device inputs, a NumPy one for host inputs);
+  `compute_on_device` always leaves the result in HBM: that is what
+  `evaluation.evaluate_chunks` assigns into the chunk."""
+
+  def compute(self, dataset):
+    if xl.is_xarray(dataset):
+      return xl.like_input(self.compute(xl.as_dataset(dataset)), dataset)
+    dataset = xl.as_dataset(dataset)
+    result = self.compute_on_device(dataset)
+    if any(_on_device(dataset[name].data) for name in self.base_variables
+           if name in dataset.data_vars):
+      return result
+    engine.order_read(result.data)
+    return xl.DataArray(feeder.download(result.data.contiguous()), result.dims,
+                        result.coords, result.name)
+
+  def compute_on_device(self, dataset: xl.Dataset) -> xl.DataArray:
+    raise NotImplementedError
+
+
+def is_materialized(dv) -> bool:
+  """True for this module's classes that `evaluate_chunks` computes up front
+  (a foreign duck-typed object, or ZonalEnergySpectrum, is not)."""
+  return isinstance(dv, _MaterializedVariable)
+
+
+def _pointwise(mode: str, dataset: xl.Dataset, a_name: str, b_name: str,
+               order_of: int, pressure_name: t.Optional[str] = None):
+  device = engine.require_gpu()
+  das = [dataset[a_name], dataset[b_name]]
+  order = tuple(das[order_of].dims)
+  if set(das[0].dims) != set(das[1].dims):
+    raise ValueError(f'{a_name} {das[0].dims} and {b_name} {das[1].dims} must '
+                     'have the same dims')
+  sizes = das[order_of].sizes
+  dtype = _float_dtype(das[0].dtype, das[1].dtype)
+  out_dtype, n_inner, pressure = dtype, min(2, len(order)), None
+  if pressure_name is not None:
+    p = dataset[pressure_name]  # the COORDINATE, broadcast by name (:464)
+    missing = [d for d in p.dims if d not in order]
+    if missing:
+      raise ValueError(f'{pressure_name} dims {missing} not in {order}')
+    pvals = np.asarray(p.values)
+    out_dtype = _float_dtype(dtype, pvals.dtype)
+    # a block = the trailing dims the pressure does not vary along
+    last = max([order.index(d) for d in p.dims], default=-1)
+    n_inner = len(order) - 1 - last
+    outer = order[:last + 1]
+    pvals = np.transpose(pvals, [p.dims.index(d) for d in outer if d in p.dims])
+    pvals = pvals.reshape([sizes[d] if d in p.dims else 1 for d in outer])
+    pressure = np.broadcast_to(pvals, [sizes[d] for d in outer]).ravel()
+  ops = [_operand(da, order, device, dtype, n_inner) for da in das]
+  shape = tuple(sizes[d] for d in order)
+  n_point = int(np.prod(shape[len(order) - n_inner:], dtype=np.int64))
+  n_slab = int(np.prod(shape[:len(order) - n_inner], dtype=np.int64))
+  if pressure is None and all(tab is None for _, tab in ops):
+    n_slab, n_point = 1, n_slab * n_point  # one stream, wide whatever the rows
+  if n_slab * n_point == 0:
+    return xl.DataArray(torch.empty(shape, dtype=out_dtype, device=device),
+                        order, _result_coords(dataset, order))
+  scalar = None
+  if pressure is not None:
+    np_out = np.float32 if out_dtype == torch.float32 else np.float64
+    host = np.ascontiguousarray(pressure, dtype=np_out)
+    if np_out is np.float32:  # (the table upload moves 8-byte words)
+      host = np.concatenate([host, np.zeros(host.size % 2, np.float32)])
+    scalar = engine.upload_table(host.view(np.int64), device).view(out_dtype)[
+        :n_slab]
+  out = engine.derived_pointwise(
+      mode, ops[0][0], _table_tensor(ops[0][1], device), ops[1][0],
+      _table_tensor(ops[1][1], device), n_slab, n_point, out_dtype,
+      scalar).reshape(shape)
+  return xl.DataArray(out, order, _result_coords(dataset, order))
+
+
+@dataclasses.dataclass
+class _WindVariable(_MaterializedVariable):
+  """A variable derived from U and V wind components
+  (derived_variables.py:59-73)."""
+
+  u_name: str
+  v_name: str
+
+  @property
+  def base_variables(self) -> list:
+    return [self.u_name, self.v_name]
+
+
+@dataclasses.dataclass
+class WindSpeed(_WindVariable):
+  """Wind speed sqrt(u**2 + v**2) (derived_variables.py:76-99): three correctly
+  rounded operations in the input dtype, bit-identical to NumPy."""
+
+  u_name: str
+  v_name: str
+
+  @property
+  def base_variables(self) -> list:
+    return [self.u_name, self.v_name]
+
+  @property
+  def core_dims(self):
+    return ([], []), []
+
+  def compute_on_device(self, dataset):
+    return _pointwise('wind_speed', dataset, self.u_name, self.v_name, 0)
+
+
+@dataclasses.dataclass
+class RelativeHumidity(_MaterializedVariable):
+  """Relative humidity from specific humidity, MetPy's formula with Bolton's
+  (1980) saturation vapour pressure (derived_variables.py:433-468).  Pressure
+  (hPa) is the COORDINATE named `pressure_name`, temperature is in Kelvin."""
+
+  temperature_name: str = 'temperature'
+  specific_humidity_name: str = 'specific_humidity'
+  pressure_name: str = 'level'
+
+  @property
+  def base_variables(self) -> list:
+    return [self.temperature_name, self.specific_humidity_name,
+            self.pressure_name]
+
+  @property
+  def core_dims(self):
+    return ([], []), []
+
+  def compute_on_device(self, dataset):
+    return _pointwise('relative_humidity', dataset, self.temperature_name,
+                      self.specific_humidity_name, 1, self.pressure_name)
+
+
+_STENCIL_TABLES: dict = {}
+_STENCIL_TABLES_LOCK = threading.Lock()
+
+
+def _stencil_tables(rows: np.ndarray, cols: np.ndarray, latitude: np.ndarray):
+  """Host tables of one coordinate set, made once (like the latitude weights
+  of a plan): np.gradient coefficients of both axes, cos / Coriolis."""
+  key = tuple(engine.digest(np.ascontiguousarray(x)) + str(x.dtype).encode()
+              for x in (rows, cols, latitude))
+  with _STENCIL_TABLES_LOCK:
+    hit = _STENCIL_TABLES.get(key)
+    if hit is None:
+      if len(_STENCIL_TABLES) >= 64:
+        _STENCIL_TABLES.clear()
+      hit = _STENCIL_TABLES[key] = (plan_lib.gradient_tables(rows),
+                                    plan_lib.gradient_tables(cols),
+                                    plan_lib.latitude_tables(latitude))
+  return hit
+
+
+def _stencil(mode: str, dataset: xl.Dataset, names: t.Sequence[str],
+             lead: int) -> xl.DataArray:
+  """One launch of the stencil kernel.  `names` = (field differentiated along
+  longitude, along latitude[, u, v]); the result has the dims of `names[lead]`,
+  the first operand of the reference's expression."""
+  device = engine.require_gpu()
+  das = [dataset[n] for n in names]
+  dims = tuple(das[lead].dims)
+  for n, da in zip(names, das):
+    if set(da.dims) != set(dims):
+      raise ValueError(f'{n} {da.dims} and {names[lead]} {dims} must have the '
+                       'same dims')
+  spatial = tuple(d for d in dims if d in ('latitude', 'longitude'))
+  if len(spatial) != 2:
+    raise ValueError(f'{names[lead]}: needs latitude and longitude, has {dims}')
+  order = tuple(d for d in dims if d not in spatial) + spatial
+  (row_coef, row_uniform), (col_coef, col_uniform), lat_tables = _stencil_tables(
+      _coord_values(dataset, spatial[0]), _coord_values(dataset, spatial[1]),
+      _coord_values(dataset, 'latitude'))
+  dtype = _float_dtype(*[da.dtype for da in das])
+  seen: dict = {}
+  ops = []
+  for n, da in zip(names, das):  # (the geostrophic modes name one field twice)
+    if n not in seen:
+      seen[n] = _operand(da, order, device, dtype, 2)
+    ops.append(seen[n])
+  sizes = das[lead].sizes
+  shape = tuple(sizes[d] for d in order)
+  n_slab = int(np.prod(shape[:-2], dtype=np.int64))
+  tabs = {n: _table_tensor(tab, device) for n, (_, tab) in seen.items()}
+  out = engine.derived_stencil(
+      mode, [x for x, _ in ops], [tabs[n] for n in names], n_slab, shape[-2],
+      shape[-1], spatial[0] == 'latitude',
+      engine.upload_f64_table(row_coef, device), row_uniform,
+      engine.upload_f64_table(col_coef, device), col_uniform,
+      engine.upload_f64_table(lat_tables, device), plan_lib.METERS_PER_DEGREE
+  ).reshape(shape)
+  if order != dims:
+    out = out.permute(*[order.index(d) for d in dims])
+  return xl.DataArray(out, dims, _result_coords(dataset, dims))
+
+
+@dataclasses.dataclass
+class _3DWindVariable(_MaterializedVariable):
+  """A variable derived from 3D U and V wind components
+  (derived_variables.py:132-146)."""
+
+  u_name: str = 'u_component_of_wind'
+  v_name: str = 'v_component_of_wind'
+
+  @property
+  def base_variables(self) -> list:
+    return [self.u_name, self.v_name]
+
+  @property
+  def core_dims(self):
+    lon_lat = ['longitude', 'latitude']
+    return (lon_lat, lon_lat), lon_lat
+
+
+@dataclasses.dataclass
+class WindDivergence(_3DWindVariable):
+  """Wind divergence d/dx u + d/dy v (derived_variables.py:124-125, 149-161).
+  Derivatives are `np.gradient` along the coordinate in degrees (one-sided at
+  both ends; longitude does not wrap, as in the reference); d/dx is 0.0 at the
+  poles."""
+
+  def compute_on_device(self, dataset):
+    return _stencil('divergence', dataset, (self.u_name, self.v_name), 0)
+
+
+@dataclasses.dataclass
+class WindVorticity(_3DWindVariable):
+  """Wind vorticity d/dx v - d/dy u (derived_variables.py:128-129, 164-176)."""
+
+  def compute_on_device(self, dataset):
+    return _stencil('vorticity', dataset, (self.v_name, self.u_name), 0)
+
+
+@dataclasses.dataclass
+class _GeostrophicWindVariable(_MaterializedVariable):
+  """Base class for geostrophic wind variables (derived_variables.py:231-260):
+  u_g = -d/dy geopotential / f, v_g = +d/dx geopotential / f with the Coriolis
+  parameter f = 2 Omega sin(latitude).  On the equator the result is +-inf /
+  NaN, as in the reference: evaluate over a region."""
+
+  geopotential_name: str = 'geopotential'
+  _mode: t.ClassVar[str] = ''
+
+  @property
+  def base_variables(self) -> list:
+    return [self.geopotential_name]
+
+  @property
+  def core_dims(self):
+    lon_lat = ['longitude', 'latitude']
+    return (lon_lat,), lon_lat
+
+  def compute_on_device(self, dataset):
+    z = self.geopotential_name
+    return _stencil(self._mode, dataset, (z, z), 0)
+
+
+@dataclasses.dataclass
+class GeostrophicWindSpeed(_GeostrophicWindVariable):
+  """Geostrophic wind speed (derived_variables.py:263-276)."""
+  _mode: t.ClassVar[str] = 'geostrophic_speed'
+
+
+class UComponentOfGeostrophicWind(_GeostrophicWindVariable):
+  """East-west component of geostrophic wind (derived_variables.py:279-284)."""
+  _mode: t.ClassVar[str] = 'geostrophic_u'
+
+
+class VComponentOfGeostrophicWind(_GeostrophicWindVariable):
+  """North-south component of geostrophic wind (derived_variables.py:287-292)."""
+  _mode: t.ClassVar[str] = 'geostrophic_v'
+
+
+@dataclasses.dataclass
+class _AgeostrophicWindVariable(_MaterializedVariable):
+  """Base class for ageostrophic wind variables: the wind minus the
+  geostrophic wind (derived_variables.py:295-310)."""
+
+  u_name: str = 'u_component_of_wind'
+  v_name: str = 'v_component_of_wind'
+  geopotential_name: str = 'geopotential'
+  _mode: t.ClassVar[str] = ''
+
+  @property
+  def base_variables(self) -> list:
+    return [self.u_name, self.v_name, self.geopotential_name]
+
+  @property
+  def core_dims(self):
+    lon_lat = ['longitude', 'latitude']
+    return (lon_lat, lon_lat, lon_lat), lon_lat
+
+  def compute_on_device(self, dataset):
+    z = self.geopotential_name
+    lead = 3 if self._mode == 'ageostrophic_v' else 2
+    return _stencil(self._mode, dataset, (z, z, self.u_name, self.v_name), lead)
+
+
+class AgeostrophicWindSpeed(_AgeostrophicWindVariable):
+  """Ageostrophic wind speed (derived_variables.py:313-320)."""
+  _mode: t.ClassVar[str] = 'ageostrophic_speed'
+
+
+class UComponentOfAgeostrophicWind(_AgeostrophicWindVariable):
+  """East-west component of ageostrophic wind (derived_variables.py:323-329)."""
+  _mode: t.ClassVar[str] = 'ageostrophic_u'
+
+
+class VComponentOfAgeostrophicWind(_AgeostrophicWindVariable):
+  """North-south component of ageostrophic wind (derived_variables.py:332-338)."""
+  _mode: t.ClassVar[str] = 'ageostrophic_v'
+
+
+# The reference's dictionary of common derived variables
+# (derived_variables.py:724-773) without the level-column and the
+# precipitation entries (DESIGN.md section 7).
+DERIVED_VARIABLE_DICT = {
+    'wind_speed': WindSpeed(
+        u_name='u_component_of_wind', v_name='v_component_of_wind'),
+    '10m_wind_speed': WindSpeed(
+        u_name='10m_u_component_of_wind', v_name='10m_v_component_of_wind'),
+    'divergence': WindDivergence(),
+    'vorticity': WindVorticity(),
+    'geostrophic_wind_speed': GeostrophicWindSpeed(),
+    'u_component_of_geostrophic_wind': UComponentOfGeostrophicWind(),
+    'v_component_of_geostrophic_wind': VComponentOfGeostrophicWind(),
+    'ageostrophic_wind_speed': AgeostrophicWindSpeed(),
+    'u_component_of_ageostrophic_wind': UComponentOfAgeostrophicWind(),
+    'v_component_of_ageostrophic_wind': VComponentOfAgeostrophicWind(),
+    'relative_humidity': RelativeHumidity(),
+}
 
 
 def zonal_energy_spectrum_area_mean(dataset, variable_name: str) -> xl.DataArray:

@@ -1000,6 +1000,95 @@ def spatial_accumulate(forecast: torch.Tensor, f_slab, truth: torch.Tensor,
       current_stream_ptr(forecast.device)), 'wb2_spatial_accumulate')
 
 
+POINT_MODES = {'wind_speed': 0, 'relative_humidity': 1}
+STENCIL_MODES = {'divergence': 0, 'vorticity': 1, 'geostrophic_u': 2,
+                 'geostrophic_v': 3, 'geostrophic_speed': 4,
+                 'ageostrophic_u': 5, 'ageostrophic_v': 6,
+                 'ageostrophic_speed': 7}
+
+
+def upload_f64_table(table: np.ndarray, device) -> torch.Tensor:
+  """float64 coefficient table -> device tensor through `upload_table` (content
+  cache, pinned ring: no stall of the queue)."""
+  table = np.ascontiguousarray(table, dtype=np.float64)
+  return upload_table(table.view(np.int64), device).view(torch.float64)
+
+
+def derived_pointwise(mode: str, a: torch.Tensor, a_slab, b: torch.Tensor,
+                      b_slab, n_slab: int, n_point: int,
+                      out_dtype: t.Optional[torch.dtype] = None,
+                      slab_scalar: t.Optional[torch.Tensor] = None):
+  """K8 pointwise maps: [n_slab, n_point] of `out_dtype` (the input dtype when
+  None).  Slab o of `a` / `b` starts `table[o] * n_point` elements after the
+  tensor's first element (identity when the table is None)."""
+  lib = _lib.load()
+  dev = a.device
+  if a.dtype not in _DTYPES or b.dtype != a.dtype:
+    raise TypeError('inputs must share a float32/float64 dtype')
+  out_dtype = a.dtype if out_dtype is None else out_dtype
+  out = torch.empty((n_slab, n_point), dtype=out_dtype, device=dev)
+  if slab_scalar is not None and (slab_scalar.dtype != out_dtype
+                                  or slab_scalar.numel() != n_slab):
+    raise ValueError('slab_scalar must hold n_slab values of out_dtype')
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('begin', 'derived_pointwise')
+  _lib.check(lib.wb2_derived_pointwise(
+      POINT_MODES[mode], _DTYPES[a.dtype], _DTYPES[out_dtype], _lib.ptr(a),
+      _lib.ptr(a_slab), _lib.ptr(b), _lib.ptr(b_slab), _lib.ptr(slab_scalar),
+      n_slab, n_point, _lib.ptr(out), current_stream_ptr(dev)),
+             'wb2_derived_pointwise')
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('end', 'derived_pointwise')
+  return out
+
+
+def stencil_geometry(dtype: torch.dtype, wide: bool) -> tuple:
+  """(columns per workgroup tile, rows per row chunk) of the stencil kernel."""
+  import ctypes
+  tile, rows = ctypes.c_int32(), ctypes.c_int32()
+  _lib.check(_lib.load().wb2_derived_stencil_geometry(
+      _DTYPES[dtype], int(wide), ctypes.byref(tile), ctypes.byref(rows)),
+             'wb2_derived_stencil_geometry')
+  return tile.value, rows.value
+
+
+def derived_stencil(mode: str, inputs: t.Sequence[t.Optional[torch.Tensor]],
+                    slabs: t.Sequence, n_slab: int, n_row: int, n_col: int,
+                    lat_rows: bool, row_coef: torch.Tensor, row_uniform: bool,
+                    col_coef: torch.Tensor, col_uniform: bool,
+                    lat_tables: torch.Tensor, m_per_deg: float):
+  """K8 horizontal stencil: float64 [n_slab, n_row, n_col].  `inputs` = (the
+  field differentiated along longitude, along latitude, u, v -- the last two
+  for the ageostrophic modes only), each with an optional slab table;
+  `row_coef` / `col_coef` are plan.gradient_tables of the two axes,
+  `lat_tables` plan.latitude_tables, all float64 on the device."""
+  lib = _lib.load()
+  first = inputs[0]
+  dev = first.device
+  if first.dtype not in _DTYPES or any(
+      x is not None and x.dtype != first.dtype for x in inputs):
+    raise TypeError('inputs must share a float32/float64 dtype')
+  n_lat = n_row if lat_rows else n_col
+  if (tuple(row_coef.shape) != (4, n_row) or tuple(col_coef.shape) != (4, n_col)
+      or tuple(lat_tables.shape) != (2, n_lat)):
+    raise ValueError('coefficient tables do not match the slab shape')
+  inputs = list(inputs) + [None] * (4 - len(inputs))
+  slabs = list(slabs) + [None] * (4 - len(slabs))
+  out = torch.empty((n_slab, n_row, n_col), dtype=torch.float64, device=dev)
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('begin', 'derived_stencil')
+  _lib.check(lib.wb2_derived_stencil(
+      STENCIL_MODES[mode], _DTYPES[first.dtype], int(lat_rows),
+      _lib.ptr_array(inputs), _lib.ptr_array(slabs), n_slab, n_row, n_col,
+      _lib.ptr(row_coef), int(row_uniform), _lib.ptr(col_coef),
+      int(col_uniform), _lib.ptr(lat_tables[0]), _lib.ptr(lat_tables[1]),
+      float(m_per_deg), _lib.ptr(out), current_stream_ptr(dev)),
+             'wb2_derived_stencil')
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('end', 'derived_stencil')
+  return out
+
+
 def ensemble_threshold_reduce(plan: ReductionPlan, ens: torch.Tensor,
                               member_stride: int, n_member: int, ens_slab,
                               truth: torch.Tensor, truth_slab,

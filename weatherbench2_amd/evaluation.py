@@ -1597,6 +1597,7 @@ def evaluate_chunks(
                      '(evaluate_climatology / _probabilistic_climatology / '
                      '_persistence) cannot share one pass over the chunks')
   substitute = _chunk_substitution(configs[0], truth, climatology, by_init)
+  configs, upfront = _split_materialized(configs)
   auto_batch = batch_chunks is None
   batch_chunks = AUTO_BATCH_MAX if auto_batch else max(1, int(batch_chunks))
   from weatherbench2_amd import map_suite
@@ -1669,7 +1670,17 @@ def evaluate_chunks(
       forecast = xl.as_dataset(forecast)
       if substitute is not None:
         forecast = xl.as_dataset(substitute(forecast, truth_chunk))
-      window.append((forecast, xl.as_dataset(truth_chunk)))
+      truth_chunk = xl.as_dataset(truth_chunk)
+      if upfront:
+        # Once per chunk, where it enters the window: from here on a derived
+        # field is one more device variable of the chunk (signature, recorder,
+        # concat_chunks, window size).  Its tensor is allocated and written on
+        # this stream and stays referenced by the window until the flush; the
+        # replay's side streams fork from and join this stream inside the
+        # replay, so the allocator cannot hand the block out under a read.
+        forecast = _with_derived(forecast, upfront)
+        truth_chunk = _with_derived(truth_chunk, upfront)
+      window.append((forecast, truth_chunk))
       if auto_batch:  # sized by the first chunk: its inputs' bytes
         nbytes = max(1, sum(_input_bytes(ds) for ds in window[0]))
         budget = AUTO_BATCH_BYTES
@@ -1688,6 +1699,37 @@ def evaluate_chunks(
   # (the sinks meet the other ranks one after the other, in config order)
   results = [sink.result() for sink in sinks]
   return dict(zip(names, results)) if several else results[0]
+
+
+def _split_materialized(configs: list) -> tuple:
+  """(configs for the loop, derived variables to compute up front or None).
+
+  When every derived variable of every config is one of
+  `derived_variables`' own materialising classes and all configs carry equal
+  dicts (what scripts/evaluate.py:458-483 builds), `evaluate_chunks` computes
+  them once per chunk and the loop sees configs WITHOUT derived variables: the
+  chunk programs and windows stay on.  Anything else -- a foreign duck-typed
+  object, ZonalEnergySpectrum, dicts that differ -- keeps the generic path,
+  where the loop computes and assigns them itself (evaluation.py:402-405)."""
+  import dataclasses
+  from weatherbench2_amd import derived_variables as dv_lib
+  dicts = [getattr(c, 'derived_variables', None) or {} for c in configs]
+  if (not dicts[0] or any(d != dicts[0] for d in dicts[1:])
+      or not all(dv_lib.is_materialized(v) for v in dicts[0].values())
+      or not all(dataclasses.is_dataclass(c) for c in configs)):
+    return configs, None
+  return ([dataclasses.replace(c, derived_variables={}) for c in configs],
+          dict(dicts[0]))
+
+
+def _with_derived(dataset: xl.Dataset, derived: dict) -> xl.Dataset:
+  """A shallow copy of `dataset` with the derived variables assigned as device
+  variables, in dict order (a later one may read an earlier one, as in the
+  loop); the caller's Dataset is not touched."""
+  out = dataset.copy()
+  for name, dv in derived.items():
+    out[name] = dv.compute_on_device(out)
+  return out
 
 
 # ---------------------------------------------------------------------------

@@ -86,6 +86,60 @@ def get_lat_weights(latitude: np.ndarray) -> np.ndarray:
   return weights
 
 
+def gradient_tables(coord: np.ndarray) -> tuple:
+  """(float64[4, n] table a, b, c, den; uniform) of `np.gradient(f, coord,
+  edge_order=1)` along one axis -- what `DataArray.differentiate` is.
+
+  NumPy takes the plain central difference only if `np.diff(coord)` is EXACTLY
+  constant (a `linspace` axis often is not):
+    uniform       g[i] = (f[i+1] - f[i-1]) / den[i],         den = 2 h
+    otherwise     g[i] = a[i] f[i-1] + b[i] f[i] + c[i] f[i+1]
+  and at both ends, always, the one-sided g = (f[1] - f[0]) / den[0],
+  (f[-1] - f[-2]) / den[-1].  With the index clamped to the axis all three
+  difference forms read (f[min(i+1, n-1)] - f[max(i-1, 0)]) / den[i]: that is
+  what wb2_derived_stencil evaluates.  ValueError below two points, like
+  np.gradient."""
+  x = np.asarray(coord)
+  if x.ndim != 1:
+    raise ValueError('distances must be either scalars or 1d')
+  if x.dtype.kind in 'iub':
+    x = x.astype(np.float64)
+  n = x.size
+  if n < 2:
+    raise ValueError(
+        'Shape of array too small to calculate a numerical gradient, '
+        'at least (edge_order + 1) elements are required.')
+  d = np.diff(x)
+  uniform = bool((d == d[0]).all())
+  table = np.zeros((4, n), dtype=np.float64)
+  if uniform:
+    table[3, 1:-1] = 2. * d[0]
+  elif n > 2:
+    dx1, dx2 = d[:-1], d[1:]
+    table[0, 1:-1] = -(dx2) / (dx1 * (dx1 + dx2))
+    table[1, 1:-1] = (dx2 - dx1) / (dx1 * dx2)
+    table[2, 1:-1] = dx1 / (dx2 * (dx1 + dx2))
+    table[3, 1:-1] = 1.0  # (unused: interior points take a, b, c)
+  table[3, 0] = d[0]
+  table[3, -1] = d[-1]
+  return table, uniform
+
+
+EARTH_RADIUS_M = 1000 * (6357 + 6378) / 2  # schema.py:59
+METERS_PER_DEGREE = 2 * np.pi * EARTH_RADIUS_M / 360  # derived_variables.py:107
+_OMEGA = 7.292e-5  # radians / second (derived_variables.py:234)
+
+
+def latitude_tables(latitude: np.ndarray) -> np.ndarray:
+  """float64[2, n_lat]: cos(lat) (`_d_dx`, `_zero_poles`,
+  derived_variables.py:102-117) and the Coriolis parameter 2 Omega sin(lat)
+  (:234-237), exactly as NumPy evaluates the reference's expressions; the
+  kernels do no trigonometry."""
+  lat = np.asarray(latitude)
+  return np.stack([np.cos(np.deg2rad(lat)),
+                   2 * _OMEGA * np.sin(np.deg2rad(lat))]).astype(np.float64)
+
+
 def _runs(signature: np.ndarray) -> np.ndarray:
   """Start offsets (plus the end) of maximal runs of equal rows."""
   n = signature.shape[0]

@@ -1006,6 +1006,69 @@ int wb2_derived_stencil(int mode, int dtype, int lat_rows,
 int wb2_derived_stencil_geometry(int dtype, int wide, int32_t* tile_cols,
                                  int32_t* chunk_rows);
 
+/*
+ * K9: derived variables that walk the `level` axis of a grid column.  A column
+ * slab c holds n_level blocks of n_point contiguous points; level l of column
+ * slab c of input k starts `slabs[k][c * n_level + l] * n_point` elements after
+ * inputs[k] (the tables are always given: a contiguous tensor, a strided view
+ * of whole blocks and a gather differ in the table alone).  A thread owns
+ * adjacent points (16-byte loads where n_point and the buffers allow) and
+ * walks the levels.
+ *
+ * wb2_derived_column, with T = dtype, O = out_dtype, x = the level coordinate
+ * and spacing[l] = x[l + 1] - x[l] (DEV double[n_level - 1], formed on the host
+ * in the coordinate's dtype):
+ *   WB2_COLUMN_INTEGRAL        out[c] = scale * trapz(in0, x)
+ *     (TotalColumnWater :365-385, scale = 1 / g)
+ *   WB2_COLUMN_TRANSPORT       out[c] = scale * sqrt(trapz(in0 * in1)^2 +
+ *     trapz(in0 * in2)^2) (IntegratedWaterTransport :388-430; in0 = the water
+ *     species, in1 = u, in2 = v, the products formed in T)
+ *   WB2_COLUMN_EDDY            out[c] = scale * trapz((in0 - m0)^2 +
+ *     (in1 - m1)^2) (EddyKineticEnergy :212-228, scale = 1 / 2); m0 = inputs[2]
+ *     and m1 = inputs[3] are DEV T[n_column][n_level][n_mean] zonal means, the
+ *     one of point i being entry (i / mean_div) % n_mean
+ *     (wb2_derived_zonal_mean writes them)
+ *   These three read the levels [level_begin, level_end) only, give exactly
+ *   0.0 where fewer than two are selected, and write O[n_column][n_point].  As
+ *   np.trapezoid does, y[l + 1] + y[l] is formed in T, multiplied by the
+ *   spacing in O and halved; the sum over levels is kept in float64 and
+ *   rounded to O once.  O >= T.
+ *   WB2_COLUMN_GRADIENT_RATIO  out[c][l] = d(in0)/dx / (T(scale) * d(in1)/dx)
+ *     (LapseRate :341-362, scale = 1 / g), T[n_column][n_level][n_point];
+ *     d/dx is np.gradient(edge_order=1) from level_coef = DEV double[4][n_level]
+ *     and level_uniform exactly as wb2_derived_stencil applies row_coef.
+ *     O == T; at least two levels.
+ *   WB2_COLUMN_CUMULATIVE      field[c][l] = sum_{k <= l} spacing[k - 1] *
+ *     ((-field[c][k]) + (-field[c][k - 1])) / 2, field[c][0] = 0: scipy's
+ *     cumulative_trapezoid(-field, x, initial=0), IN PLACE on out = DEV double,
+ *     addressed through slabs[0] (VerticalVelocity :179-209 over the divergence
+ *     of wb2_derived_stencil, spacing in Pa).  inputs is not read.
+ * NaN propagates in every mode.  Unused arguments may be NULL / 0.
+ * wb2_derived_column_geometry: points per workgroup tile (wide != 0: 16-byte
+ * loads) and the number of levels a thread requests before it combines any.
+ * wb2_derived_zonal_mean: out = DEV T[n_slab][n_lat], the mean over longitude
+ * of every (n_row, n_col) slab that skips NaN (NaN where a latitude circle
+ * holds no other value); slab o starts slab[o] * n_row * n_col elements after
+ * `in` (identity when NULL).  lat_rows != 0: rows are latitudes.
+ */
+#define WB2_COLUMN_INTEGRAL 0
+#define WB2_COLUMN_TRANSPORT 1
+#define WB2_COLUMN_GRADIENT_RATIO 2
+#define WB2_COLUMN_CUMULATIVE 3
+#define WB2_COLUMN_EDDY 4
+int wb2_derived_column(int mode, int dtype, int out_dtype,
+                       const void* const* inputs, const int64_t* const* slabs,
+                       int64_t n_column, int32_t n_level, int64_t n_point,
+                       int32_t level_begin, int32_t level_end,
+                       const double* spacing, const double* level_coef,
+                       int level_uniform, int64_t mean_div, int32_t n_mean,
+                       double scale, void* out, void* stream);
+int wb2_derived_column_geometry(int dtype, int wide, int32_t* tile_points,
+                                int32_t* levels_ahead);
+int wb2_derived_zonal_mean(int dtype, int lat_rows, const void* in,
+                           const int64_t* slab, int64_t n_slab, int32_t n_row,
+                           int32_t n_col, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,686 @@
+"""The level-column derived variables on the GPU (csrc/derived_column.hip):
+every class against the reference's fixture with a tolerance taken from the
+reference's own float32 noise, exact zeros where the reference gives them,
+non-finite values compared (never skipped), VerticalVelocity bit for bit
+against scipy on the project's own divergence, the kernel's geometry against
+the NumPy restatement, and `evaluate_chunks` keeping its chunk programs and
+windows when a config uses these classes.
+Reference: weatherbench2/derived_variables.py:179-228, 341-430."""
+import dataclasses
+import os
+
+import numpy as np
+import pytest
+
+from tests import column_cases as cc
+from tests import column_np
+from tests import helpers, official_chunks as oc
+from tests.test_column_variables_cpu import analytic_cases, check_analytic
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+
+
+@pytest.fixture(scope='module')
+def golden():
+  return cc.load_golden(GOLDEN_DIR)
+
+
+def _dataset(variables, coords, device=True):
+  import torch
+  from weatherbench2_amd import xarray_lite as xl
+  return xl.Dataset(
+      {k: xl.DataArray(torch.from_numpy(np.ascontiguousarray(a)).cuda()
+                       if device else a, d) for k, (d, a) in variables.items()},
+      dict(coords))
+
+
+def _make(label):
+  from weatherbench2_amd import derived_variables as dv
+  name, kwargs = cc.CLASSES[label]
+  return getattr(dv, name)(**kwargs)
+
+
+def _same_non_finite(got, want, msg):
+  np.testing.assert_array_equal(np.isnan(got), np.isnan(want), err_msg=msg)
+  inf = np.isinf(want)
+  np.testing.assert_array_equal(np.isinf(got), inf, err_msg=msg)
+  np.testing.assert_array_equal(np.sign(got[inf]), np.sign(want[inf]),
+                                err_msg=msg)
+
+
+def _exact_zeros(got, want, msg):
+  assert got.dtype == want.dtype and got.shape == want.shape, msg
+  assert (want == 0).all(), msg
+  assert (got == 0).all() and not np.signbit(got).any(), msg
+
+
+# ---------------------------------------------------------------------------
+# every class, case and label against the reference's fixture
+# ---------------------------------------------------------------------------
+def test_the_classes_are_importable():
+  from weatherbench2_amd.derived_variables import (  # noqa: F401
+      EddyKineticEnergy, IntegratedWaterTransport, LapseRate, TotalColumnWater,
+      VerticalVelocity)
+
+
+@pytest.mark.parametrize('label', list(cc.CLASSES))
+@pytest.mark.parametrize('cname', list(cc.cases()))
+def test_classes_against_the_reference(golden, cname, label):
+  """float32 inputs: with noise = max |ref32 - ref64| over the finite points
+  (the reference's own float32 error), max |hip - ref64| <= 4 noise.  float64
+  inputs: 1e-9 of the rms.  Where the reference is identically 0.0
+  (column_cases.ZERO) the result must be exact zeros.  dtype, dims, coords and
+  non-finite positions must be equal.  The ratio is printed (DESIGN.md section
+  4 records it)."""
+  case = cc.cases()[cname]()
+  key = f'{cname}/{label}'
+  ref64 = golden[f'{key}/ref64']
+  zero = (cname, label) in cc.ZERO
+  ok = np.isfinite(ref64)
+  rms = np.sqrt(np.mean(ref64[ok] ** 2))
+  assert zero == (rms == 0)
+  if case['dtype'] == 'float32':
+    ref32 = golden[f'{key}/ref32']
+    res = _make(label).compute(_dataset(case['vars'], case['coords']))
+    got = res.values
+    assert got.dtype == ref32.dtype and got.shape == ref32.shape, key
+    assert list(res.dims) == list(golden[f'{key}/dims'])
+    assert sorted(res.coords) == list(golden[f'{key}/coords'])
+    _same_non_finite(got, ref32, key)
+    if zero:
+      _exact_zeros(got, ref32, key)
+    else:
+      noise = np.abs(ref32[ok].astype(np.float64) - ref64[ok]).max()
+      err = np.abs(got[ok].astype(np.float64) - ref64[ok]).max()
+      print(f'RATIO {key}: max|hip - ref64| / noise = {err / noise:.3f} '
+            f'(noise / rms = {noise / rms:.2e}, bit-equal to ref32: '
+            f'{np.array_equal(got, ref32, equal_nan=True)})')
+      assert err <= 4 * noise, (key, err / noise)
+    case = cc.as_float64(case)
+  res = _make(label).compute(_dataset(case['vars'], case['coords']))
+  got = res.values
+  assert got.dtype == ref64.dtype and got.shape == ref64.shape, key
+  assert list(res.dims) == list(golden[f'{key}/dims'])
+  assert sorted(res.coords) == list(golden[f'{key}/coords'])
+  _same_non_finite(got, ref64, key)
+  if zero:
+    _exact_zeros(got, ref64, key)
+  else:
+    err = np.abs(got[ok] - ref64[ok]).max()
+    assert err <= 1e-9 * rms, (key, err / rms)
+
+
+def test_non_finite_counts():
+  """The NaN patches of `lonlat_nan`: 24 non-finite EKE points of 684 (the
+  zonal mean skips NaN, the integral does not), 12 TCW, 36 IVT, 44 vertical
+  velocity, 48 lapse rate -- and none anywhere else: a kernel cannot pass by
+  producing NaNs, nor by hiding the reference's."""
+  counts = {'eddy_kinetic_energy': 24, 'total_column_vapor': 12,
+            'integrated_vapor_transport': 36, 'ivt_500_850': 0,
+            'vertical_velocity': 44, 'lapse_rate': 48}
+  case = cc.cases()['lonlat_nan']()
+  for label, n in counts.items():
+    got = _make(label).compute(_dataset(case['vars'], case['coords'])).values
+    assert (~np.isfinite(got)).sum() == n, label
+  case = cc.cases()['era5_levels']()
+  for label in cc.CLASSES:
+    got = _make(label).compute(_dataset(case['vars'], case['coords'])).values
+    assert np.isfinite(got).all(), label
+
+
+@pytest.mark.parametrize('name', list(analytic_cases()))
+@pytest.mark.parametrize('device', [True, False])
+def test_analytic_answers(name, device):
+  import torch
+  from weatherbench2_amd import derived_variables as dv
+  class_name, fields, variables, coords, _, _, _ = analytic_cases()[name]
+  res = getattr(dv, class_name)(**fields).compute(
+      _dataset(variables, coords, device))
+  assert isinstance(res.data, torch.Tensor) == device
+  check_analytic(name, res.dims, res.values)
+
+
+@pytest.mark.parametrize('cname', list(cc.cases()))
+def test_vertical_velocity_is_scipy_on_the_divergence_bit_for_bit(cname):
+  """The same float64 arithmetic in the same order: scipy's
+  cumulative_trapezoid(-divergence, 100 * level, initial=0) of the project's
+  own WindDivergence result."""
+  from weatherbench2_amd import derived_variables as dv
+  case = cc.cases()[cname]()
+  ds = _dataset(case['vars'], case['coords'])
+  div = dv.WindDivergence().compute(ds)
+  got = dv.VerticalVelocity().compute(ds)
+  assert got.dims == div.dims
+  with np.errstate(all='ignore'):
+    want = column_np.cumulative(div.values, div.dims, case['coords']['level'])
+  assert got.values.dtype == want.dtype == np.float64
+  assert np.array_equal(got.values, want, equal_nan=True)
+  assert (got.isel(level=0).values == 0).all()
+
+
+# ---------------------------------------------------------------------------
+# geometry, against the NumPy restatement
+# ---------------------------------------------------------------------------
+LEVELS13 = np.array(cc.ERA5_LEVELS)
+
+
+def _levels(n):
+  return LEVELS13[-n:] if n <= 13 else np.arange(n) * 37 + 20
+
+
+def _fields(dims, sizes, dtype, seed):
+  rs = np.random.RandomState(seed)
+  shape = tuple(sizes[d] for d in dims)
+  lev = _levels(sizes['level']).astype(np.float64).reshape(
+      [sizes[d] if d == 'level' else 1 for d in dims])
+  variables = {
+      'u_component_of_wind': 10.0 * rs.standard_normal(shape),
+      'v_component_of_wind': 8.0 * rs.standard_normal(shape),
+      'geopotential': 7.0e4 * np.log(1050.0 / lev)
+                      + 1.0e3 * rs.standard_normal(shape),
+      'temperature': 215.0 + 0.09 * lev + 5.0 * rs.standard_normal(shape),
+      'specific_humidity': 1e-3 + 9e-3 * rs.random_sample(shape),
+  }
+  return {k: (dims, a.astype(dtype)) for k, a in variables.items()}
+
+
+def _coords(sizes):
+  out = {'level': _levels(sizes['level'])}
+  if 'latitude' in sizes:
+    out['latitude'] = np.linspace(-90, 90, sizes['latitude'])
+  if 'longitude' in sizes:
+    out['longitude'] = np.arange(sizes['longitude']) * (
+        360.0 / sizes['longitude'])
+  return out
+
+
+def _compare(got, dims, np32, np64, msg):
+  """The fixture's rule against the restatement: np32 = NumPy on the inputs
+  (None for float64 inputs), np64 = on the same values as float64."""
+  assert got.shape == np64.shape, msg
+  ok = np.isfinite(np64)
+  rms = np.sqrt(np.mean(np64[ok] ** 2)) if ok.any() else 0.0
+  if np32 is not None:
+    assert got.dtype == np32.dtype, msg
+    _same_non_finite(got, np32, msg)
+    if rms == 0:
+      return _exact_zeros(got, np32, msg)
+    noise = np.abs(np32[ok].astype(np.float64) - np64[ok]).max()
+    err = np.abs(got[ok].astype(np.float64) - np64[ok]).max()
+    assert err <= 4 * noise, (msg, err, noise)
+  else:
+    assert got.dtype == np64.dtype, msg
+    _same_non_finite(got, np64, msg)
+    if rms == 0:
+      return _exact_zeros(got, np64, msg)
+    assert np.abs(got[ok] - np64[ok]).max() <= 1e-9 * rms, msg
+
+
+def _check_against_numpy(label, variables, coords, dtype, dataset=None,
+                         device=True):
+  name, fields = cc.fields_of(label)
+  res = _make(label).compute(
+      _dataset(variables, coords, device) if dataset is None else dataset)
+  as64 = {k: (d, a.astype(np.float64)) for k, (d, a) in variables.items()}
+  with np.errstate(all='ignore'):
+    dims, np64 = column_np.compute(name, fields, as64, coords)
+    np32 = (column_np.compute(name, fields, variables, coords)[1]
+            if dtype == np.float32 else None)
+  assert res.dims == tuple(dims), label
+  _compare(res.values, dims, np32, np64, (label, res.dims, res.shape))
+  return res
+
+
+def _geometry(dtype, wide):
+  import torch
+  from weatherbench2_amd import engine
+  return engine.column_geometry(
+      torch.float32 if dtype == np.float32 else torch.float64, wide)
+
+
+FLAT = ('integrated_vapor_transport', 'total_column_vapor', 'lapse_rate')
+GRID = ('eddy_kinetic_energy', 'vertical_velocity')
+
+
+def _offset_dataset(variables, coords):
+  """Device fields that start one element into their buffers: 4- or 8-byte
+  aligned only, so the launch takes the scalar path whatever the sizes."""
+  import torch
+  from weatherbench2_amd import xarray_lite as xl
+  out = {}
+  for k, (d, a) in variables.items():
+    buf = torch.empty(a.size + 1, dtype=torch.from_numpy(a).dtype,
+                      device='cuda')
+    buf[1:] = torch.from_numpy(np.ascontiguousarray(a)).cuda().reshape(-1)
+    view = buf[1:].view(a.shape)
+    assert view.data_ptr() % 16 != 0
+    out[k] = xl.DataArray(view, d)
+  return xl.Dataset(out, dict(coords))
+
+
+@pytest.mark.parametrize('dtype', [np.float32, np.float64])
+def test_point_counts_around_the_workgroup_tile(dtype):
+  """Point counts one below, at and one above the workgroup tile of the scalar
+  path (odd counts, and buffers that are not 16-byte aligned) and of the
+  16-byte path: the last workgroup is partly or wholly empty."""
+  width = 4 if dtype == np.float32 else 2
+  tile1, ahead = _geometry(dtype, False)
+  tilew, _ = _geometry(dtype, True)
+  assert (tile1, tilew) == (256, 256 * width) and ahead >= 1
+  seed = 0
+  for n_point, offset in ((tile1 - 1, False), (tile1, True), (tile1 + 1, False),
+                          (2 * tile1 + 1, False), (tilew - width, False),
+                          (tilew, False), (tilew + width, False), (width, False),
+                          (1, False)):
+    seed += 1
+    dims = ('time', 'level', 'cell')
+    sizes = dict(time=2, level=5, cell=n_point)
+    variables, coords = _fields(dims, sizes, dtype, seed), _coords(sizes)
+    ds = _offset_dataset(variables, coords) if offset else None
+    for label in FLAT:
+      _check_against_numpy(label, variables, coords, dtype, ds)
+  # the two classes that need the grid: n_lat * n_lon around the tiles
+  for n_lat, n_lon, offset in ((15, 17, False), (16, 16, True), (3, 86, False),
+                               (tilew // 64 - 1, 64, False),
+                               (tilew // 64, 64, False),
+                               (tilew // 64, 64 + width, False)):
+    for dims in (('level', 'latitude', 'longitude'),
+                 ('level', 'longitude', 'latitude')):
+      seed += 1
+      sizes = dict(level=4, latitude=n_lat, longitude=n_lon)
+      variables, coords = _fields(dims, sizes, dtype, seed), _coords(sizes)
+      ds = _offset_dataset(variables, coords) if offset else None
+      for label in GRID:
+        _check_against_numpy(label, variables, coords, dtype, ds)
+
+
+@pytest.mark.parametrize('dtype', [np.float32, np.float64])
+def test_level_counts_around_the_in_flight_depth(dtype):
+  """2, 3 (a uniform coordinate: np.gradient's other formula) and 13 levels,
+  one fewer than, exactly and one more than the levels a thread requests at
+  once, and two rounds plus one."""
+  _, ahead = _geometry(dtype, True)
+  counts = sorted({2, 3, 13, ahead - 1, ahead, ahead + 1, 2 * ahead + 1} - {0, 1})
+  for n_level in counts:
+    for dims in (('level', 'latitude', 'longitude'),
+                 ('level', 'longitude', 'latitude')):
+      sizes = dict(level=n_level, latitude=7, longitude=12)
+      variables, coords = (_fields(dims, sizes, dtype, n_level),
+                           _coords(sizes))
+      for label in cc.CLASSES:
+        if 'liquid' in label or 'ice' in label:
+          continue
+        _check_against_numpy(label, variables, coords, dtype)
+
+
+def test_one_level():
+  """The integrals and the vertical velocity give zeros (even where the field
+  is NaN), LapseRate raises like np.gradient."""
+  dims = ('level', 'latitude', 'longitude')
+  sizes = dict(level=1, latitude=5, longitude=8)
+  variables, coords = _fields(dims, sizes, np.float32, 3), _coords(sizes)
+  variables['specific_humidity'][1][0, 2, 3] = np.nan
+  for label in ('total_column_vapor', 'ivt_open', 'eddy_kinetic_energy',
+                'vertical_velocity', 'integrated_vapor_transport'):
+    res = _make(label).compute(_dataset(variables, coords))
+    got = res.values
+    assert got.dtype == np.float64, label
+    assert got.shape == ((1, 5, 8) if label == 'vertical_velocity'
+                         else (5, 8)), label
+    assert (got == 0).all() and not np.signbit(got).any(), label
+  with pytest.raises(ValueError):
+    _make('lapse_rate').compute(_dataset(variables, coords))
+
+
+@pytest.mark.parametrize('dtype', [np.float32, np.float64])
+def test_level_anywhere_among_the_dims(dtype):
+  """`level` outermost, between `time` and the spatial dims, between the
+  spatial dims, and innermost (transposed and copied); u and v in different
+  dim orders: the result follows the first operand."""
+  import torch
+  from weatherbench2_amd import xarray_lite as xl
+  sizes = dict(time=3, level=5, latitude=9, longitude=16)
+  for seed, dims in enumerate((
+      ('level', 'time', 'latitude', 'longitude'),
+      ('time', 'level', 'latitude', 'longitude'),
+      ('time', 'level', 'longitude', 'latitude'),
+      ('time', 'latitude', 'level', 'longitude'),
+      ('time', 'latitude', 'longitude', 'level'),
+      ('latitude', 'longitude', 'level'))):
+    use = {d: sizes[d] for d in dims}
+    variables, coords = _fields(dims, use, dtype, seed), _coords(use)
+    for label in cc.CLASSES:
+      if 'liquid' in label or 'ice' in label:
+        continue
+      res = _check_against_numpy(label, variables, coords, dtype)
+      assert isinstance(res.data, torch.Tensor) and res.data.is_cuda
+  dims = ('time', 'level', 'latitude', 'longitude')
+  variables, coords = _fields(dims, sizes, dtype, 11), _coords(sizes)
+  ds = _dataset(variables, coords)
+  v = ds['v_component_of_wind']
+  ds['v_component_of_wind'] = xl.DataArray(
+      v.data.permute(3, 1, 0, 2).contiguous(),
+      ('longitude', 'level', 'time', 'latitude'))
+  for label in ('integrated_vapor_transport', 'eddy_kinetic_energy',
+                'vertical_velocity'):
+    _check_against_numpy(label, variables, coords, dtype, ds)
+
+
+def test_strided_views_gathers_and_host_inputs(monkeypatch):
+  """Strided views of whole slabs and a SlabGather over a resident base are
+  read in place (no copy of the field is made); host inputs give NumPy
+  results."""
+  import torch
+  from weatherbench2_amd import derived_variables as dv
+  from weatherbench2_amd import xarray_lite as xl
+  dims = ('time', 'level', 'latitude', 'longitude')
+  sizes = dict(time=4, level=13, latitude=9, longitude=16)
+  variables, coords = _fields(dims, sizes, np.float32, 7), _coords(sizes)
+  full = _dataset(variables, coords)
+  view = xl.Dataset({k: xl.DataArray(v.data[1::2, ::2], dims)
+                     for k, v in full.data_vars.items()},
+                    dict(coords, level=coords['level'][::2]))
+  assert not view['temperature'].data.is_contiguous()
+  sub = {k: (d, a[1::2, ::2]) for k, (d, a) in variables.items()}
+  copies = []
+  real = torch.Tensor.contiguous
+  monkeypatch.setattr(torch.Tensor, 'contiguous',
+                      lambda self, *a, **k: (copies.append(self.is_contiguous()),
+                                             real(self, *a, **k))[1])
+  labels = [k for k in cc.CLASSES if 'liquid' not in k and 'ice' not in k]
+  for label in labels:
+    got = _make(label).compute_on_device(view)
+    assert all(copies), label  # .contiguous() only ever met contiguous tensors
+    _check_against_numpy(label, sub, view.coords, np.float32, view)
+    want = _make(label).compute(_dataset(sub, view.coords)).values
+    assert np.array_equal(got.values, want, equal_nan=True), label
+  # a gather: slabs of a resident base picked by index, in any order
+  base = {k: torch.from_numpy(np.ascontiguousarray(a)).cuda().reshape(
+      -1, sizes['latitude'], sizes['longitude'])
+          for k, (d, a) in variables.items()}
+  rs = np.random.RandomState(1)
+  index = np.stack([rs.permutation(sizes['level']) + t * sizes['level']
+                    for t in (2, 0, 3)])
+  picked = {k: (dims, a.reshape((-1,) + a.shape[2:])[index])
+            for k, (d, a) in variables.items()}
+  gathered = xl.Dataset({k: xl.DataArray(xl.SlabGather(b, index), dims)
+                         for k, b in base.items()}, dict(coords))
+  materialized = []
+  real_m = xl.SlabGather.materialize
+  monkeypatch.setattr(xl.SlabGather, 'materialize',
+                      lambda self, *a, **k: (materialized.append(1),
+                                             real_m(self, *a, **k))[1])
+  for label in labels:
+    _check_against_numpy(label, picked, coords, np.float32, gathered)
+  assert not materialized
+  monkeypatch.undo()
+  # host inputs: NumPy out, the same values
+  for label in labels:
+    host = _make(label).compute(_dataset(variables, coords, device=False))
+    assert isinstance(host.data, np.ndarray), label
+    dev = _make(label).compute(full)
+    assert isinstance(dev.data, torch.Tensor)
+    assert np.array_equal(host.values, dev.values, equal_nan=True), label
+
+
+def test_level_min_and_level_max():
+  """Inclusive labels, open ends, a decreasing and a non-monotonic level
+  coordinate."""
+  from weatherbench2_amd import derived_variables as dv
+  dims = ('level', 'latitude', 'longitude')
+  sizes = dict(level=13, latitude=5, longitude=8)
+  variables, coords = _fields(dims, sizes, np.float32, 2), _coords(sizes)
+  name = 'IntegratedWaterTransport'
+
+  def check(coords, variables, **kw):
+    fields = {**cc.REFERENCE_FIELDS[name], **kw}
+    res = dv.IntegratedWaterTransport(**kw).compute(_dataset(variables, coords))
+    as64 = {k: (d, a.astype(np.float64)) for k, (d, a) in variables.items()}
+    _, np32 = column_np.compute(name, fields, variables, coords)
+    _, np64 = column_np.compute(name, fields, as64, coords)
+    _compare(res.values, res.dims, np32, np64, kw)
+    return res.values
+
+  for kw in ({}, dict(level_min=500, level_max=850), dict(level_min=None),
+             dict(level_max=None), dict(level_min=320.5, level_max=925),
+             dict(level_min=None, level_max=None)):
+    assert check(coords, variables, **kw).any()
+  for kw in (dict(level_min=500, level_max=500), dict(level_min=501,
+                                                      level_max=599),
+             dict(level_min=2000, level_max=3000)):
+    assert not check(coords, variables, **kw).any()
+  down = {k: (d, a[::-1].copy()) for k, (d, a) in variables.items()}
+  down_coords = dict(coords, level=coords['level'][::-1].copy())
+  assert not check(down_coords, down).any()
+  assert check(down_coords, down, level_min=1000, level_max=300).any()
+  open_down = check(down_coords, down, level_min=None, level_max=None)
+  open_up = check(coords, variables, level_min=None, level_max=None)
+  np.testing.assert_allclose(open_down, open_up, rtol=1e-6)
+  tcw_up = dv.TotalColumnWater().compute(_dataset(variables, coords)).values
+  tcw_down = dv.TotalColumnWater().compute(_dataset(down, down_coords)).values
+  assert (tcw_up > 0).all() and (tcw_down < 0).all()
+  # a non-monotonic coordinate: open bounds are plain np.trapezoid, numeric
+  # bounds are refused
+  perm = np.random.RandomState(0).permutation(13)
+  mixed = {k: (d, a[perm].copy()) for k, (d, a) in variables.items()}
+  mixed_coords = dict(coords, level=coords['level'][perm])
+  check(mixed_coords, mixed, level_min=None, level_max=None)
+  with pytest.raises(ValueError, match='not monotonic'):
+    dv.IntegratedWaterTransport().compute(_dataset(mixed, mixed_coords))
+
+
+def test_xarray_lite_protocol():
+  """lite in, lite out, with the coords whose dims survive."""
+  from weatherbench2_amd import xarray_lite as xl
+  case = cc.cases()['era5_levels']()
+  ds = _dataset(case['vars'], case['coords'])
+  res = _make('total_column_vapor').compute(ds)
+  assert isinstance(res, xl.DataArray)
+  assert res.dims == ('time', 'latitude', 'longitude')
+  assert sorted(res.coords) == ['latitude', 'longitude', 'time']
+  res = _make('lapse_rate').compute(ds)
+  assert res.dims == cc.dc.LATLON and 'level' in res.coords
+  with pytest.raises(ValueError, match="'level'"):
+    _make('total_column_vapor').compute(xl.Dataset(
+        {'specific_humidity': xl.DataArray(
+            np.zeros((3, 4), np.float32), ('latitude', 'longitude'))}, {}))
+
+
+# ---------------------------------------------------------------------------
+# evaluate_chunks keeps windows and programs
+# ---------------------------------------------------------------------------
+VARS_3D = oc.VARS_3D + ('temperature', 'specific_humidity')
+LEVEL = np.array([300, 500, 700, 850])
+
+
+def _official(n_init, n_lead, n_lat, n_lon, seed=0):
+  """(forecast, truth at valid time) as oracle DS, in the shape of
+  official_chunks.make with an increasing level coordinate and the humidity
+  and temperature fields it lacks; the fields are shaped like the real ones
+  so that the lapse rate is well conditioned."""
+  from oracle import evaluation_np as oe
+  from oracle.named import DS, NA
+  rs = np.random.RandomState(seed)
+  lat = np.linspace(-90, 90, n_lat)
+  lon = np.linspace(0, 360, n_lon, endpoint=False)
+  init = (np.datetime64('2020-01-01T00', 'ns') +
+          np.arange(n_init) * np.timedelta64(12, 'h'))
+  lead = (np.arange(n_lead) * np.timedelta64(6, 'h')).astype('timedelta64[ns]')
+  n_time = 2 * n_init + n_lead
+  time = (np.datetime64('2020-01-01T00', 'ns') +
+          np.arange(n_time) * np.timedelta64(6, 'h'))
+  lev = LEVEL.astype(np.float64)[:, None, None]
+
+  def fields(outer):
+    shape3 = outer + (len(LEVEL), n_lat, n_lon)
+    shape2 = outer + (n_lat, n_lon)
+    out = {
+        'geopotential': 7.0e4 * np.log(1050.0 / lev)
+                        + 1.0e3 * rs.standard_normal(shape3),
+        'u_component_of_wind': 10.0 * rs.standard_normal(shape3),
+        'v_component_of_wind': 8.0 * rs.standard_normal(shape3),
+        'temperature': 215.0 + 0.09 * lev + 5.0 * rs.standard_normal(shape3),
+        'specific_humidity': 1e-3 + 9e-3 * rs.random_sample(shape3),
+    }
+    out.update({k: rs.standard_normal(shape2) for k in oc.VARS_2D})
+    return {k: a.astype(np.float32) for k, a in out.items()}
+  fcoords = {'init_time': init, 'lead_time': lead, 'level': LEVEL,
+             'latitude': lat, 'longitude': lon,
+             'valid_time': NA(init[:, None] + lead[None, :],
+                              ('init_time', 'lead_time'))}
+  d3 = ('init_time', 'lead_time', 'level', 'latitude', 'longitude')
+  d2 = ('init_time', 'lead_time', 'latitude', 'longitude')
+  forecast = DS({k: NA(a, d3 if k in VARS_3D else d2)
+                 for k, a in fields((n_init, n_lead)).items()}, fcoords)
+  tcoords = {'time': time, 'level': LEVEL, 'latitude': lat, 'longitude': lon}
+  truth = DS({k: NA(a, (('time', 'level') if k in VARS_3D else ('time',))
+                    + ('latitude', 'longitude'))
+              for k, a in fields((n_time,)).items()}, tcoords)
+  return forecast, oe.truth_at_valid_time(truth, forecast)
+
+
+def _derived():
+  from weatherbench2_amd import derived_variables as dv
+  return {k: dv.ALL_DERIVED_VARIABLES[k] for k in (
+      'total_column_vapor', 'integrated_vapor_transport', 'lapse_rate',
+      'vertical_velocity', 'eddy_kinetic_energy')}
+
+
+def _eval_setup(**kw):
+  from weatherbench2_amd import config, evaluation, metrics as gm
+  forecast, truth = _official(**kw)
+  lat, lon = forecast.coords['latitude'], forecast.coords['longitude']
+  lsm = oc.land_sea_mask(len(lat), len(lon))
+  oregions = oc.oracle_regions(lat, lon, lsm)
+  gregions = {k: helpers.to_gpu_region(v) for k, v in oregions.items()}
+  hf, ht = (helpers.to_gpu_dataset(x) for x in (forecast, truth))
+  gf, gt = (evaluation.make_resident(x) for x in (hf, ht))
+  wv = [gm.WindVectorMSE(u_name=u, v_name=v, vector_name=n)
+        for u, v, n in oc.WIND]
+  cfg = config.Eval(metrics={'mse': gm.MSE(wind_vector_mse=wv),
+                             'mae': gm.MAE(), 'bias': gm.Bias()},
+                    regions=gregions, derived_variables=_derived())
+  return forecast, truth, oregions, hf, ht, gf, gt, cfg
+
+
+def _same(a, b):
+  assert sorted(a.data_vars) == sorted(b.data_vars)
+  for name in a.data_vars:
+    x, y = np.asarray(a[name].values), np.asarray(b[name].values)
+    assert a[name].dims == b[name].dims and x.dtype == y.dtype, name
+    assert np.array_equal(x, y, equal_nan=True), name
+
+
+def _count_runs(monkeypatch):
+  from weatherbench2_amd import program
+  calls = []
+  real = program.ChunkProgram.run
+
+  def run(self, *a, **k):
+    calls.append(1)
+    return real(self, *a, **k)
+  monkeypatch.setattr(program.ChunkProgram, 'run', run)
+  return calls
+
+
+def test_evaluate_chunks_is_bit_identical_on_every_path(monkeypatch):
+  from weatherbench2_amd import evaluation
+  _, _, _, hf, ht, gf, gt, cfg = _eval_setup(n_init=4, n_lead=3, n_lat=31,
+                                             n_lon=72)
+  chunks = oc.chunk_pairs(gf, gt)
+  fed = [(h, t) for (h, _), (_, t) in zip(oc.chunk_pairs(hf, ht), chunks)]
+  before = [(sorted(f.data_vars), sorted(t.data_vars)) for f, t in chunks]
+  monkeypatch.setenv('WB2HIP_CHUNK_PROGRAM', '0')
+  want = evaluation.evaluate_chunks(chunks, cfg, False, prefetch=0,
+                                    batch_chunks=1)
+  for name in _derived():
+    assert name in want.data_vars
+    # the results without `level` travel as surface variables
+    assert ('level' in want[name].dims) == (name in ('lapse_rate',
+                                                     'vertical_velocity'))
+    assert np.isfinite(want[name].values).all(), name
+  monkeypatch.setattr(evaluation, '_STAGE_MIN_BYTES', 1024)
+  for how in ('0', '1', 'verify'):
+    monkeypatch.setenv('WB2HIP_CHUNK_PROGRAM', how)
+    for batch in (1, 3, 8, None):
+      kwargs = {} if batch is None else {'batch_chunks': batch}
+      got = evaluation.evaluate_chunks(chunks, cfg, False, prefetch=0,
+                                       **kwargs)
+      _same(got, want)
+      got = evaluation.evaluate_chunks(fed, cfg, False, prefetch=2, **kwargs)
+      _same(got, want)
+  # the caller's chunk Datasets hold no new variables
+  assert before == [(sorted(f.data_vars), sorted(t.data_vars))
+                    for f, t in chunks]
+  assert all('lapse_rate' not in f.data_vars for f, _ in fed)
+
+
+def test_the_fast_path_is_taken(monkeypatch):
+  """Programs on: every chunk after the first of its structure is replayed
+  (chunk by chunk), and a window holds more than one chunk (one fused launch
+  for several chunks)."""
+  from weatherbench2_amd import engine, evaluation, program
+  _, _, _, _, _, gf, gt, cfg = _eval_setup(n_init=4, n_lead=3, n_lat=31,
+                                           n_lon=72)
+  chunks = oc.chunk_pairs(gf, gt)
+  monkeypatch.setenv('WB2HIP_CHUNK_PROGRAM', '1')
+  calls = _count_runs(monkeypatch)
+  evaluation.evaluate_chunks(chunks, cfg, False, prefetch=0, batch_chunks=1)
+  assert len(calls) == len(chunks) - 1, program.REASONS
+  seen = []
+  old = engine.set_launch_hook(lambda when, kernel: seen.append(kernel)
+                               if when == 'begin' else None)
+  try:
+    evaluation.evaluate_chunks(chunks, cfg, False, prefetch=0,
+                               batch_chunks=len(chunks))
+  finally:
+    engine.set_launch_hook(old)
+  # per chunk and dataset: one column launch per class, the zonal means of u
+  # and v, the divergence; far fewer fused passes than chunks: the whole job
+  # is one window
+  assert seen.count('derived_column') == 5 * 2 * len(chunks), seen
+  assert seen.count('derived_zonal_mean') == 2 * 2 * len(chunks), seen
+  assert seen.count('derived_stencil') == 2 * len(chunks), seen
+  assert 1 <= seen.count('stream_partials') < len(chunks) / 2, seen
+
+
+def test_derived_mse_equals_the_oracles():
+  """MSE of the derived total column vapour against the oracle's MSE of the
+  NumPy one (1e-9): per-chunk values averaged over init_time."""
+  from oracle import evaluation_np as oe
+  from oracle import metrics_np as om
+  from oracle.named import DS, NA
+  from weatherbench2_amd import evaluation
+  forecast, truth, oregions, _, _, gf, gt, cfg = _eval_setup(
+      n_init=3, n_lead=2, n_lat=19, n_lon=36)
+  got = evaluation.evaluate_chunks(oc.chunk_pairs(gf, gt), cfg, False,
+                                   prefetch=0)
+
+  def with_tcw(ds):
+    out = dict(ds.items())
+    q = ds['specific_humidity']
+    dims, tcw = column_np.integrate(q.data, tuple(q.dims), LEVEL)
+    out['total_column_vapor'] = NA(1 / 9.81 * tcw, dims)
+    return DS(out, ds.coords)
+  per_chunk = oe.metric_and_region_loop(
+      with_tcw(forecast), with_tcw(truth), {'mse': om.MSE()}, oregions, False,
+      compute_chunk=True)
+  metric_labels = list(got.coords['metric'])
+  region_labels = list(got.coords['region'])
+  checked = 0
+  var = 'total_column_vapor'
+  for (mname, rname), ds in per_chunk.items():
+    mi, ri = metric_labels.index(mname), region_labels.index(rname)
+    want = np.asarray(ds[var].data, dtype=np.float64)
+    dims = tuple(ds[var].dims)
+    want = want.mean(axis=dims.index('init_time'))
+    dims = tuple(d for d in dims if d != 'init_time')
+    order = [d for d in got[var].dims if d not in ('metric', 'region')]
+    vals = np.transpose(got[var].values[mi, ri],
+                        [order.index(d) for d in dims])
+    helpers.assert_close(vals, want, rtol=1e-9, atol=1e-12,
+                         err_msg=f'{rname}/{var}')
+    checked += 1
+  assert checked == len(oregions)

@@ -3,6 +3,11 @@
 and the two wind speeds are derived on the fly.
 
   python tools/derived_chunk.py [--chunks 64] [--pool 8] [--reps 5]
+  python tools/derived_chunk.py --family column
+
+`--family column` derives `total_column_vapor` and
+`integrated_vapor_transport` instead (the level-column kernel against duck-typed
+`torch.trapezoid` classes); the chunks keep all their variables.
 
 (a) `derived_variables.WindSpeed`: computed once per chunk up front by
     `evaluate_chunks`, chunk programs and windows stay on;
@@ -51,12 +56,57 @@ class TorchWindSpeed:
                         u.coords)
 
 
-def without_speeds(chunks):
+class _TorchColumn:
+  """Duck-typed level-column classes in torch (`--family column`)."""
+  G = 9.81
+
+  def _integrate(self, da, data, lo=0):
+    import torch
+    axis = da.dims.index('level')
+    level = torch.as_tensor(np.asarray(da.coords['level'])[lo:],
+                            dtype=torch.float64, device=data.device)
+    shape = [1] * data.dim()
+    shape[axis] = -1
+    return torch.trapezoid(data.narrow(axis, lo, data.shape[axis] - lo),
+                           level.view(shape), dim=axis)
+
+  def _wrap(self, da, data):
+    from weatherbench2_amd import xarray_lite as xl
+    return xl.DataArray(data, tuple(d for d in da.dims if d != 'level'),
+                        {k: v for k, v in da.coords.items() if k != 'level'})
+
+
+class TorchTotalColumnWater(_TorchColumn):
+  base_variables = ['specific_humidity']
+
+  def compute(self, dataset):
+    q = dataset['specific_humidity']
+    return self._wrap(q, 1 / self.G * self._integrate(q, q.data))
+
+
+class TorchIntegratedVaporTransport(_TorchColumn):
+  base_variables = ['u_component_of_wind', 'v_component_of_wind',
+                    'specific_humidity']
+
+  def compute(self, dataset):
+    import torch
+    q = dataset['specific_humidity']
+    u, v = dataset['u_component_of_wind'], dataset['v_component_of_wind']
+    lo = int(np.searchsorted(np.asarray(q.coords['level']), 300))
+    iu = self._integrate(q, q.data * u.data, lo)
+    iv = self._integrate(q, q.data * v.data, lo)
+    return self._wrap(q, 1 / self.G * torch.sqrt(iu ** 2 + iv ** 2))
+
+
+COLUMN = ('total_column_vapor', 'integrated_vapor_transport')
+
+
+def without_speeds(chunks, drop=PAIRS):
   from weatherbench2_amd import xarray_lite as xl
   out = []
   for f, t in chunks:
     out.append(tuple(xl.Dataset({k: v for k, v in ds.data_vars.items()
-                                 if k not in PAIRS}, ds.coords)
+                                 if k not in drop}, ds.coords)
                      for ds in (f, t)))
   return out
 
@@ -66,6 +116,7 @@ def main():
   ap.add_argument('--chunks', type=int, default=64)
   ap.add_argument('--pool', type=int, default=8)
   ap.add_argument('--reps', type=int, default=5)
+  ap.add_argument('--family', choices=('wind', 'column'), default='wind')
   args = ap.parse_args()
   import torch
   import official_chunk as leg
@@ -77,9 +128,22 @@ def main():
       k: dv.WindSpeed(u_name=u, v_name=v) for k, (u, v) in PAIRS.items()})
   foreign = dataclasses.replace(cfg, derived_variables={
       k: TorchWindSpeed(u, v) for k, (u, v) in PAIRS.items()})
+  drop = PAIRS
+  if args.family == 'column':
+    from weatherbench2_amd import xarray_lite as xl
+    clim = cfg.metrics['acc'].climatology  # ACC needs the derived fields too
+    some = clim['2m_temperature']
+    for k in COLUMN:
+      clim[k] = xl.DataArray(torch.randn(some.shape, device=dev), some.dims)
+    ours = dataclasses.replace(cfg, derived_variables={
+        k: dv.ALL_DERIVED_VARIABLES[k] for k in COLUMN})
+    foreign = dataclasses.replace(cfg, derived_variables={
+        COLUMN[0]: TorchTotalColumnWater(),
+        COLUMN[1]: TorchIntegratedVaporTransport()})
+    drop = ()
 
   def once(config, batch):
-    fresh = without_speeds(chunks)  # (the generic path assigns in place)
+    fresh = without_speeds(chunks, drop)  # (the generic path assigns in place)
     kwargs = {} if batch is None else {'batch_chunks': batch}
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -88,7 +152,8 @@ def main():
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) * 1e3 / len(fresh), res
 
-  out = {'chunks': args.chunks, 'pool': args.pool, 'reps': args.reps}
+  out = {'family': args.family, 'chunks': args.chunks, 'pool': args.pool,
+         'reps': args.reps}
   for label, batch in (('chunk_by_chunk', 1), ('default_window', None)):
     times = {'hip_classes': [], 'torch_duck_typed': []}
     results = {}
@@ -109,6 +174,12 @@ def main():
         float(np.median(times['torch_duck_typed'])
               / np.median(times['hip_classes'])), 3)
     row['same_values'] = bool(same)
+    if not same:  # (torch.trapezoid rounds differently)
+      with np.errstate(all='ignore'):
+        row['max_rel_diff'] = float(max(
+            np.nanmax(np.abs(a[k].values - b[k].values)
+                      / np.maximum(np.abs(b[k].values), 1e-300))
+            for k in a.data_vars))
     out[label] = row
   print(json.dumps(out))
 

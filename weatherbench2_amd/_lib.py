@@ -184,6 +184,13 @@ _SIGNATURES = {
         _vp, _int, _vp, _int, _vp, _vp, _c.c_double, _vp, _vp]),
     'wb2_derived_stencil_geometry': (_int, [_int, _int, _c.POINTER(_i32),
                                             _c.POINTER(_i32)]),
+    'wb2_derived_column': (_int, [
+        _int, _int, _int, _c.POINTER(_vp), _c.POINTER(_vp), _i64, _i32, _i64,
+        _i32, _i32, _vp, _vp, _int, _i64, _i32, _c.c_double, _vp, _vp]),
+    'wb2_derived_column_geometry': (_int, [_int, _int, _c.POINTER(_i32),
+                                           _c.POINTER(_i32)]),
+    'wb2_derived_zonal_mean': (_int, [_int, _int, _vp, _vp, _i64, _i32, _i32,
+                                      _vp, _vp]),
 }
 
 _lib = None

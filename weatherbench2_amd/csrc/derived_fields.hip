@@ -13,63 +13,13 @@
 // All per-latitude and per-axis factors are float64 tables made on the host.
 
 #include "common.hpp"
+#include "derived_common.hpp"
 #include "trace.hpp"
 #include "wb2hip.h"
 
 namespace wb2 {
 namespace {
 
-template <typename T, int VEC>
-__device__ __forceinline__ void load_v(const T* p, T (&v)[VEC]) {
-  if constexpr (VEC == 1) {
-    v[0] = __builtin_nontemporal_load(p);
-  } else {
-    typedef T V __attribute__((ext_vector_type(VEC)));
-    const V x = __builtin_nontemporal_load(reinterpret_cast<const V*>(p));
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) v[e] = x[e];
-  }
-}
-
-// (rows that are read again by the neighbouring lanes / the next row chunk)
-template <typename T, int VEC>
-__device__ __forceinline__ void load_cached(const T* p, T (&v)[VEC]) {
-  if constexpr (VEC == 1) {
-    v[0] = *p;
-  } else {
-    typedef T V __attribute__((ext_vector_type(VEC)));
-    const V x = *reinterpret_cast<const V*>(p);
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) v[e] = x[e];
-  }
-}
-
-template <typename T, int VEC>
-__device__ __forceinline__ void store_v(T* p, const T (&v)[VEC]) {
-  if constexpr (VEC == 1) {
-    __builtin_nontemporal_store(v[0], p);
-  } else if constexpr (sizeof(T) * VEC > 16) {
-    // 32 bytes per lane (four doubles): two 16-byte stores
-    T lo[VEC / 2], hi[VEC / 2];
-#pragma unroll
-    for (int e = 0; e < VEC / 2; ++e) {
-      lo[e] = v[e];
-      hi[e] = v[VEC / 2 + e];
-    }
-    store_v<T, VEC / 2>(p, lo);
-    store_v<T, VEC / 2>(p + VEC / 2, hi);
-  } else {
-    typedef T V __attribute__((ext_vector_type(VEC)));
-    V x;
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) x[e] = v[e];
-    __builtin_nontemporal_store(x, reinterpret_cast<V*>(p));
-  }
-}
-
-// correctly rounded (IEEE) square roots, whatever the fast-math defaults are
-__device__ __forceinline__ float sqrt_rn(float x) { return __builtin_sqrtf(x); }
-__device__ __forceinline__ double sqrt_rn(double x) { return __builtin_sqrt(x); }
 __device__ __forceinline__ float exp_of(float x) { return expf(x); }
 __device__ __forceinline__ double exp_of(double x) { return exp(x); }
 
@@ -153,17 +103,6 @@ struct StencilParams {
   int n_row, n_col, row_uniform, col_uniform, mode;
   double m_per_deg;
 };
-
-// np.gradient(edge_order=1) at one point: `lo`, `mid`, `hi` are the values at
-// i - 1, i, i + 1 with the index clamped to the axis, so that the one-sided
-// ends are (hi - lo) / den as well.
-template <typename T>
-__device__ __forceinline__ T gradient_at(T lo, T mid, T hi, bool diff_form,
-                                         double a, double b, double c,
-                                         double den) {
-  if (diff_form) return (T)((double)(T)(hi - lo) / den);
-  return (T)((a * (double)lo + b * (double)mid) + c * (double)hi);
-}
 
 // grid: x = column tiles of 64 * VEC, y = row chunks of kStencilRows, z = slabs
 template <typename T, int VEC, bool LAT_ROWS>
@@ -303,8 +242,6 @@ __global__ void __launch_bounds__(kStencilThreads)
     }
   }
 }
-
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 dim3 point_grid(long long n_point, int vec, long long n_y) {
   const long long gx = (n_point / vec + 255) / 256;

@@ -10,6 +10,10 @@ computed by a HIP kernel (csrc/derived_fields.hip):
                       U/VComponentOfGeostrophicWind, AgeostrophicWindSpeed,
                       U/VComponentOfAgeostrophicWind
 
+  level column        TotalColumnWater, IntegratedWaterTransport, LapseRate,
+                      VerticalVelocity, EddyKineticEnergy
+                      (csrc/derived_column.hip)
+
 They MATERIALISE their result as one more field of the chunk, in the dtype the
 reference's NumPy expression gives; `evaluation.evaluate_chunks` computes them
 once per chunk where the chunk enters the window, so that chunk programs and
@@ -17,9 +21,13 @@ windows treat them as ordinary variables.
 `ZonalEnergySpectrum` (derived_variables.py:531-626, driven by
 scripts/compute_zonal_energy_spectrum.py) is the spectral one.
 
-Not here: the level-column classes (TotalColumnWater,
-IntegratedWaterTransport, LapseRate, VerticalVelocity, EddyKineticEnergy) and
-the two precipitation accumulations, which act along lead time.
+Names: DERIVED_VARIABLE_DICT holds the pointwise and stencil entries of the
+reference's dictionary, COLUMN_VARIABLE_DICT the seven level-column ones, and
+ALL_DERIVED_VARIABLES both in the reference's key order: a
+`--derived_variables=` name is resolved in ALL_DERIVED_VARIABLES.
+
+Not here: the precipitation accumulations, which act
+along lead time.
 """
 from __future__ import annotations
 
@@ -394,11 +402,12 @@ def _stencil_tables(rows: np.ndarray, cols: np.ndarray, latitude: np.ndarray):
   return hit
 
 
-def _stencil(mode: str, dataset: xl.Dataset, names: t.Sequence[str],
-             lead: int) -> xl.DataArray:
+def _stencil_launch(mode: str, dataset: xl.Dataset, names: t.Sequence[str],
+                    lead: int):
   """One launch of the stencil kernel.  `names` = (field differentiated along
-  longitude, along latitude[, u, v]); the result has the dims of `names[lead]`,
-  the first operand of the reference's expression."""
+  longitude, along latitude[, u, v]).  Returns (the contiguous result with its
+  dims in `order` = the other dims, then the two spatial ones; order; the dims
+  of `names[lead]`, the first operand of the reference's expression)."""
   device = engine.require_gpu()
   das = [dataset[n] for n in names]
   dims = tuple(das[lead].dims)
@@ -431,6 +440,13 @@ def _stencil(mode: str, dataset: xl.Dataset, names: t.Sequence[str],
       engine.upload_f64_table(col_coef, device), col_uniform,
       engine.upload_f64_table(lat_tables, device), plan_lib.METERS_PER_DEGREE
   ).reshape(shape)
+  return out, order, dims
+
+
+def _stencil(mode: str, dataset: xl.Dataset, names: t.Sequence[str],
+             lead: int) -> xl.DataArray:
+  """The stencil kernel's result with the dims of `names[lead]`."""
+  out, order, dims = _stencil_launch(mode, dataset, names, lead)
   if order != dims:
     out = out.permute(*[order.index(d) for d in dims])
   return xl.DataArray(out, dims, _result_coords(dataset, dims))
@@ -553,6 +569,308 @@ class VComponentOfAgeostrophicWind(_AgeostrophicWindVariable):
   _mode: t.ClassVar[str] = 'ageostrophic_v'
 
 
+# ---------------------------------------------------------------------------
+# Level-column variables (csrc/derived_column.hip)
+# ---------------------------------------------------------------------------
+_G = 9.81  # (derived_variables.py:357, :384, :419)
+
+
+def _level_values(dataset: xl.Dataset, dims: tuple, name: str) -> np.ndarray:
+  if 'level' not in dims:
+    raise ValueError(f"{name}: needs a 'level' dim, has {dims}")
+  if 'level' not in dataset.coords:
+    raise ValueError(f"{name}: the dataset has no 'level' coordinate")
+  level = _coord_values(dataset, 'level')
+  if level.ndim != 1 or level.dtype.kind not in 'iuf':
+    raise ValueError(f"{name}: 'level' must be a 1-D numeric coordinate")
+  return level
+
+
+def _level_range(level: np.ndarray, level_min, level_max) -> tuple:
+  """Positions [begin, end) of the inclusive label slice
+  `sel(level=slice(level_min, level_max))` on a monotonic coordinate, as
+  pandas resolves it: on a decreasing one a bound pair (small, large) selects
+  nothing."""
+  n = len(level)
+  if level_min is None and level_max is None:
+    return 0, n
+  d = np.diff(level)
+  if (d > 0).all():
+    begin = 0 if level_min is None else int(np.searchsorted(level, level_min,
+                                                            'left'))
+    end = n if level_max is None else int(np.searchsorted(level, level_max,
+                                                          'right'))
+  elif (d < 0).all():
+    begin = 0 if level_min is None else int((level > level_min).sum())
+    end = n if level_max is None else int((level >= level_max).sum())
+  else:
+    raise ValueError(
+        f'level={level} is not monotonic: what the label slice '
+        f'({level_min}, {level_max}) selects on it is not defined here (pass '
+        'level_min=None, level_max=None to integrate over every level)')
+  return begin, max(begin, end)
+
+
+class _Columns(t.NamedTuple):
+  """Operands of one column launch: dims in `order` = outer dims (with `level`
+  at `at`), then `n_inner` dims of contiguous points."""
+  tensors: list
+  tables: list      # device int64 [n_column * n_level] per operand
+  order: tuple
+  shape: tuple
+  at: int
+  n_inner: int
+  n_column: int
+  n_level: int
+  n_point: int
+  dtype: torch.dtype
+  device: t.Any
+
+
+def _columns(dataset: xl.Dataset, names: t.Sequence[str],
+             spatial_last: bool = False) -> _Columns:
+  """The fields `names` laid out for the column kernel, in the dims of the
+  first one.  Dims after `level` (two at the most) form the block of points a
+  level is read in; every other dim indexes a column slab, read where it lies
+  through the slab table.  `level` as the innermost dim is moved to the front
+  (a copy).  `spatial_last`: latitude / longitude become the block."""
+  device = engine.require_gpu()
+  das = [dataset[n] for n in names]
+  dims = tuple(das[0].dims)
+  for n, da in zip(names, das):
+    if set(da.dims) != set(dims):
+      raise ValueError(f'{n} {da.dims} and {names[0]} {dims} must have the '
+                       'same dims')
+  order = dims
+  if spatial_last:
+    spatial = tuple(d for d in dims if d in ('latitude', 'longitude'))
+    order = tuple(d for d in dims if d not in spatial) + spatial
+    n_inner = len(spatial)
+  else:
+    if len(dims) > 1 and dims[-1] == 'level':
+      order = ('level',) + dims[:-1]
+    n_inner = min(2, len(order) - 1 - order.index('level'))
+  at = order.index('level')
+  sizes = das[0].sizes
+  shape = tuple(sizes[d] for d in order)
+  n_outer = len(order) - n_inner
+  dtype = _float_dtype(*[da.dtype for da in das])
+  n_level = shape[at]
+  n_point = int(np.prod(shape[n_outer:], dtype=np.int64))
+  n_column = int(np.prod(shape[:n_outer], dtype=np.int64)) // max(n_level, 1)
+  tensors, tables, seen = [], [], {}
+  for n, da in zip(names, das):
+    if n not in seen:
+      ten, table = (_operand(da, order, device, dtype, n_inner)
+                    if n_column * n_level * n_point else (None, None))
+      if table is None:
+        table = np.arange(n_column * n_level, dtype=np.int64)
+      # [outer dims] -> [column slab][level]
+      table = np.moveaxis(table.reshape(shape[:n_outer]), at, -1)
+      seen[n] = (ten, engine.upload_table(np.ascontiguousarray(table).ravel(),
+                                          device)
+                 if table.size else None)
+    tensors.append(seen[n][0])
+    tables.append(seen[n][1])
+  return _Columns(tensors, tables, order, shape, at, n_inner, n_column,
+                  n_level, n_point, dtype, device)
+
+
+def _spacing(values: np.ndarray, device) -> t.Optional[torch.Tensor]:
+  """np.diff in the coordinate's dtype, as a float64 device table."""
+  if len(values) < 2:
+    return None
+  return engine.upload_f64_table(np.diff(values).astype(np.float64), device)
+
+
+def _without_level(dataset: xl.Dataset, cols: _Columns, out: torch.Tensor,
+                   dims: tuple) -> xl.DataArray:
+  """[n_column, n_point] -> the operand's dims without `level`."""
+  order = tuple(d for d in cols.order if d != 'level')
+  out = out.reshape(tuple(n for d, n in zip(cols.order, cols.shape)
+                          if d != 'level'))
+  dims = tuple(d for d in dims if d != 'level')
+  if order != dims:
+    out = out.permute(*[order.index(d) for d in dims])
+  return xl.DataArray(out, dims, _result_coords(dataset, dims))
+
+
+def _column_integral(mode: str, dataset: xl.Dataset, names: t.Sequence[str],
+                     scale: float, level_min=None, level_max=None,
+                     label: str = '') -> xl.DataArray:
+  dims = tuple(dataset[names[0]].dims)
+  level = _level_values(dataset, dims, label)
+  levels = _level_range(level, level_min, level_max)
+  if mode == 'eddy' and 'longitude' not in dims:
+    raise ValueError(f"{label}: needs a 'longitude' dim, has {dims}")
+  cols = _columns(dataset, names, spatial_last=mode == 'eddy')
+  out_dtype = _float_dtype(cols.dtype, level.dtype)
+  if cols.n_column * cols.n_point == 0:
+    out = torch.empty((cols.n_column, cols.n_point), dtype=out_dtype,
+                      device=cols.device)
+    return _without_level(dataset, cols, out, dims)
+  means, mean_div = (), 1
+  if mode == 'eddy':
+    block = cols.order[len(cols.order) - cols.n_inner:]
+    lat_rows = block[-1] == 'longitude'
+    n_row = cols.shape[-2] if cols.n_inner == 2 else 1
+    n_col = cols.shape[-1]
+    means = [engine.zonal_mean(x, tab, cols.n_column * cols.n_level, n_row,
+                               n_col, lat_rows)
+             for x, tab in zip(cols.tensors, cols.tables)]
+    mean_div = n_col if lat_rows else 1
+  out = engine.derived_column(
+      mode, cols.tensors, cols.tables, cols.n_column, cols.n_level,
+      cols.n_point, out_dtype=out_dtype, levels=levels,
+      spacing=_spacing(level, cols.device), means=means, mean_div=mean_div,
+      scale=scale)
+  return _without_level(dataset, cols, out, dims)
+
+
+@dataclasses.dataclass
+class VerticalVelocity(_3DWindVariable):
+  r"""Vertical wind velocity under the hydrostatic approximation
+  (derived_variables.py:179-209): omega = -\int dp div(u, v), scipy's
+  `cumulative_trapezoid(-divergence, 100 * level, initial=0)`.  The stencil
+  kernel writes the divergence, the column kernel integrates it in place;
+  float64 like the divergence."""
+
+  @property
+  def core_dims(self):
+    zxy = ['level', 'longitude', 'latitude']
+    return (zxy, zxy), zxy
+
+  def compute_on_device(self, dataset):
+    u_dims = tuple(dataset[self.u_name].dims)
+    level = _level_values(dataset, u_dims, 'VerticalVelocity')
+    out, order, dims = _stencil_launch('divergence', dataset,
+                                       (self.u_name, self.v_name), 0)
+    at = order.index('level')
+    n_level = out.shape[at]
+    n_point = out.shape[-2] * out.shape[-1]
+    if out.numel():
+      n_column = out.numel() // (n_level * n_point)
+      table = np.arange(n_column * n_level, dtype=np.int64).reshape(
+          out.shape[:-2])
+      table = np.ascontiguousarray(np.moveaxis(table, at, -1)).ravel()
+      pascals_per_hpa = 100
+      engine.derived_column(
+          'cumulative', [], [engine.upload_table(table, out.device)], n_column,
+          n_level, n_point, spacing=_spacing(pascals_per_hpa * level,
+                                             out.device), out=out)
+    if order != dims:
+      out = out.permute(*[order.index(d) for d in dims])
+    return xl.DataArray(out, dims, _result_coords(dataset, dims))
+
+
+@dataclasses.dataclass
+class EddyKineticEnergy(_3DWindVariable):
+  """Eddy kinetic energy (derived_variables.py:212-228): eddies are the
+  deviation from the instantaneous zonal mean (which skips NaN, as xarray's
+  `mean` does), 1/2 (u'^2 + v'^2) integrated over `level` (in hPa)."""
+
+  @property
+  def core_dims(self):
+    return (['level', 'longitude'], ['level', 'longitude']), ['longitude']
+
+  def compute_on_device(self, dataset):
+    return _column_integral('eddy', dataset, (self.u_name, self.v_name), 1 / 2,
+                            label='EddyKineticEnergy')
+
+
+@dataclasses.dataclass
+class LapseRate(_MaterializedVariable):
+  """Lapse rate in temperature (derived_variables.py:341-362):
+  dT/dp / ((1 / g) dz/dp) with `np.gradient` along `level`, in the fields'
+  dtype.  ValueError on a single level, like `np.gradient`."""
+
+  temperature_name: str = 'temperature'
+  geopotential_name: str = 'geopotential'
+
+  @property
+  def base_variables(self) -> list:
+    return [self.temperature_name, self.geopotential_name]
+
+  @property
+  def core_dims(self):
+    return (['level'], ['level']), ['level']
+
+  def compute_on_device(self, dataset):
+    names = (self.temperature_name, self.geopotential_name)
+    dims = tuple(dataset[names[0]].dims)
+    level = _level_values(dataset, dims, 'LapseRate')
+    coef, uniform = plan_lib.gradient_tables(level)
+    cols = _columns(dataset, names)
+    if cols.n_column * cols.n_point == 0:
+      out = torch.empty((cols.n_column, cols.n_level, cols.n_point),
+                        dtype=cols.dtype, device=cols.device)
+    else:
+      out = engine.derived_column(
+          'gradient_ratio', cols.tensors, cols.tables, cols.n_column,
+          cols.n_level, cols.n_point,
+          level_coef=engine.upload_f64_table(coef, cols.device),
+          level_uniform=uniform, scale=1 / _G)
+    # [column slabs][level][points] -> the temperature's dims
+    n_outer = len(cols.order) - cols.n_inner
+    outer = tuple(d for d in cols.order[:n_outer] if d != 'level')
+    now = outer + ('level',) + cols.order[n_outer:]
+    sizes = dict(zip(cols.order, cols.shape))
+    out = out.reshape(tuple(sizes[d] for d in now))
+    if now != dims:
+      out = out.permute(*[now.index(d) for d in dims])
+    return xl.DataArray(out, dims, _result_coords(dataset, dims))
+
+
+@dataclasses.dataclass
+class TotalColumnWater(_MaterializedVariable):
+  """Total column water (derived_variables.py:365-385): (1 / g) times the
+  trapezoid integral of a water species over `level` -- in hPa, as the
+  reference has it.  Has the species' dims without `level`."""
+
+  water_species_name: str = 'specific_humidity'
+
+  @property
+  def base_variables(self) -> list:
+    return [self.water_species_name]
+
+  @property
+  def core_dims(self):
+    return (['level'],), []
+
+  def compute_on_device(self, dataset):
+    return _column_integral('integral', dataset, (self.water_species_name,),
+                            1 / _G, label='TotalColumnWater')
+
+
+@dataclasses.dataclass
+class IntegratedWaterTransport(_MaterializedVariable):
+  """Integrated horizontal water transport of a column
+  (derived_variables.py:388-430): (1 / g) |(trapz(q u), trapz(q v))| over the
+  levels of the inclusive label slice [level_min, level_max] (None = open; the
+  defaults are the GraphCast paper's).  One selected level, or none, gives 0.0.
+  A non-monotonic `level` with a numeric bound is refused (ValueError)."""
+
+  u_name: str = 'u_component_of_wind'
+  v_name: str = 'v_component_of_wind'
+  water_species_name: str = 'specific_humidity'
+  level_min: t.Optional[float] = 300
+  level_max: t.Optional[float] = 1000
+
+  @property
+  def base_variables(self) -> list:
+    return [self.u_name, self.v_name, self.water_species_name]
+
+  @property
+  def core_dims(self):
+    return (['level'], ['level']), []
+
+  def compute_on_device(self, dataset):
+    return _column_integral(
+        'transport', dataset,
+        (self.water_species_name, self.u_name, self.v_name), 1 / _G,
+        self.level_min, self.level_max, label='IntegratedWaterTransport')
+
+
 # The reference's dictionary of common derived variables
 # (derived_variables.py:724-773) without the level-column and the
 # precipitation entries (DESIGN.md section 7).
@@ -571,6 +889,38 @@ DERIVED_VARIABLE_DICT = {
     'v_component_of_ageostrophic_wind': VComponentOfAgeostrophicWind(),
     'relative_humidity': RelativeHumidity(),
 }
+
+# The level-column entries of the reference's dictionary, with its constructor
+# arguments.  They are kept apart from DERIVED_VARIABLE_DICT for now (DESIGN.md
+# section 7); a `--derived_variables=` name is resolved in
+# ALL_DERIVED_VARIABLES.
+COLUMN_VARIABLE_DICT = {
+    'vertical_velocity': VerticalVelocity(),
+    'eddy_kinetic_energy': EddyKineticEnergy(),
+    'lapse_rate': LapseRate(),
+    'total_column_vapor': TotalColumnWater(
+        water_species_name='specific_humidity'),
+    'total_column_liquid': TotalColumnWater(
+        water_species_name='specific_cloud_liquid_water_content'),
+    'total_column_ice': TotalColumnWater(
+        water_species_name='specific_cloud_ice_water_content'),
+    'integrated_vapor_transport': IntegratedWaterTransport(),
+}
+
+# Both dictionaries in the reference's key order (derived_variables.py:724-752)
+_REFERENCE_KEY_ORDER = (
+    'wind_speed', '10m_wind_speed', 'divergence', 'vorticity',
+    'vertical_velocity', 'eddy_kinetic_energy', 'geostrophic_wind_speed',
+    'u_component_of_geostrophic_wind', 'v_component_of_geostrophic_wind',
+    'ageostrophic_wind_speed', 'u_component_of_ageostrophic_wind',
+    'v_component_of_ageostrophic_wind', 'lapse_rate', 'total_column_vapor',
+    'total_column_liquid', 'total_column_ice', 'integrated_vapor_transport',
+    'relative_humidity')
+ALL_DERIVED_VARIABLES = {
+    k: {**DERIVED_VARIABLE_DICT, **COLUMN_VARIABLE_DICT}[k]
+    for k in _REFERENCE_KEY_ORDER}
+assert len(ALL_DERIVED_VARIABLES) == (len(DERIVED_VARIABLE_DICT)
+                                      + len(COLUMN_VARIABLE_DICT))
 
 
 def zonal_energy_spectrum_area_mean(dataset, variable_name: str) -> xl.DataArray:

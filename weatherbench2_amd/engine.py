@@ -1089,6 +1089,100 @@ def derived_stencil(mode: str, inputs: t.Sequence[t.Optional[torch.Tensor]],
   return out
 
 
+COLUMN_MODES = {'integral': 0, 'transport': 1, 'gradient_ratio': 2,
+                'cumulative': 3, 'eddy': 4}
+
+
+def column_geometry(dtype: torch.dtype, wide: bool) -> tuple:
+  """(points per workgroup tile, levels in flight per thread) of the column
+  kernel."""
+  import ctypes
+  tile, ahead = ctypes.c_int32(), ctypes.c_int32()
+  _lib.check(_lib.load().wb2_derived_column_geometry(
+      _DTYPES[dtype], int(wide), ctypes.byref(tile), ctypes.byref(ahead)),
+             'wb2_derived_column_geometry')
+  return tile.value, ahead.value
+
+
+def zonal_mean(x: torch.Tensor, slab, n_slab: int, n_row: int, n_col: int,
+               lat_rows: bool) -> torch.Tensor:
+  """[n_slab, n_lat] NaN-skipping means over longitude of (n_row, n_col) slabs
+  of `x` (slab o at `slab[o]` slabs after its first element; identity when
+  None), in the dtype of `x`."""
+  out = torch.empty((n_slab, n_row if lat_rows else n_col), dtype=x.dtype,
+                    device=x.device)
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('begin', 'derived_zonal_mean')
+  _lib.check(_lib.load().wb2_derived_zonal_mean(
+      _DTYPES[x.dtype], int(lat_rows), _lib.ptr(x), _lib.ptr(slab), n_slab,
+      n_row, n_col, _lib.ptr(out), current_stream_ptr(x.device)),
+             'wb2_derived_zonal_mean')
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('end', 'derived_zonal_mean')
+  return out
+
+
+def derived_column(mode: str, inputs: t.Sequence[torch.Tensor],
+                   slabs: t.Sequence[torch.Tensor], n_column: int, n_level: int,
+                   n_point: int, *, out_dtype: t.Optional[torch.dtype] = None,
+                   levels: t.Optional[tuple] = None,
+                   spacing: t.Optional[torch.Tensor] = None,
+                   level_coef: t.Optional[torch.Tensor] = None,
+                   level_uniform: bool = False,
+                   means: t.Sequence[torch.Tensor] = (), mean_div: int = 1,
+                   scale: float = 1.0,
+                   out: t.Optional[torch.Tensor] = None) -> torch.Tensor:
+  """K9 column kernel.  `slabs[k]` is the int64 device table [n_column,
+  n_level] of input k (level l of column slab c starts `table * n_point`
+  elements after the tensor's first element).
+
+    integral / transport / eddy  -> [n_column, n_point] of `out_dtype`, over the
+      levels `levels` = (begin, end); `spacing` = float64 [n_level - 1];
+      `means` = the two zonal-mean tables [n_column * n_level, n_mean] (eddy)
+    gradient_ratio               -> [n_column, n_level, n_point] of the input
+      dtype; `level_coef` / `level_uniform` = plan.gradient_tables(level)
+    cumulative                   -> `out` itself (float64), integrated in place
+      through slabs[0]
+  """
+  lib = _lib.load()
+  inputs = list(inputs)
+  first = out if mode == 'cumulative' else inputs[0]
+  dev = first.device
+  if first.dtype not in _DTYPES or any(x.dtype != first.dtype
+                                       for x in inputs + list(means)):
+    raise TypeError('inputs must share a float32/float64 dtype')
+  for tab in slabs:
+    if tab.dtype != torch.int64 or tab.numel() != n_column * n_level:
+      raise ValueError('a slab table must hold n_column * n_level int64')
+  if spacing is not None and spacing.numel() != n_level - 1:
+    raise ValueError('spacing must hold n_level - 1 values')
+  if level_coef is not None and tuple(level_coef.shape) != (4, n_level):
+    raise ValueError('the coefficient table does not match the level count')
+  n_mean = 0
+  if mode == 'eddy':
+    n_mean = means[0].shape[-1]
+    if any(m.numel() != n_column * n_level * n_mean for m in means):
+      raise ValueError('a zonal-mean table must be [n_column * n_level, n_mean]')
+  out_dtype = first.dtype if out_dtype is None else out_dtype
+  if mode == 'gradient_ratio':
+    out = torch.empty((n_column, n_level, n_point), dtype=out_dtype, device=dev)
+  elif mode != 'cumulative':
+    out = torch.empty((n_column, n_point), dtype=out_dtype, device=dev)
+  begin, end = (0, n_level) if levels is None else levels
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('begin', 'derived_column')
+  _lib.check(lib.wb2_derived_column(
+      COLUMN_MODES[mode], _DTYPES[first.dtype], _DTYPES[out_dtype],
+      _lib.ptr_array((inputs + list(means) + [None] * 4)[:4]),
+      _lib.ptr_array((list(slabs) + [None] * 3)[:3]), n_column, n_level,
+      n_point, begin, end, _lib.ptr(spacing), _lib.ptr(level_coef),
+      int(level_uniform), mean_div, n_mean, float(scale), _lib.ptr(out),
+      current_stream_ptr(dev)), 'wb2_derived_column')
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('end', 'derived_column')
+  return out
+
+
 def ensemble_threshold_reduce(plan: ReductionPlan, ens: torch.Tensor,
                               member_stride: int, n_member: int, ens_slab,
                               truth: torch.Tensor, truth_slab,

@@ -1069,6 +1069,46 @@ int wb2_derived_zonal_mean(int dtype, int lat_rows, const void* in,
                            const int64_t* slab, int64_t n_slab, int32_t n_row,
                            int32_t n_col, void* out, void* stream);
 
+/*
+ * K10: derived variables that act along the lead-time axis.  The data is
+ * T[n_outer][n_lead][n_point], T = dtype: n_point is the contiguous block after
+ * the lead axis, n_outer everything before it.  Lead l of outer index o starts
+ * `slab[o * n_lead + l] * n_point` elements after `in` (DEV int64; NULL = the
+ * identity o * n_lead + l), so a contiguous tensor, a lead-sliced view and a
+ * gather differ in the table alone.  out = DEV T[n_outer][n_lead][n_point],
+ * contiguous; every lead is written.  A thread owns adjacent points (16-byte
+ * loads where n_point and the buffers allow) and walks the leads.
+ *
+ * wb2_derived_lead_window, with w = window >= 1 and x the series of one point:
+ *   WB2_LEAD_DIFF_SUM  d[l] = x[l] - x[l - 1] formed in T; out[l] = NaN for
+ *     l < w (lead 0 included), else ((d[l-w+1] + d[l-w+2]) + ...) + d[l]; with
+ *     clamp_negative != 0 a sum < 0 becomes 0.0 (NaN and -0.0 stay)
+ *     (PrecipitationAccumulation :504-528)
+ *   WB2_LEAD_SUM       out[l] = NaN for l < w - 1, else the same ordered sum of
+ *     x[l-w+1 .. l]; clamp_negative is ignored
+ *     (AggregatePrecipitationAccumulation :709-720)
+ * These are xarray's rolling(dim=w).sum() with min_periods = w: every window
+ * is summed afresh, oldest term first, in T, so a NaN gives NaN for exactly
+ * the windows that hold it.  w >= n_lead is not an error (all NaN, but for
+ * out[n_lead - 1] of WB2_LEAD_SUM at w == n_lead).  The window counts of
+ * wb2_derived_lead_geometry keep their terms in registers and read every
+ * element once; any other count gives the same values by reading the terms of
+ * each window again.
+ * wb2_derived_lead_geometry: points per workgroup tile (wide != 0: 16-byte
+ * loads), the number of leads a thread requests before it combines any, and
+ * the window counts with a register ring (a static table of *n_windows
+ * entries).
+ */
+#define WB2_LEAD_DIFF_SUM 0
+#define WB2_LEAD_SUM 1
+int wb2_derived_lead_window(int mode, int dtype, const void* in,
+                            const int64_t* slab, int64_t n_outer,
+                            int32_t n_lead, int64_t n_point, int32_t window,
+                            int clamp_negative, void* out, void* stream);
+int wb2_derived_lead_geometry(int dtype, int wide, int32_t* tile_points,
+                              int32_t* leads_ahead, const int32_t** windows,
+                              int32_t* n_windows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,11 +37,11 @@ LEVELS = np.array([50, 100, 150, 200, 250, 300, 400, 500, 600, 700, 850, 925,
 G = 9.81
 
 
-def resource_report() -> dict:
+def resource_report(source: str = 'derived_column.hip') -> dict:
   """{kernel: VGPRs, scratch bytes per lane, waves per SIMD} of every
-  instantiation in derived_column.hip, from hipcc's own remarks."""
+  instantiation in `source`, from hipcc's own remarks."""
   import re
-  src = os.path.join(build.CSRC, 'derived_column.hip')
+  src = os.path.join(build.CSRC, source)
   cmd = [build._hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17',
          '-ffp-contract=off', '-fPIC', '-I' + os.path.join(build.ROOT, 'include'),
          '-I' + build.CSRC, '-Rpass-analysis=kernel-resource-usage',
@@ -54,6 +54,7 @@ def resource_report() -> dict:
       name = subprocess.run(['c++filt', m.group(1)], capture_output=True,
                             text=True).stdout.strip() or m.group(1)
       name = name.replace('wb2::(anonymous namespace)::', '').split('(')[0]
+      name = name.replace('void ', '')
       out[name] = {}
     for key, pat in (('vgprs', r' VGPRs: (\d+)'),
                      ('scratch', r'ScratchSize \[bytes/lane\]: (\d+)'),

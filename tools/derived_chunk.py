@@ -4,10 +4,17 @@ and the two wind speeds are derived on the fly.
 
   python tools/derived_chunk.py [--chunks 64] [--pool 8] [--reps 5]
   python tools/derived_chunk.py --family column
+  python tools/derived_chunk.py --family lead [--chunks 16] [--pool 4]
 
 `--family column` derives `total_column_vapor` and
 `integrated_vapor_transport` instead (the level-column kernel against duck-typed
 `torch.trapezoid` classes); the chunks keep all their variables.
+
+`--family lead` derives `total_precipitation_24hr` on chunks of their own:
+one init time with the whole lead axis (41 six-hourly leads of 721 x 1440
+float32 cumulative precipitation), what the class's `core_dims` ask a chunker
+for, against a duck-typed torch class (`diff`, `unfold(...).sum(-1)`,
+`where`); MSE, MAE and bias of both variables.
 
 (a) `derived_variables.WindSpeed`: computed once per chunk up front by
     `evaluate_chunks`, chunk programs and windows stay on;
@@ -101,6 +108,61 @@ class TorchIntegratedVaporTransport(_TorchColumn):
 COLUMN = ('total_column_vapor', 'integrated_vapor_transport')
 
 
+class TorchPrecipitationAccumulation:
+  """Duck-typed PrecipitationAccumulation in torch (`--family lead`)."""
+  base_variables = ['total_precipitation']
+
+  def __init__(self, hours, lead_name='lead_time'):
+    self.hours, self.lead_name = hours, lead_name
+
+  def compute(self, dataset):
+    import torch
+    from weatherbench2_amd import xarray_lite as xl
+    tp = dataset['total_precipitation']
+    axis = tp.dims.index(self.lead_name)
+    step = np.diff(np.asarray(dataset.coords[self.lead_name]))[0]
+    w = int(np.timedelta64(self.hours, 'h') / step)
+    acc = tp.data.diff(dim=axis).unfold(axis, w, 1).sum(-1)
+    acc = torch.where((acc >= 0) | acc.isnan(), acc, 0.0)
+    shape = list(tp.data.shape)
+    shape[axis] = w
+    pad = torch.full(shape, float('nan'), dtype=acc.dtype, device=acc.device)
+    return xl.DataArray(torch.cat([pad, acc], dim=axis), tp.dims, tp.coords)
+
+
+def build_lead(dev, n_chunks: int, pool: int, n_lead: int = 41):
+  """(chunks, eval config): `n_chunks` (init_time=1, whole lead axis) chunk
+  pairs of cumulative precipitation over `pool` distinct device arrays."""
+  import torch
+  from weatherbench2_amd import config, metrics as gm
+  from weatherbench2_amd import xarray_lite as xl
+  n_lat, n_lon = 721, 1440
+  gen = torch.Generator(device=dev).manual_seed(0)
+  dims = ('init_time', 'lead_time', 'latitude', 'longitude')
+
+  def field():
+    steps = torch.rand((1, n_lead, n_lat, n_lon), device=dev,
+                       generator=gen) * 4e-3 - 1e-3
+    return steps.cumsum(dim=1)
+  arrays = [(field(), field()) for _ in range(pool)]
+  init = (np.datetime64('2020-01-01T00', 'ns')
+          + np.arange(n_chunks) * np.timedelta64(12, 'h'))
+  lead = (np.arange(n_lead) * np.timedelta64(6, 'h')).astype('timedelta64[ns]')
+  chunks = []
+  for j in range(n_chunks):
+    coords = {'init_time': init[j:j + 1], 'lead_time': lead,
+              'latitude': np.linspace(-90, 90, n_lat),
+              'longitude': np.arange(n_lon) * 0.25,
+              'valid_time': xl.DataArray(init[j:j + 1, None] + lead[None, :],
+                                         ('init_time', 'lead_time'))}
+    chunks.append(tuple(
+        xl.Dataset({'total_precipitation': xl.DataArray(a, dims)}, coords)
+        for a in arrays[j % pool]))
+  cfg = config.Eval(metrics={'mse': gm.MSE(), 'mae': gm.MAE(),
+                             'bias': gm.Bias()})
+  return chunks, cfg
+
+
 def without_speeds(chunks, drop=PAIRS):
   from weatherbench2_amd import xarray_lite as xl
   out = []
@@ -116,14 +178,19 @@ def main():
   ap.add_argument('--chunks', type=int, default=64)
   ap.add_argument('--pool', type=int, default=8)
   ap.add_argument('--reps', type=int, default=5)
-  ap.add_argument('--family', choices=('wind', 'column'), default='wind')
+  ap.add_argument('--family', choices=('wind', 'column', 'lead'),
+                  default='wind')
   args = ap.parse_args()
   import torch
   import official_chunk as leg
   from weatherbench2_amd import derived_variables as dv
   from weatherbench2_amd import engine, evaluation
   dev = engine.require_gpu()
-  chunks, cfg = leg.build(dev, args.chunks, args.pool, seeps=False)
+  if args.family == 'lead':
+    chunks, cfg = build_lead(dev, min(args.chunks, 16), min(args.pool, 4))
+    args.chunks = len(chunks)
+  else:
+    chunks, cfg = leg.build(dev, args.chunks, args.pool, seeps=False)
   ours = dataclasses.replace(cfg, derived_variables={
       k: dv.WindSpeed(u_name=u, v_name=v) for k, (u, v) in PAIRS.items()})
   foreign = dataclasses.replace(cfg, derived_variables={
@@ -140,6 +207,14 @@ def main():
     foreign = dataclasses.replace(cfg, derived_variables={
         COLUMN[0]: TorchTotalColumnWater(),
         COLUMN[1]: TorchIntegratedVaporTransport()})
+    drop = ()
+  if args.family == 'lead':
+    name = 'total_precipitation_24hr'
+    ours = dataclasses.replace(cfg, derived_variables={
+        name: dv.PrecipitationAccumulation('total_precipitation', 24,
+                                           lead_time_name='lead_time')})
+    foreign = dataclasses.replace(cfg, derived_variables={
+        name: TorchPrecipitationAccumulation(24)})
     drop = ()
 
   def once(config, batch):

@@ -191,6 +191,11 @@ _SIGNATURES = {
                                            _c.POINTER(_i32)]),
     'wb2_derived_zonal_mean': (_int, [_int, _int, _vp, _vp, _i64, _i32, _i32,
                                       _vp, _vp]),
+    'wb2_derived_lead_window': (_int, [_int, _int, _vp, _vp, _i64, _i32, _i64,
+                                       _i32, _int, _vp, _vp]),
+    'wb2_derived_lead_geometry': (_int, [
+        _int, _int, _c.POINTER(_i32), _c.POINTER(_i32),
+        _c.POINTER(_c.POINTER(_i32)), _c.POINTER(_i32)]),
 }
 
 _lib = None

@@ -1,9 +1,8 @@
 """GPU derived variables with the reference's `DerivedVariable` protocol.
 
-Every class of weatherbench2/derived_variables.py that acts inside one
-`init_time=1,lead_time=1` chunk on single fields or horizontal neighbours is
-here, with the reference's names, dataclass fields and defaults, and is
-computed by a HIP kernel (csrc/derived_fields.hip):
+Every class of weatherbench2/derived_variables.py is here, with the
+reference's names, dataclass fields and defaults, and is computed by a HIP
+kernel (csrc/derived_fields.hip unless named):
 
   pointwise           WindSpeed, RelativeHumidity
   horizontal stencil  WindDivergence, WindVorticity, GeostrophicWindSpeed,
@@ -14,6 +13,15 @@ computed by a HIP kernel (csrc/derived_fields.hip):
                       VerticalVelocity, EddyKineticEnergy
                       (csrc/derived_column.hip)
 
+  lead time           PrecipitationAccumulation,
+                      AggregatePrecipitationAccumulation
+                      (csrc/derived_lead.hip)
+
+The first three families act inside one `init_time=1,lead_time=1` chunk.  The
+lead-time family needs the whole lead axis in one chunk -- what its
+`core_dims` ask a chunker for: `compute()` on a dataset, the in-memory driver
+and `evaluate_chunks` on chunks that hold every lead.
+
 They MATERIALISE their result as one more field of the chunk, in the dtype the
 reference's NumPy expression gives; `evaluation.evaluate_chunks` computes them
 once per chunk where the chunk enters the window, so that chunk programs and
@@ -22,12 +30,11 @@ windows treat them as ordinary variables.
 scripts/compute_zonal_energy_spectrum.py) is the spectral one.
 
 Names: DERIVED_VARIABLE_DICT holds the pointwise and stencil entries of the
-reference's dictionary, COLUMN_VARIABLE_DICT the seven level-column ones, and
-ALL_DERIVED_VARIABLES both in the reference's key order: a
-`--derived_variables=` name is resolved in ALL_DERIVED_VARIABLES.
-
-Not here: the precipitation accumulations, which act
-along lead time.
+reference's dictionary, COLUMN_VARIABLE_DICT the seven level-column ones,
+ALL_DERIVED_VARIABLES both in the reference's key order, LEAD_VARIABLE_DICT
+the four precipitation accumulations, and REFERENCE_DERIVED_VARIABLES all 22
+keys in the reference's order: a `--derived_variables=` name is resolved
+there.
 """
 from __future__ import annotations
 
@@ -871,9 +878,128 @@ class IntegratedWaterTransport(_MaterializedVariable):
         self.level_min, self.level_max, label='IntegratedWaterTransport')
 
 
+# ---------------------------------------------------------------------------
+# Lead-time variables (csrc/derived_lead.hip)
+# ---------------------------------------------------------------------------
+def _lead_window(mode: str, dataset: xl.Dataset, name: str, lead_name: str,
+                 window: int, clamp_negative: bool = False) -> xl.DataArray:
+  """One launch of the lead-window kernel over the field `name`: the dims
+  after `lead_name` form the block of points a lead is read in, the dims
+  before it index the outer slabs, read where they lie through the slab table
+  (a contiguous tensor needs none).  `lead_name` as the innermost of several
+  dims is moved to the front (a copy).  The result has the field's dims."""
+  da = dataset[name]
+  dims = tuple(da.dims)
+  if lead_name not in dims:
+    raise ValueError(f'{name}: needs a {lead_name!r} dim, has {dims}')
+  device = engine.require_gpu()
+  order = dims
+  if len(dims) > 1 and dims[-1] == lead_name:
+    order = (lead_name,) + dims[:-1]
+  at = order.index(lead_name)
+  n_inner = len(order) - 1 - at
+  sizes = da.sizes
+  shape = tuple(sizes[d] for d in order)
+  dtype = _float_dtype(da.dtype)
+  n_lead = shape[at]
+  n_outer = int(np.prod(shape[:at], dtype=np.int64))
+  n_point = int(np.prod(shape[at + 1:], dtype=np.int64))
+  if n_outer * n_lead * n_point == 0:
+    out = torch.empty(shape, dtype=dtype, device=device)
+  else:
+    ten, table = _operand(da, order, device, dtype, n_inner)
+    out = engine.derived_lead_window(
+        mode, ten, _table_tensor(table, device), n_outer, n_lead, n_point,
+        window, clamp_negative).reshape(shape)
+  if order != dims:
+    out = out.permute(*[order.index(d) for d in dims])
+  return xl.DataArray(out, dims, _result_coords(dataset, dims))
+
+
+def _whole_steps(numerator, denominator) -> int:
+  """derived_variables.py:513-514, :713-717."""
+  steps = float(numerator / denominator)
+  assert steps.is_integer(), 'Accumulation time must be multiple of timestep.'
+  if steps < 1:
+    raise ValueError(f'a window of {int(steps)} steps cannot be accumulated')
+  return int(steps)
+
+
+@dataclasses.dataclass
+class PrecipitationAccumulation(_MaterializedVariable):
+  """Precipitation accumulated over the `accumulation_hours` leading up to and
+  including each lead time, from the cumulative `total_precipitation_name`
+  (derived_variables.py:471-528): the rolling sum of the lead-to-lead
+  differences, NaN where the window is not complete (the first lead included),
+  negative sums set to zero unless `set_negative_to_zero` is False.
+
+  Needs the whole lead axis in one chunk; fewer than two leads raise a
+  ValueError (the reference fails there with an IndexError)."""
+
+  total_precipitation_name: str
+  accumulation_hours: int
+  lead_time_name: str = 'prediction_timedelta'
+  set_negative_to_zero: bool = True
+
+  @property
+  def base_variables(self) -> list:
+    return [self.total_precipitation_name]
+
+  @property
+  def core_dims(self):
+    return ([self.lead_time_name],), [self.lead_time_name]
+
+  def compute_on_device(self, dataset):
+    lead_name = self.lead_time_name
+    if lead_name not in dataset.coords:
+      raise ValueError(
+          f'PrecipitationAccumulation: the dataset has no {lead_name!r} '
+          'coordinate to take the time step from')
+    lead = _coord_values(dataset, lead_name)
+    if lead.ndim != 1 or lead.size < 2:
+      raise ValueError(
+          f'PrecipitationAccumulation: {lead_name!r} holds {lead.size} lead '
+          'time(s); the variable needs the whole lead axis in one chunk (at '
+          'least two leads, equally spaced)')
+    timestep = np.diff(lead)
+    assert np.all(timestep == timestep[0]), 'All time steps must be equal.'
+    steps = _whole_steps(np.timedelta64(self.accumulation_hours, 'h'),
+                         timestep[0])
+    return _lead_window('diff_sum', dataset, self.total_precipitation_name,
+                        lead_name, steps, self.set_negative_to_zero)
+
+
+@dataclasses.dataclass
+class AggregatePrecipitationAccumulation(_MaterializedVariable):
+  """A longer accumulation period from existing shorter accumulations
+  (derived_variables.py:685-720): the rolling sum of `raw_accumulation_name`
+  over accumulation_hours / raw_accumulation_hours leads, NaN where the window
+  is not complete.  As in the reference the lead coordinate is not looked
+  at."""
+
+  accumulation_hours: int
+  raw_accumulation_name: str = 'total_precipitation_6hr'
+  raw_accumulation_hours: int = 6
+  lead_time_name: str = 'prediction_timedelta'
+
+  @property
+  def base_variables(self) -> list:
+    return [self.raw_accumulation_name]
+
+  @property
+  def core_dims(self):
+    return ([self.lead_time_name],), [self.lead_time_name]
+
+  def compute_on_device(self, dataset):
+    steps = _whole_steps(np.timedelta64(self.accumulation_hours, 'h'),
+                         np.timedelta64(self.raw_accumulation_hours, 'h'))
+    return _lead_window('sum', dataset, self.raw_accumulation_name,
+                        self.lead_time_name, steps)
+
+
 # The reference's dictionary of common derived variables
 # (derived_variables.py:724-773) without the level-column and the
-# precipitation entries.
+# precipitation entries, which live in the two dictionaries below.
 DERIVED_VARIABLE_DICT = {
     'wind_speed': WindSpeed(
         u_name='u_component_of_wind', v_name='v_component_of_wind'),
@@ -921,6 +1047,35 @@ ALL_DERIVED_VARIABLES = {
     for k in _REFERENCE_KEY_ORDER}
 assert len(ALL_DERIVED_VARIABLES) == (len(DERIVED_VARIABLE_DICT)
                                       + len(COLUMN_VARIABLE_DICT))
+
+# The lead-time entries of the reference's dictionary (derived_variables.py:
+# 753-772), with its constructor arguments.  They need the whole lead axis in
+# one chunk, so they stay out of ALL_DERIVED_VARIABLES, whose entries all act
+# inside an `init_time=1,lead_time=1` chunk.
+LEAD_VARIABLE_DICT = {
+    'total_precipitation_6hr': PrecipitationAccumulation(
+        total_precipitation_name='total_precipitation',
+        accumulation_hours=6,
+        lead_time_name='prediction_timedelta'),
+    'total_precipitation_24hr': PrecipitationAccumulation(
+        total_precipitation_name='total_precipitation',
+        accumulation_hours=24,
+        lead_time_name='prediction_timedelta'),
+    'total_precipitation_24hr_from_6hr': AggregatePrecipitationAccumulation(
+        accumulation_hours=24,
+        lead_time_name='prediction_timedelta'),
+    'total_precipitation_24hr_from_12hr': AggregatePrecipitationAccumulation(
+        accumulation_hours=24,
+        lead_time_name='prediction_timedelta',
+        raw_accumulation_name='total_precipitation_12hr',
+        raw_accumulation_hours=12),
+}
+
+# Every key of the reference's dictionary, in its order, with the objects of
+# the three family dictionaries: what a `--derived_variables=` name may be
+# resolved in.
+REFERENCE_DERIVED_VARIABLES = {**ALL_DERIVED_VARIABLES, **LEAD_VARIABLE_DICT}
+assert len(REFERENCE_DERIVED_VARIABLES) == 22
 
 
 def zonal_energy_spectrum_area_mean(dataset, variable_name: str) -> xl.DataArray:

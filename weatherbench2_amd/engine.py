@@ -1183,6 +1183,56 @@ def derived_column(mode: str, inputs: t.Sequence[torch.Tensor],
   return out
 
 
+LEAD_MODES = {'diff_sum': 0, 'sum': 1}
+
+
+def lead_geometry(dtype: torch.dtype, wide: bool) -> tuple:
+  """(points per workgroup tile, leads in flight per thread, the window counts
+  that keep their terms in registers) of the lead-window kernel."""
+  import ctypes
+  tile, ahead, n = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+  windows = ctypes.POINTER(ctypes.c_int32)()
+  _lib.check(_lib.load().wb2_derived_lead_geometry(
+      _DTYPES[dtype], int(wide), ctypes.byref(tile), ctypes.byref(ahead),
+      ctypes.byref(windows), ctypes.byref(n)), 'wb2_derived_lead_geometry')
+  return tile.value, ahead.value, tuple(windows[k] for k in range(n.value))
+
+
+def derived_lead_window(mode: str, x: torch.Tensor,
+                        slab: t.Optional[torch.Tensor], n_outer: int,
+                        n_lead: int, n_point: int, window: int,
+                        clamp_negative: bool = False) -> torch.Tensor:
+  """K10 lead-window kernel: [n_outer, n_lead, n_point] of the dtype of `x`.
+  `slab` is the int64 device table [n_outer, n_lead] (lead l of outer index o
+  starts `table * n_point` elements after the first element of `x`), None for
+  a contiguous `x`.
+
+    diff_sum  the rolling sum over `window` leads of x[l] - x[l - 1], NaN at
+              the first `window` leads; sums below zero become 0.0 when
+              `clamp_negative`
+    sum       the rolling sum over `window` leads of x, NaN at the first
+              `window - 1` leads
+  """
+  lib = _lib.load()
+  if x.dtype not in _DTYPES:
+    raise TypeError('the input must be float32 or float64')
+  if slab is not None and (slab.dtype != torch.int64
+                           or slab.numel() != n_outer * n_lead):
+    raise ValueError('the slab table must hold n_outer * n_lead int64')
+  if window < 1:
+    raise ValueError(f'window={window} must be at least one lead')
+  out = torch.empty((n_outer, n_lead, n_point), dtype=x.dtype, device=x.device)
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('begin', 'derived_lead_window')
+  _lib.check(lib.wb2_derived_lead_window(
+      LEAD_MODES[mode], _DTYPES[x.dtype], _lib.ptr(x), _lib.ptr(slab), n_outer,
+      n_lead, n_point, min(int(window), 2**31 - 1), int(clamp_negative),
+      _lib.ptr(out), current_stream_ptr(x.device)), 'wb2_derived_lead_window')
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('end', 'derived_lead_window')
+  return out
+
+
 def ensemble_threshold_reduce(plan: ReductionPlan, ens: torch.Tensor,
                               member_stride: int, n_member: int, ens_slab,
                               truth: torch.Tensor, truth_slab,

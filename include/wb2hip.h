@@ -1109,6 +1109,83 @@ int wb2_derived_lead_geometry(int dtype, int wide, int32_t* tile_points,
                               int32_t* leads_ahead, const int32_t** windows,
                               int32_t* n_windows);
 
+/*
+ * K11: horizontal regridding (weatherbench2/regridding.py).  A slab is one
+ * 2-D field of T = dtype: (lat, lon) with longitude contiguous when lat_rows
+ * != 0 (the layout of everything else here), (lon, lat) with latitude
+ * contiguous when lat_rows == 0 (the reference's regrid_array).  Slab o starts
+ * `slab[o] * n_src_lat * n_src_lon` elements after `in` (DEV int64; NULL = the
+ * identity), so a contiguous tensor, a strided view of whole slabs and a
+ * gather differ in the table alone.  out = DEV T[n_slab][target slab],
+ * contiguous, in the layout of the input.
+ *
+ * wb2_regrid_separable acts on each axis in turn.  Each axis has a table in
+ * CSR form, built on the host from the dense (target, source) float64 weight
+ * matrix of that axis: ptr = DEV int32[n_target + 1], idx = DEV int32[], w =
+ * DEV double[], nan = DEV uint8[n_target].  Entries ptr[k] .. ptr[k + 1] - 1
+ * belong to target index k: the entries of row k with w != 0, in ascending
+ * source index; for the longitude of a periodic source a band that runs over
+ * the seam (its wrap-around gap is smaller than its largest inner gap) starts
+ * behind that largest gap, so that it is in ascending position within the
+ * band.  nan[k] != 0: row k holds a NaN (the target index is not covered by
+ * the source), it has no entries and every result along it is NaN.  idx < the
+ * source extent of its axis; the tables are trusted.
+ * With a = target longitude, c = target latitude, b / d = source longitude /
+ * latitude, f the slab, all arithmetic in float64, every multiply and every
+ * add rounded on its own (no FMA contraction), sums started at 0.0 and run in
+ * table order:
+ *   WB2_REGRID_NANMEAN (ConservativeRegridder :505-536)
+ *     inner_t[b,c] = sum_d wlat[c,d] * (isnan(f[b,d]) ? 0.0 : f[b,d])
+ *     inner_n[b,c] = sum_d wlat[c,d] * (isnan(f[b,d]) ? 0.0 : 1.0)
+ *     total[a,c] = sum_b wlon[a,b] * inner_t[b,c], count[a,c] likewise over
+ *     inner_n; out[a,c] = T(total / count): 0 / 0 -> NaN.  An infinity reaches
+ *     the cells whose bands hold it and no other.
+ *   WB2_REGRID_LINEAR (BilinearRegridder :256-294)
+ *     every target index has exactly two entries: idx = (i0, i1), w = (t, *);
+ *     lerp(f0, f1, t) = t == 0 ? f0 : f0 + t * (f1 - f0) (a target node on a
+ *     source node takes that node's value whatever its neighbour holds;
+ *     otherwise NaN propagates).  g[b,c] = lerp(f[b,i0], f[b,i1], t) along
+ *     latitude, out[a,c] = T(lerp(g[j0,c], g[j1,c], u)) along longitude.
+ *     Clamping at the poles, NaN outside the source and the wrap of a periodic
+ *     source are in the table (t = 0 with i1 = i0; nan).
+ * Workgroups of the (lat, lon) layout own one target latitude: a thread walks
+ * the latitude band of its source longitudes (16-byte loads where wide: the
+ * row length a multiple of the vector and `in` aligned), the longitude sums
+ * run over the row of partial results in LDS.  Workgroups of the (lon, lat)
+ * layout own one target longitude and stage the meridians of its band in LDS.
+ * A thread requests `band` entries before it combines any; longer bands are
+ * walked in pieces of that length and give the same values.  A contiguous
+ * axis longer than `max_contig` takes a kernel of one thread per target cell.
+ *
+ * wb2_regrid_gather (NearestRegridder :230-248): out[o][j] = in_slab_o[
+ * index[j]], index = DEV int32[n_tgt] into a slab of n_src elements of
+ * elem_size = 1, 2, 4 or 8 bytes.  The host permutes the index table for the
+ * layout: the kernel knows none.
+ *
+ * wb2_regrid_geometry, for wb2_regrid_separable: contiguous-axis elements per
+ * workgroup pass (wide != 0: 16-byte loads), target rows (columns) per
+ * workgroup, band entries in flight per thread, the longest contiguous axis of
+ * the workgroup kernels, and the slabs per grid row (more are folded into the
+ * grid's third dimension).
+ */
+#define WB2_REGRID_NANMEAN 0
+#define WB2_REGRID_LINEAR 1
+int wb2_regrid_separable(int mode, int dtype, int lat_rows, const void* in,
+                         const int64_t* slab, int64_t n_slab,
+                         int32_t n_src_lon, int32_t n_src_lat,
+                         int32_t n_tgt_lon, int32_t n_tgt_lat,
+                         const int32_t* lon_ptr, const int32_t* lon_idx,
+                         const double* lon_w, const uint8_t* lon_nan,
+                         const int32_t* lat_ptr, const int32_t* lat_idx,
+                         const double* lat_w, const uint8_t* lat_nan,
+                         void* out, void* stream);
+int wb2_regrid_gather(int elem_size, const void* in, const int64_t* slab,
+                      int64_t n_slab, int64_t n_src, const int32_t* index,
+                      int64_t n_tgt, void* out, void* stream);
+int wb2_regrid_geometry(int dtype, int lat_rows, int wide, int32_t* tile_elems,
+                        int32_t* run_targets, int32_t* band_ahead,
+                        int32_t* max_contig, int32_t* grid_slabs);
+
 #ifdef __cplusplus
 }
 #endif

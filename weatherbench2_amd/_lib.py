@@ -196,6 +196,14 @@ _SIGNATURES = {
     'wb2_derived_lead_geometry': (_int, [
         _int, _int, _c.POINTER(_i32), _c.POINTER(_i32),
         _c.POINTER(_c.POINTER(_i32)), _c.POINTER(_i32)]),
+    'wb2_regrid_separable': (_int, [
+        _int, _int, _int, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp,
+        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'wb2_regrid_gather': (_int, [_int, _vp, _vp, _i64, _i64, _vp, _i64, _vp,
+                                 _vp]),
+    'wb2_regrid_geometry': (_int, [
+        _int, _int, _int, _c.POINTER(_i32), _c.POINTER(_i32),
+        _c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i32)]),
 }
 
 _lib = None

@@ -1233,6 +1233,81 @@ def derived_lead_window(mode: str, x: torch.Tensor,
   return out
 
 
+REGRID_MODES = {'nanmean': 0, 'linear': 1}
+
+
+def regrid_geometry(dtype: torch.dtype, lat_rows: bool, wide: bool) -> dict:
+  """Tile extents of the K11 regridding kernels: `tile` contiguous-axis
+  elements per workgroup pass, `run` target rows (columns) per workgroup,
+  `band` band entries a thread requests before it combines any, `max_contig`
+  the longest contiguous axis the workgroup kernels hold (longer ones take the
+  one-thread-per-cell kernel), `grid_slabs` slabs per grid row."""
+  import ctypes
+  vals = [ctypes.c_int32() for _ in range(5)]
+  _lib.check(_lib.load().wb2_regrid_geometry(
+      _DTYPES[dtype], int(lat_rows), int(wide),
+      *[ctypes.byref(v) for v in vals]), 'wb2_regrid_geometry')
+  return dict(zip(('tile', 'run', 'band', 'max_contig', 'grid_slabs'),
+                  (v.value for v in vals)))
+
+
+def regrid_separable(mode: str, x: torch.Tensor,
+                     slab: t.Optional[torch.Tensor], n_slab: int,
+                     lat_rows: bool, source_shape: tuple, target_shape: tuple,
+                     tables: t.Sequence[torch.Tensor]) -> torch.Tensor:
+  """K11 separable regridding: [n_slab, target slab] of the dtype of `x`, in
+  the layout of the input ((lat, lon) slabs when `lat_rows`, else (lon, lat)).
+  Shapes are (n_lon, n_lat); `tables` = (ptr, idx, w, nan) of the longitude
+  axis, then of the latitude axis, on the device of `x`; `slab` the int64
+  device table of the slabs (None: contiguous)."""
+  lib = _lib.load()
+  if x.dtype not in _DTYPES:
+    raise TypeError('the input must be float32 or float64')
+  if slab is not None and (slab.dtype != torch.int64
+                           or slab.numel() != n_slab):
+    raise ValueError('the slab table must hold n_slab int64')
+  (s_lon, s_lat), (t_lon, t_lat) = source_shape, target_shape
+  ptr_lon, idx_lon, w_lon, nan_lon, ptr_lat, idx_lat, w_lat, nan_lat = tables
+  for ptr, n in ((ptr_lon, t_lon), (ptr_lat, t_lat)):
+    if ptr.dtype != torch.int32 or ptr.numel() != n + 1:
+      raise ValueError('an axis table must hold n_target + 1 int32 offsets')
+  out = torch.empty((n_slab, t_lat * t_lon), dtype=x.dtype, device=x.device)
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('begin', 'regrid_separable')
+  _lib.check(lib.wb2_regrid_separable(
+      REGRID_MODES[mode], _DTYPES[x.dtype], int(lat_rows), _lib.ptr(x),
+      _lib.ptr(slab), n_slab, s_lon, s_lat, t_lon, t_lat, _lib.ptr(ptr_lon),
+      _lib.ptr(idx_lon), _lib.ptr(w_lon), _lib.ptr(nan_lon), _lib.ptr(ptr_lat),
+      _lib.ptr(idx_lat), _lib.ptr(w_lat), _lib.ptr(nan_lat), _lib.ptr(out),
+      current_stream_ptr(x.device)), 'wb2_regrid_separable')
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('end', 'regrid_separable')
+  return out
+
+
+def regrid_gather(x: torch.Tensor, slab: t.Optional[torch.Tensor],
+                  n_slab: int, n_src: int, index: torch.Tensor) -> torch.Tensor:
+  """K11 gather: out[o][j] = slab o of `x` at index[j] (int32 device table),
+  for elements of 1, 2, 4 or 8 bytes, [n_slab, len(index)] of the dtype of
+  `x`."""
+  lib = _lib.load()
+  if index.dtype != torch.int32:
+    raise ValueError('the index table must be int32')
+  if slab is not None and (slab.dtype != torch.int64
+                           or slab.numel() != n_slab):
+    raise ValueError('the slab table must hold n_slab int64')
+  out = torch.empty((n_slab, index.numel()), dtype=x.dtype, device=x.device)
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('begin', 'regrid_gather')
+  _lib.check(lib.wb2_regrid_gather(
+      x.element_size(), _lib.ptr(x), _lib.ptr(slab), n_slab, n_src,
+      _lib.ptr(index), index.numel(), _lib.ptr(out),
+      current_stream_ptr(x.device)), 'wb2_regrid_gather')
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('end', 'regrid_gather')
+  return out
+
+
 def ensemble_threshold_reduce(plan: ReductionPlan, ens: torch.Tensor,
                               member_stride: int, n_member: int, ens_slab,
                               truth: torch.Tensor, truth_slab,

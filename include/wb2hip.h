@@ -1186,6 +1186,63 @@ int wb2_regrid_geometry(int dtype, int lat_rows, int wide, int32_t* tile_elems,
                         int32_t* run_targets, int32_t* band_ahead,
                         int32_t* max_contig, int32_t* grid_slabs);
 
+/*
+ * K12: exact quantiles along one axis (scripts/compute_quantiles.py, whose
+ * numerical content is xarray's quantile: NumPy's quantile / nanquantile with
+ * method='linear').  The data is T[n_outer][n_red][n_inner], T = dtype:
+ * n_inner is the contiguous block after the reduced axis, n_outer everything
+ * before it.  Sample r of outer index o starts `slab[o * n_red + r] * n_inner`
+ * elements after `in` (DEV int64; NULL = the identity o * n_red + r), so a
+ * contiguous tensor, a sliced view, a gather and a permuted sample order
+ * differ in the table alone.  q = HOST double[n_q], each in [0, 1], taken as
+ * given (unsorted, duplicates, 0 and 1); out = DEV double[n_q][n_outer][
+ * n_inner], row i belonging to q[i].  Every count is at least 1.
+ *
+ * wb2_quantile_select, for the series x of one point:
+ *   skipna == 0: a NaN in x makes every quantile of that point (and of no
+ *     other) NaN; otherwise m = n_red.  skipna != 0: NaNs are dropped and m is
+ *     the number of values left; m == 0 gives NaN.
+ *   With s the m values in ascending order (+-inf are ordinary values):
+ *     v = q * (m - 1) in float64, lo = floor(v), hi = min(lo + 1, m - 1),
+ *     t = v - lo, a = s[lo], b = s[hi], d = b - a formed in T;
+ *     out = double(a) + double(d) * t where t < 0.5,
+ *           double(b) - double(d) * (1 - t) where t >= 0.5
+ *   (no FMA contraction).  This is NumPy's result bit for bit, its NaNs from
+ *   infinities included (inf - inf); where +0.0 and -0.0 both occur the sign
+ *   of a zero result is not pinned (NumPy's is not either).
+ * Selection is exact and sorts nothing: values become order-preserving
+ * unsigned keys of their own width (NaN above +inf, counted in the first
+ * pass); the key of rank lo is found from the most significant bit down,
+ * key_bits_per_pass bits per counting pass, after the leading bits that the
+ * smallest and the largest key of the series share; one more pass counts the
+ * keys <= it and takes the smallest key above it, which is s[hi] unless the
+ * found key repeats past lo.
+ *   n_red <= max_resident: a workgroup stages its tile of tile_points adjacent
+ *     points (64 bytes per sample row; 16-byte loads where n_inner is a
+ *     multiple of the vector and `in` is 16-byte aligned) into LDS once, as
+ *     keys; a wave then serves one quantile of the tile at a time, its lanes
+ *     being (slice of the samples, point) pairs that add their counters up by
+ *     lane exchange: the input is read from memory once, whatever n_q is (up
+ *     to 64 per launch; more are served in groups of 64).
+ *   longer series: lanes are spread over (point, slice of the samples) and
+ *     walk the samples through the table once per pass, targets_per_pass
+ *     quantiles at a time, the groups looped over inside the call.  The input
+ *     is read 1 + ceil(n_q / targets_per_pass) * (passes + 1) times: from L2 or
+ *     the Infinity Cache where the problem fits there.  This is the correct
+ *     and simple fallback, not a tuned path.
+ * wb2_quantile_geometry: points per workgroup tile (the same with wide != 0:
+ * wide loads change how a tile is staged, not its extent), the longest series
+ * of the resident regime, the quantiles that share a streaming pass and the
+ * key bits settled per counting pass.
+ */
+int wb2_quantile_select(int dtype, int skipna, const void* in,
+                        const int64_t* slab, int64_t n_outer, int64_t n_red,
+                        int64_t n_inner, const double* q, int32_t n_q,
+                        double* out, void* stream);
+int wb2_quantile_geometry(int dtype, int wide, int32_t* tile_points,
+                          int64_t* max_resident, int32_t* targets_per_pass,
+                          int32_t* key_bits_per_pass);
+
 #ifdef __cplusplus
 }
 #endif

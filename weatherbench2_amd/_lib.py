@@ -204,6 +204,11 @@ _SIGNATURES = {
     'wb2_regrid_geometry': (_int, [
         _int, _int, _int, _c.POINTER(_i32), _c.POINTER(_i32),
         _c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i32)]),
+    'wb2_quantile_select': (_int, [_int, _int, _vp, _vp, _i64, _i64, _i64,
+                                   _c.POINTER(_c.c_double), _i32, _vp, _vp]),
+    'wb2_quantile_geometry': (_int, [_int, _int, _c.POINTER(_i32),
+                                     _c.POINTER(_i64), _c.POINTER(_i32),
+                                     _c.POINTER(_i32)]),
 }
 
 _lib = None

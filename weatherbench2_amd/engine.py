@@ -1308,6 +1308,51 @@ def regrid_gather(x: torch.Tensor, slab: t.Optional[torch.Tensor],
   return out
 
 
+def quantile_geometry(dtype: torch.dtype, wide: bool = False) -> dict:
+  """Extents of the K12 quantile kernels: `tile_points` adjacent points per
+  workgroup, `max_resident` the longest series selected out of LDS (longer
+  ones stream), `targets_per_pass` quantiles that share a streaming pass,
+  `key_bits_per_pass` key bits settled per counting pass."""
+  import ctypes
+  tile, targets, bits = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+  resident = ctypes.c_int64()
+  _lib.check(_lib.load().wb2_quantile_geometry(
+      _DTYPES[dtype], int(wide), ctypes.byref(tile), ctypes.byref(resident),
+      ctypes.byref(targets), ctypes.byref(bits)), 'wb2_quantile_geometry')
+  return {'tile_points': tile.value, 'max_resident': resident.value,
+          'targets_per_pass': targets.value, 'key_bits_per_pass': bits.value}
+
+
+def quantile_select(x: torch.Tensor, slab: t.Optional[torch.Tensor],
+                    n_outer: int, n_red: int, n_inner: int, q,
+                    skipna: bool) -> torch.Tensor:
+  """K12 exact quantiles: float64 [len(q), n_outer, n_inner] of the series
+  x[o, :, i] (NumPy's quantile, or nanquantile with `skipna`, method 'linear').
+  `slab` is the int64 device table [n_outer, n_red] (sample r of outer index o
+  starts `table * n_inner` elements after the first element of `x`), None for
+  a contiguous `x`; `q` a sequence of numbers in [0, 1]."""
+  import ctypes
+  lib = _lib.load()
+  if x.dtype not in _DTYPES:
+    raise TypeError('the input must be float32 or float64')
+  if slab is not None and (slab.dtype != torch.int64
+                           or slab.numel() != n_outer * n_red):
+    raise ValueError('the slab table must hold n_outer * n_red int64')
+  qs = [float(v) for v in q]
+  q_host = (ctypes.c_double * len(qs))(*qs)
+  out = torch.empty((len(qs), n_outer, n_inner), dtype=torch.float64,
+                    device=x.device)
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('begin', 'quantile_select')
+  _lib.check(lib.wb2_quantile_select(
+      _DTYPES[x.dtype], int(bool(skipna)), _lib.ptr(x), _lib.ptr(slab), n_outer,
+      n_red, n_inner, q_host, len(qs), _lib.ptr(out),
+      current_stream_ptr(x.device)), 'wb2_quantile_select')
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('end', 'quantile_select')
+  return out
+
+
 def ensemble_threshold_reduce(plan: ReductionPlan, ens: torch.Tensor,
                               member_stride: int, n_member: int, ens_slab,
                               truth: torch.Tensor, truth_slab,

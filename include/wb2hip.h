@@ -1243,6 +1243,65 @@ int wb2_quantile_geometry(int dtype, int wide, int32_t* tile_points,
                           int64_t* max_resident, int32_t* targets_per_pass,
                           int32_t* key_bits_per_pass);
 
+/*
+ * K13: statistics over runs of a time axis (scripts/resample_in_time.py:
+ * 270-309: xarray's resample(...) and rolling(...) followed by mean, min, max
+ * or sum).  The data is T[n_outer][n_time][n_point], T = dtype: n_point is the
+ * contiguous block after the time axis, n_outer everything before it.  Time
+ * step t of outer index o starts `slab[o * n_time + t] * n_point` elements
+ * after `in` (DEV int64; NULL = the identity o * n_time + t), so a contiguous
+ * tensor, a time-sliced view, a gather and a permuted time order differ in the
+ * table alone.
+ *
+ * wb2_time_bin_stats: bin b covers the time steps [bin_range[b][0],
+ * bin_range[b][1]) of every series (DEV int32[n_bin][2]).  Bins may overlap
+ * (rolling windows: output t has the range [t - w + 1, t + 1)) and need not be
+ * ordered.  stat_mask is a sum of WB2_STAT_*; out = HOST array of the four DEV
+ * outputs in the order sum, mean, min, max, each a contiguous
+ * T[n_outer][n_bin][n_point], NULL where the statistic is not in the mask.
+ * Every bin of every outer index is written.  A bin with begin >= end, begin <
+ * 0 or end > n_time is empty or incomplete: NaN in every statistic, sum
+ * included, and nothing is read for it.  Otherwise, with x0 .. x(n-1) its
+ * samples in time order, m of them not NaN, all arithmetic in T without FMA
+ * contraction:
+ *   sum   skipna == 0: ((x0 + x1) + x2) + ..., starting from x0 itself (a bin
+ *         of -0.0 alone gives -0.0); skipna != 0: the same chain with +0.0 in
+ *         the place of every NaN (all NaN gives +0.0)
+ *   mean  skipna == 0: sum / T(n); skipna != 0: the skipna sum / T(m), NaN if
+ *         m == 0
+ *   min, max  skipna == 0: NaN if any sample is NaN; skipna != 0: over the
+ *         samples that are not NaN, NaN if m == 0.  +-inf are ordinary values;
+ *         where +0.0 and -0.0 both occur in a bin the sign of a zero result is
+ *         not pinned (NumPy's is not either).
+ * Each bin is computed afresh: no running update across bins, so a NaN touches
+ * exactly the bins that hold it.  All statistics of the mask come from one read
+ * of the input, and a statistic has the same bits whatever else is in the
+ * mask.  A thread owns adjacent points (16-byte loads where n_point is a
+ * multiple of the vector and `in` and the outputs are 16-byte aligned, scalar
+ * loads otherwise) and requests steps_ahead time steps before it combines
+ * any.  A workgroup handles one tile of points and bins_per_group >= 1
+ * consecutive bins, one after another: a small count for disjoint bins
+ * (parallelism over points x bins), a larger one for overlapping bins, whose
+ * shared terms then come from the workgroup's own cache lines.  The value
+ * changes no result.  Zero sizes are a no-op.
+ * wb2_time_window_geometry: points per workgroup tile (wide != 0: 16-byte
+ * loads), the number of time steps a thread requests before it combines any,
+ * and the number of outer indices per grid row (more are split over a further
+ * grid dimension).
+ */
+#define WB2_STAT_SUM 1
+#define WB2_STAT_MEAN 2
+#define WB2_STAT_MIN 4
+#define WB2_STAT_MAX 8
+#define WB2_STAT_ALL 15
+int wb2_time_bin_stats(int stat_mask, int dtype, int skipna, const void* in,
+                       const int64_t* slab, int64_t n_outer, int32_t n_time,
+                       int64_t n_point, const int32_t* bin_range,
+                       int32_t n_bin, int32_t bins_per_group,
+                       void* const* out, void* stream);
+int wb2_time_window_geometry(int dtype, int wide, int32_t* tile_points,
+                             int32_t* steps_ahead, int32_t* max_grid_outer);
+
 #ifdef __cplusplus
 }
 #endif

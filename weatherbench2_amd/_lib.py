@@ -209,6 +209,11 @@ _SIGNATURES = {
     'wb2_quantile_geometry': (_int, [_int, _int, _c.POINTER(_i32),
                                      _c.POINTER(_i64), _c.POINTER(_i32),
                                      _c.POINTER(_i32)]),
+    'wb2_time_bin_stats': (_int, [_int, _int, _int, _vp, _vp, _i64, _i32,
+                                  _i64, _vp, _i32, _i32, _c.POINTER(_vp),
+                                  _vp]),
+    'wb2_time_window_geometry': (_int, [_int, _int, _c.POINTER(_i32),
+                                        _c.POINTER(_i32), _c.POINTER(_i32)]),
 }
 
 _lib = None

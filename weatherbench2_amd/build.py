@@ -12,7 +12,8 @@ LIB_PATH = os.path.join(PKG_DIR, 'libwb2hip.so')
 SOURCES = ('common.cpp', 'comm.cpp', 'staging.cpp', 'program.cpp', 'stream_reduce.hip', 'ensemble.hip', 'energy_score.hip',
            'spectrum.hip', 'spectrum_fused.hip', 'spatial_maps.hip',
            'rank_histogram.hip', 'axis_reduce.hip', 'derived_fields.hip',
-           'derived_column.hip', 'derived_lead.hip', 'regrid.hip', 'quantile.hip')
+           'derived_column.hip', 'derived_lead.hip', 'regrid.hip', 'quantile.hip',
+           'time_window.hip')
 # compiled once per member count listed in sort3_networks.inc (WB2_SORT3_SIZES)
 EXACT_SOURCE = 'ensemble_exact.hip'
 

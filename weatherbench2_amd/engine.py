@@ -1353,6 +1353,66 @@ def quantile_select(x: torch.Tensor, slab: t.Optional[torch.Tensor],
   return out
 
 
+TIME_STATS = ('sum', 'mean', 'min', 'max')  # bit s of the K13 mask, in order
+
+
+def time_window_geometry(dtype: torch.dtype, wide: bool = False) -> dict:
+  """Extents of the K13 kernel: `tile_points` adjacent points per workgroup,
+  `steps_ahead` time steps a thread requests before it combines any,
+  `max_grid_outer` outer indices per grid row."""
+  import ctypes
+  tile, ahead, outer = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+  _lib.check(_lib.load().wb2_time_window_geometry(
+      _DTYPES[dtype], int(wide), ctypes.byref(tile), ctypes.byref(ahead),
+      ctypes.byref(outer)), 'wb2_time_window_geometry')
+  return {'tile_points': tile.value, 'steps_ahead': ahead.value,
+          'max_grid_outer': outer.value}
+
+
+def time_bin_stats(x: torch.Tensor, slab: t.Optional[torch.Tensor],
+                   n_outer: int, n_time: int, n_point: int,
+                   bin_range: torch.Tensor, statistics: t.Sequence[str],
+                   skipna: bool, bins_per_group: int = 1) -> dict:
+  """K13 statistics of time bins: {statistic: [n_outer, n_bin, n_point] of
+  the dtype of `x`} for the names in `statistics` (of TIME_STATS), all from
+  ONE launch and one read of `x`.  Bin b is the time steps [bin_range[b, 0],
+  bin_range[b, 1]) of the series x[o, :, i] (`bin_range` an int32 device
+  tensor [n_bin, 2]; an empty or incomplete range gives NaN).  `slab` is the
+  int64 device table [n_outer, n_time] (time step t of outer index o starts
+  `table * n_point` elements after the first element of `x`), None for a
+  contiguous `x`."""
+  lib = _lib.load()
+  if x.dtype not in _DTYPES:
+    raise TypeError('the input must be float32 or float64')
+  if slab is not None and (slab.dtype != torch.int64
+                           or slab.numel() != n_outer * n_time):
+    raise ValueError('the slab table must hold n_outer * n_time int64')
+  if (bin_range.dtype != torch.int32 or bin_range.dim() != 2
+      or bin_range.shape[1] != 2 or not bin_range.is_contiguous()
+      or bin_range.device != x.device):
+    raise ValueError('bin_range must be a contiguous int32 [n_bin, 2] on the '
+                     'device of the input')
+  names = list(dict.fromkeys(statistics))
+  unknown = [s for s in names if s not in TIME_STATS]
+  if unknown or not names:
+    raise ValueError(f'statistics must be some of {TIME_STATS}: {statistics}')
+  n_bin = int(bin_range.shape[0])
+  outs = {s: torch.empty((n_outer, n_bin, n_point), dtype=x.dtype,
+                         device=x.device) for s in names}
+  mask = sum(1 << TIME_STATS.index(s) for s in names)
+  out_ptrs = _lib.ptr_array([outs.get(s) for s in TIME_STATS])
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('begin', 'time_bin_stats')
+  _lib.check(lib.wb2_time_bin_stats(
+      mask, _DTYPES[x.dtype], int(bool(skipna)), _lib.ptr(x), _lib.ptr(slab),
+      n_outer, n_time, n_point, _lib.ptr(bin_range), n_bin,
+      int(bins_per_group), out_ptrs, current_stream_ptr(x.device)),
+             'wb2_time_bin_stats')
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('end', 'time_bin_stats')
+  return outs
+
+
 def ensemble_threshold_reduce(plan: ReductionPlan, ens: torch.Tensor,
                               member_stride: int, n_member: int, ens_slab,
                               truth: torch.Tensor, truth_slab,

@@ -347,6 +347,13 @@ __device__ __forceinline__ bool eval_slots(
 #ifndef WB2_NT_LOADS
 #define WB2_NT_LOADS 1
 #endif
+#ifndef WB2_K1_RING_DEPTH
+// Ring form of K1 (stream_partials_kernel<..., RING>): rows per wave in flight
+// of a launch that takes it by the rule of ring_choice().  Depth 4 against 3,
+// and 2 waves per workgroup (as the batch form, WB2_MAX_WG_WAVES) against 3:
+// profiles/k1_ring_headline.md.
+#define WB2_K1_RING_DEPTH 4
+#endif
 #ifndef WB2_GAUSS_GROUP
 // Gaussian modes: points of a lane's load evaluated as one straight-line block
 // (2: two dependent fp64 chains interleaved at 114 VGPRs; 4 costs a wave per SIMD)
@@ -396,6 +403,81 @@ __device__ __forceinline__ void load_wf(const WB2_GLOBAL FT* p,
   for (int e = 0; e < VEC; ++e) v[e] = (double)x[e];
 }
 
+// LDS-DMA (gfx950 `global_load_lds_dwordx4`): 16 bytes per lane straight from
+// global memory into LDS at M0 + 16 * lane, no VGPR in between.  `row` is the
+// wave-uniform row pointer (an SGPR pair), `voff` the lane's byte offset in the
+// row, `lds_dst` the wave-uniform LDS byte address of the 1 KiB destination.
+// M0 is written in the statement that reads it and restored behind it.  hipcc
+// does not count these loads (inline asm): the ring kernel waits for them
+// itself (ring_wait).
+__device__ __forceinline__ void glds16(unsigned long long row, unsigned voff,
+                                       unsigned lds_dst) {
+  unsigned keep;
+#if WB2_NT_LOADS
+  asm volatile(
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %3\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %1, %2 nt\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(voff), "s"(row), "s"(lds_dst)
+      : "memory");
+#else
+  asm volatile(
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %3\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %1, %2\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(voff), "s"(row), "s"(lds_dst)
+      : "memory");
+#endif
+}
+// The scalar loads of the ring form's prologue in one batch: the chunk's first
+// row and row count and the slab numbers of (up to) four inputs, one wait.
+// `in`, `step` and `n_col` are not read here: as operands they are in SGPRs
+// when the batch is issued, i.e. their kernel-argument loads are waited for
+// BEFORE it and not one by one between it and the first request.
+__device__ __forceinline__ void prologue_loads(
+    const int* row0_at, const int* nrow_at, const long long* const (&slab_at)[4],
+    const void* const (&in)[4], long long step, int n_col, int& row0, int& nrow,
+    long long (&slab)[4]) {
+  asm volatile(
+      "s_load_dword %0, %6, 0x0\n\t"
+      "s_load_dword %1, %7, 0x0\n\t"
+      "s_load_dwordx2 %2, %8, 0x0\n\t"
+      "s_load_dwordx2 %3, %9, 0x0\n\t"
+      "s_load_dwordx2 %4, %10, 0x0\n\t"
+      "s_load_dwordx2 %5, %11, 0x0\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&s"(row0), "=&s"(nrow), "=&s"(slab[0]), "=&s"(slab[1]),
+        "=&s"(slab[2]), "=&s"(slab[3])
+      : "s"(row0_at), "s"(nrow_at), "s"(slab_at[0]), "s"(slab_at[1]),
+        "s"(slab_at[2]), "s"(slab_at[3]), "s"(in[0]), "s"(in[1]), "s"(in[2]),
+        "s"(in[3]), "s"(step), "s"(n_col)
+      : "memory");
+}
+// s_waitcnt vmcnt(N): at most N of the wave's vector memory operations (the
+// youngest N: loads complete in order) are still on their way
+template <int N>
+__device__ __forceinline__ void ring_wait_n() {
+  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit field");
+  asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory");
+}
+// the same for `rows` (wave-uniform, 0 .. RING - 1) rows of NSLOT loads each
+template <int RING, int NSLOT>
+__device__ __forceinline__ void ring_wait(int rows) {
+  static_assert(RING >= 2 && RING <= 4, "ring_wait covers 0 .. 3 rows");
+  switch (rows) {
+    case 1: ring_wait_n<NSLOT>(); break;
+    case 2: ring_wait_n<2 * NSLOT>(); break;
+    case 3: ring_wait_n<3 * NSLOT>(); break;
+    default: ring_wait_n<0>();
+  }
+}
+
 // Geometry.  Workgroups are dealt to the 8 XCDs round-robin by their linear
 // index, and the chunks of a slab differ in size (bands cut them at region
 // boundaries, the last one is short, the padding to a multiple of 8 is empty).
@@ -421,8 +503,18 @@ __device__ __forceinline__ void load_wf(const WB2_GLOBAL FT* p,
 // lane are in flight before the first one is consumed.  The prologue is written
 // branch-free on purpose: every scalar (table / slab-index) load is issued
 // before the first wait, instead of one dependent round trip per table.
+//
+// RING > 0 (float32, 4 columns per lane, point-op modes, no field, no skipna,
+// 16-byte aligned rows): the rows of the chunk come through a ring of RING row
+// stages per wave in dynamic LDS (NIN x 1 KiB each), filled by LDS-DMA -- row
+// r + RING is requested when row r has been read out of its stage, so a wave
+// has RING rows outstanding ALL the time and none of them holds a VGPR.  The
+// batch form has its U rows in flight only while it waits for them and computes
+// with nothing outstanding.  Same loads per lane, same arithmetic in the same
+// order: the same bits.  No row at or beyond nrow is ever requested, and the
+// last row's wait is vmcnt(0): nothing is outstanding at the fold.
 template <typename T, int VEC, int MODE, bool SKIPNA, bool WF,
-          bool SG = false, typename FT = double>
+          bool SG = false, typename FT = double, int RING = 0>
 __global__ void __launch_bounds__(512)
     stream_partials_kernel(const StreamParams p) {
   using M = ModeTraits<MODE, SKIPNA>;
@@ -445,22 +537,53 @@ __global__ void __launch_bounds__(512)
       SLAB_FASTEST ? (long long)blockIdx.z * gridDim.x + blockIdx.x
                    : (long long)blockIdx.z * gridDim.y + blockIdx.y;
   int chunk = (int)(bx - tblk * (unsigned)p.n_chunk);
-  if (!SLAB_FASTEST && WB2_ROTATE_CHUNKS)
-    chunk = (int)(((long long)chunk + o) % p.n_chunk);
+  if (!SLAB_FASTEST && WB2_ROTATE_CHUNKS) {
+    // (chunk + o) % n_chunk in 32 bits (o < 2^32, chunk < n_chunk): a 64-bit
+    // `%` is a ~130-instruction scalar division in every wave's prologue
+    const unsigned rot =
+        (unsigned)chunk + (unsigned)o % (unsigned)p.n_chunk;
+    chunk = (int)(rot >= (unsigned)p.n_chunk ? rot - (unsigned)p.n_chunk : rot);
+  }
   const int tile = (int)tblk * nwave + wave;
 
   // ---- branch-free prologue: issue every scalar load before any wait ----
-  const int row0 = p.chunk_row0[chunk];
-  const int nrow = p.chunk_nrow[chunk];
+  int row0, nrow;
   long long slab_idx[NIN];
+  if constexpr (RING > 0) {
+    // ring form: what the first requests need -- row0, nrow, the slab numbers
+    // -- as ONE batch of scalar loads behind ONE wait (hipcc sinks each load
+    // to its first use and waits for them one after the other: seven waits
+    // before the first request, four with this).  The same dummy read as
+    // below when no table is given.
+    const long long* slab_at[kMaxIn];
+    const void* in[kMaxIn];
 #pragma unroll
-  for (int i = 0; i < NIN; ++i) {
-    // Identity when no table is given; the dummy read keeps the load
-    // unconditional (chunk tables are >= 8 ints, i.e. >= 4 readable int64).
-    const long long* tab =
-        p.slab[i] ? p.slab[i] : reinterpret_cast<const long long*>(p.chunk_row0);
-    const long long v = tab[(p.slab[i] && o < p.n_outer) ? o : 0];
-    slab_idx[i] = p.slab[i] ? v : o;
+    for (int i = 0; i < kMaxIn; ++i) {
+      const int j = i < NIN ? i : 0;
+      const long long* tab =
+          p.slab[j] ? p.slab[j]
+                    : reinterpret_cast<const long long*>(p.chunk_row0);
+      slab_at[i] = tab + ((p.slab[j] && o < p.n_outer) ? o : 0);
+      in[i] = p.in[j];
+    }
+    long long v[kMaxIn];
+    prologue_loads(p.chunk_row0 + chunk, p.chunk_nrow + chunk, slab_at, in,
+                   p.slab_step_bytes, p.n_col, row0, nrow, v);
+#pragma unroll
+    for (int i = 0; i < NIN; ++i) slab_idx[i] = p.slab[i] ? v[i] : o;
+  } else {
+    row0 = p.chunk_row0[chunk];
+    nrow = p.chunk_nrow[chunk];
+#pragma unroll
+    for (int i = 0; i < NIN; ++i) {
+      // Identity when no table is given; the dummy read keeps the load
+      // unconditional (chunk tables are >= 8 ints, i.e. >= 4 readable int64).
+      const long long* tab =
+          p.slab[i] ? p.slab[i]
+                    : reinterpret_cast<const long long*>(p.chunk_row0);
+      const long long v = tab[(p.slab[i] && o < p.n_outer) ? o : 0];
+      slab_idx[i] = p.slab[i] ? v : o;
+    }
   }
   const int col0 = tile * TILE + lane * VEC;  // first column the lane OWNS
   const bool active = tile < p.n_ctile && col0 < p.n_col;
@@ -504,6 +627,36 @@ __global__ void __launch_bounds__(512)
                     static_cast<const char*>(p.in[i]) +
                     slab_idx[i] * p.slab_step_bytes) +
                 (long long)row0 * p.n_col;
+    // Ring form: the first min(nrow, RING) rows are requested HERE -- they need
+    // only row0, nrow, the slab numbers and the input bases; the weight row,
+    // the seg tables and the partials pointer load behind them.
+    typedef __attribute__((address_space(3))) char* LdsPtr;
+    [[maybe_unused]] LdsPtr ring_mine = nullptr;  // the wave's RING stages
+    [[maybe_unused]] unsigned long long ring_src[NIN];  // next row to request
+    [[maybe_unused]] auto ring_request = [&](int stage) {  // wave-uniform
+      const unsigned dst = (unsigned)(unsigned long long)ring_mine +
+                           (unsigned)stage * (NIN * 1024u);
+#pragma unroll
+      for (int i = 0; i < NIN; ++i) {
+        glds16(ring_src[i], (unsigned)colb * (unsigned)sizeof(T),
+               dst + i * 1024u);
+        ring_src[i] += (unsigned long long)p.n_col * sizeof(T);
+      }
+    };
+    if constexpr (RING > 0) {
+      static_assert(sizeof(T) == 4 && VEC == 4 && !SKIPNA && !WF && !SG &&
+                        (MODE == WB2_MODE_DET || MODE == WB2_MODE_DET_ACC ||
+                         MODE == WB2_MODE_WIND),
+                    "ring form: float32 x 4 columns, point-op modes, no field");
+      extern __shared__ __attribute__((aligned(16))) char ring_lds[];
+      ring_mine = (LdsPtr)ring_lds + wave * (RING * NIN * 1024);
+#pragma unroll
+      for (int i = 0; i < NIN; ++i)
+        ring_src[i] = reinterpret_cast<unsigned long long>(base[i]);
+#pragma unroll
+      for (int q = 0; q < RING; ++q)
+        if (q < nrow) ring_request(q);
+    }
     const FT* wfp =
         WF ? static_cast<const FT*>(p.wfield) + (long long)row0 * p.n_col
            : nullptr;
@@ -691,8 +844,59 @@ __global__ void __launch_bounds__(512)
                 MODE == WB2_MODE_SEEPS ? bt.ax[u] : nullptr);
     };
     int r = 0;
+    if constexpr (RING > 0) {
+      typedef T V4 __attribute__((ext_vector_type(4)));
+      typedef const __attribute__((address_space(3))) V4* StagePtr;
+      const LdsPtr mine = ring_mine + lane * 16;
+      int stage = 0;
+      // One row: wait until it has landed (`wait` leaves the rows behind it in
+      // flight), read it out of its stage, request the next row into the stage
+      // (`more`), fold it into the accumulators.
+      auto ring_row = [&](auto wait, bool more) {
+        // the row weight by a scalar load of our own, issued before the wait:
+        // behind the asm memory clobbers hipcc turns wrp[r] into a VECTOR load
+        // and waits vmcnt(0) for it -- the ring would drain at every row
+        // (wr counts as written at the end of this statement but lands later:
+        // the "+s" of the wait below orders its uses, it does not keep the
+        // register allocator from copying the pair in between.  The loop's
+        // assembly has no access to it between the load and that wait --
+        // audit that again whenever this loop body changes.)
+        double wr;
+        asm volatile("s_load_dwordx2 %0, %1, 0x0"
+                     : "=s"(wr)
+                     : "s"(wrp + r)
+                     : "memory");
+        wait();
+        const LdsPtr st = mine + stage * (NIN * 1024);
+        T v[NIN][VEC];
+        double wf[VEC];
+#pragma unroll
+        for (int i = 0; i < NIN; ++i) {
+          const V4 x = *reinterpret_cast<StagePtr>(st + i * 1024);
+#pragma unroll
+          for (int e = 0; e < VEC; ++e) v[i][e] = x[e];
+        }
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) wf[e] = 1.0;
+        // the stage (and wr) in registers before its next row is requested
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(wr) : : "memory");
+        if (more) ring_request(stage);
+        stage = stage + 1 == RING ? 0 : stage + 1;
+        consume(v, wf, wr, nullptr);
+      };
+      // steady state: rows r + 1 .. r + RING - 1 stay in flight
 #pragma clang loop unroll(disable)
-    for (; r + U <= nrow; r += U) {
+      for (; r + RING < nrow; ++r)
+        ring_row([] { ring_wait_n<(RING - 1) * NIN>(); }, true);
+      // the last min(nrow, RING) rows: nrow - r - 1 rows behind row r, none
+      // behind the last one -- nothing is outstanding when the loop ends
+#pragma clang loop unroll(disable)
+      for (; r < nrow; ++r)
+        ring_row([&] { ring_wait<RING, NIN>(nrow - r - 1); }, false);
+    }
+    // (the batch form: both loops are empty behind the ring, r == nrow)
+#pragma clang loop unroll(disable)
+    for (; RING == 0 && r + U <= nrow; r += U) {
       Batch bt;
       issue(bt, r);
       // Keep every load of the batch in flight before the first use: without
@@ -701,7 +905,7 @@ __global__ void __launch_bounds__(512)
       eat(bt, r);
     }
 #pragma clang loop unroll(disable)
-    for (; r < nrow; ++r) {
+    for (; RING == 0 && r < nrow; ++r) {
       T v[NIN][VEC];
       double wf[VEC];
       pin_offsets();
@@ -1363,9 +1567,80 @@ bool field_f32_supported(int dtype, int mode) {
                               mode == WB2_MODE_WIND);
 }
 
+// CUs of the current device (queried once per device)
+int device_cu_count() {
+  constexpr int kMaxDev = 64;
+  static std::atomic<int> cus[kMaxDev];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return 0;
+  int n = cus[dev].load(std::memory_order_relaxed);
+  if (n == 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) !=
+            hipSuccess || n <= 0)
+      return 0;
+    cus[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+
+// Ring form of K1: the depth (rows per wave in flight) of this launch, 0 = the
+// batch form.  WB2HIP_K1_RING: unset = the rule below, 0 = always the batch
+// form, 3 / 4 = that depth wherever a ring instantiation exists (read at every
+// launch: tests and A/B runs switch inside one process).  `waves`: waves per
+// workgroup of the launch, `nin` its inputs.
+//
+// The rule: a LARGE launch -- at least four rounds of the workgroups that are
+// resident at once (CUs x workgroups per CU as the ring's LDS allows).  At
+// depth 4 the ring form has 12 waves per CU (DET_ACC: 12 KiB of LDS per wave)
+// where the batch form has 16 and so ramps up and drains slower: a launch of
+// a few rounds (one API call on one chunk) has nothing to gain from it.
+int ring_choice(const StreamParams& p, int waves, int nin) {
+  if (p.unaligned || p.n_col % 4 != 0) return 0;
+  // dynamic LDS of a launch without an opt-in attribute: a wider workgroup
+  // (WB2_MAX_WG_WAVES) whose ring does not fit keeps the batch form
+  constexpr long long kMaxRingLds = 64 * 1024;
+  if (const char* e = getenv("WB2HIP_K1_RING")) {
+    const int v = atoi(e);
+    if (v != 3 && v != 4) return 0;
+    return (long long)waves * v * nin * 1024 <= kMaxRingLds ? v : 0;
+  }
+  const int depth = WB2_K1_RING_DEPTH;
+  if (depth != 3 && depth != 4) return 0;
+  const int cus = device_cu_count();
+  if (cus <= 0) return 0;
+  constexpr long long kLdsPerCu = 160 * 1024, kMaxWavesPerCu = 32;
+  const long long lds_wg = (long long)waves * depth * nin * 1024;
+  if (lds_wg > kMaxRingLds) return 0;
+  long long wg_per_cu = kLdsPerCu / lds_wg;
+  if (wg_per_cu > kMaxWavesPerCu / waves) wg_per_cu = kMaxWavesPerCu / waves;
+  const long long n_tblk = (p.n_ctile + waves - 1) / waves;
+  const long long wgs = (long long)p.n_chunk * n_tblk * p.n_outer;
+  return wgs >= 4 * cus * wg_per_cu ? depth : 0;
+}
+
+template <typename T, int VEC, int MODE, bool SKIPNA, bool WF, int RING>
+int launch_ring(const StreamParams& p, dim3 grid, int threads,
+                hipStream_t stream) {
+  constexpr int NIN = ModeTraits<MODE, SKIPNA>::NIN;
+  const size_t lds = (size_t)(threads / kWave) * RING * NIN * 1024;
+  hipLaunchKernelGGL(
+      (stream_partials_kernel<T, VEC, MODE, SKIPNA, WF, false, double, RING>),
+      grid, dim3(threads), lds, stream, p);
+  WB2_HIP_OK(hipGetLastError());
+  return 0;
+}
+
 template <typename T, int VEC, int MODE, bool SKIPNA, bool WF>
 int launch_stream(const StreamParams& p, int threads, hipStream_t stream) {
+  // the ring form: float32, 4 columns per lane, no skipna, no field
+  constexpr bool HAS_RING = std::is_same<T, float>::value && VEC == 4 &&
+                            !SKIPNA && !WF &&
+                            (MODE == WB2_MODE_DET || MODE == WB2_MODE_DET_ACC ||
+                             MODE == WB2_MODE_WIND);
   const int nwave = threads / kWave;
+  int ring = 0;
+  if constexpr (HAS_RING)
+    ring = ring_choice(p, nwave, ModeTraits<MODE, SKIPNA>::NIN);
   const int n_tblk = (p.n_ctile + nwave - 1) / nwave;
   const long long gy = p.n_outer < 32768 ? p.n_outer : 32768;
   const long long gz = (p.n_outer + gy - 1) / gy;  // kernel guards o < n_outer
@@ -1387,6 +1662,12 @@ int launch_stream(const StreamParams& p, int threads, hipStream_t stream) {
       WB2_HIP_OK(hipGetLastError());
       return 0;
     }
+  }
+  if constexpr (HAS_RING) {
+    if (ring == 3)
+      return launch_ring<T, VEC, MODE, SKIPNA, WF, 3>(p, grid, threads, stream);
+    if (ring == 4)
+      return launch_ring<T, VEC, MODE, SKIPNA, WF, 4>(p, grid, threads, stream);
   }
   if constexpr (field_f32_supported<T, MODE>() && WF) {
     if (p.wfield_f32) {
@@ -1502,7 +1783,8 @@ __global__ void __launch_bounds__(256) seeps_map_kernel(const SeepsMapParams p) 
 
 // One wave per column tile; up to 8 tiles share a workgroup.
 #ifndef WB2_MAX_WG_WAVES
-// Waves per workgroup.  Every wave is independent (no LDS, no barrier), so the
+// Waves per workgroup.  Every wave is independent (no barrier; no LDS but the
+// ring form's own stages of each wave), so the
 // workgroup is only a scheduling unit: with 2 waves instead of 6-8 the headline
 // kernel gains 4 % (0.435 -> 0.418 ms), the weight-field and skipna
 // instantiations 8-11 % (same box, interleaved: profiles/r03_k1_variants.md) --

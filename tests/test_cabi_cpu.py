@@ -446,3 +446,174 @@ def test_pair_and_program_entry_points_validate_without_a_gpu(lib):
   assert b'finalize the program first' in h.wb2_last_error()
   assert h.wb2_program_destroy(prog) == 0
   assert h.wb2_program_destroy(None) == 0
+
+
+# ---------------------------------------------------------------------------
+# the rejection table of the entry points that launch over a reduction plan
+# ---------------------------------------------------------------------------
+_PARTIALS_TABLES = ('w_row', 'chunk_row0', 'chunk_nrow', 'seg_col0', 'seg_eoff')
+_FOLD_TABLES = ('seg_eoff', 'band_chunk0', 'coef_band', 'coef_seg', 'region_wf',
+                'region_wsum')
+_REJECT_CASES = ('empty', 'dtype', 'n_seg', 'n_chunk', 'n_ctile', 'n_outer',
+                 'seeps_aux') + tuple(
+                     'null:' + t for t in dict.fromkeys(_PARTIALS_TABLES +
+                                                        _FOLD_TABLES))
+# entry -> case -> words of wb2_last_error() (None: the entry point has no such
+# argument or accepts the case -- wb2_det_combine has no n_chunk % 8 rule and
+# no n_ctile; the folds take no dtype).  `*_all_pairs`: every slab of the
+# launch belongs to a wind-vector pair, so the pair kernel's own checks answer.
+# `null:<table>`: that table alone is null -- the tables of the partials launch
+# for the entry points that launch one first, the fold's for the folds, all ten
+# for the energy score, which checks its whole plan up front.  `seeps_aux`: a
+# launch with pairs has no mode-specific operand, whatever the plan carries.
+_PARTIALS = {'dtype': b'unknown dtype', 'null_table': b'null pointer',
+             'n_seg': b'bad sizes', 'n_chunk': b'multiple of 8',
+             'n_ctile': b'n_ctile', 'n_outer': b'too large'}
+_PAIRS = dict(_PARTIALS, n_chunk=b'bad sizes', n_outer=b'bad sizes')
+_FOLD = {'dtype': None, 'null_table': b'null pointer', 'n_seg': b'bad sizes',
+         'n_chunk': None, 'n_ctile': None, 'n_outer': None}
+_REJECT_ENTRIES = {
+    'wb2_stream_partials_ex': _PARTIALS,
+    'wb2_stream_partials_addr': _PARTIALS,
+    'wb2_stream_partials_pairs': _PARTIALS,
+    'wb2_stream_partials_pairs_all_pairs': _PAIRS,
+    'wb2_det_combine': _FOLD,
+    'wb2_ens_combine': _FOLD,
+    'wb2_det_suite_step': _PARTIALS,
+    'wb2_det_wind_suite_step': _PARTIALS,
+    'wb2_det_wind_suite_step_all_pairs': _PAIRS,
+    'wb2_ens_partials_maps': _PARTIALS,
+    'wb2_ens_partials_addr': _PARTIALS,
+    'wb2_ens_partials_gather': _PARTIALS,
+    'wb2_ens_threshold_partials': dict(_PARTIALS, n_outer=b'bad sizes'),
+    'wb2_energy_score': dict(_PARTIALS, null_table=b'null table in the plan'),
+}
+
+
+def _reject_words(entry, case):
+  """The words of `case` at `entry`, None where the cell is left out."""
+  cells = _REJECT_ENTRIES[entry]
+  if case == 'seeps_aux':
+    return b'`aux`' if 'wind_suite_step' in entry else None
+  if not case.startswith('null:'):
+    return cells[case]
+  tables = (_FOLD_TABLES if cells is _FOLD else
+            _PARTIALS_TABLES + _FOLD_TABLES if entry == 'wb2_energy_score' else
+            _PARTIALS_TABLES)
+  return cells['null_table'] if case[5:] in tables else None
+
+
+def _reject_call(lib, h, entry, case):
+  """Calls `entry` over a small valid plan (every pointer at one host buffer:
+  nothing is dereferenced before the launch) with the one defect of `case`."""
+  all_pairs = entry.endswith('_all_pairs')
+  name = entry[:-len('_all_pairs')] if all_pairs else entry
+  ens = name.startswith('wb2_ens_') or name == 'wb2_energy_score'
+  buf = np.zeros(64, dtype=np.int64)
+  b = None if case == 'empty' else buf.ctypes.data
+  v = dict(mode=lib.MODE_DET, dtype=lib.WB2_F32, n_outer=4, n_row=8, n_col=16,
+           n_chunk=8, n_seg=1, n_ts=1, n_band=1, n_region=1, nwf=1)
+  tile = (h.wb2_ens_tile_cols(v['n_col']) if ens else
+          h.wb2_tile_cols_ex(v['mode'], v['dtype'], 0, 0, v['n_col'], 1))
+  v['n_ctile'] = -(-v['n_col'] // tile)
+  tab = dict.fromkeys(('w_row', 'chunk_row0', 'chunk_nrow', 'seg_col0',
+                       'seg_eoff', 'band_chunk0', 'coef_band', 'coef_seg',
+                       'region_wf', 'region_wsum'), b)
+  if case == 'empty':
+    v['n_outer'] = 0
+  elif case == 'dtype':
+    v['dtype'] = 7
+  elif case.startswith('null:'):
+    tab[case[5:]] = None
+  elif case == 'seeps_aux':
+    v['mode'] = lib.MODE_SEEPS
+  elif case == 'n_seg':
+    v['n_seg'] = 0
+  elif case == 'n_chunk':
+    v['n_chunk'] = 12
+  elif case == 'n_ctile':
+    v['n_ctile'] += 1
+  elif case == 'n_outer':
+    v['n_outer'] = 2 ** 31
+  n_pair = v['n_outer'] // 2 if all_pairs else 0
+  # (the slab list itself is checked before the slab count by the two long
+  # forms that take one: there it is a host array of four null slabs)
+  own_list = name in ('wb2_stream_partials_ex', 'wb2_stream_partials_addr')
+  ptrs = lib.ptr_array([b] * 4) if b or own_list else None
+  # the plan as the long forms spell it, and as the struct
+  run = (v['n_row'], v['n_col'], tab['w_row'], None, None)
+  run_tail = (tab['chunk_row0'], tab['chunk_nrow'], v['n_chunk'], v['n_ctile'],
+              tab['seg_col0'], tab['seg_eoff'], v['n_seg'], v['n_ts'])
+  fold_run = (v['n_outer'], v['n_chunk'], v['nwf'], v['n_seg'],
+              tab['seg_eoff'], v['n_ts'], tab['band_chunk0'], v['n_band'],
+              tab['coef_band'], tab['coef_seg'], tab['region_wf'],
+              tab['region_wsum'], v['n_region'], None, b, None)
+  plan = ctypes.byref(lib.PlanTables(
+      wfield_dtype=lib.WB2_F64, aux=b,
+      **{k: v[k] for k in ('n_row', 'n_col', 'n_chunk', 'n_ctile', 'n_seg',
+                           'n_ts', 'n_band', 'n_region')}, **tab))
+  head = (v['mode'], v['dtype'], 0)
+  if name == 'wb2_stream_partials_ex':
+    return h.wb2_stream_partials_ex(*head, ptrs, ptrs, v['n_outer'], *run,
+                                    lib.WB2_F64, None, 0.0, *run_tail, b, None)
+  if name == 'wb2_stream_partials_addr':
+    return h.wb2_stream_partials_addr(*head, ptrs, 1, v['n_outer'], *run,
+                                      lib.WB2_F64, None, 0.0, *run_tail, b,
+                                      None)
+  if name == 'wb2_stream_partials_pairs':
+    return h.wb2_stream_partials_pairs(*head, None, ptrs, 1, v['n_outer'],
+                                       n_pair, *run, lib.WB2_F64, *run_tail, b,
+                                       b, None)
+  if name == 'wb2_det_combine':
+    return h.wb2_det_combine(v['mode'], 0, b, *fold_run)
+  if name == 'wb2_ens_combine':
+    return h.wb2_ens_combine(0, b, *fold_run)
+  if name == 'wb2_det_suite_step':
+    return h.wb2_det_suite_step(plan, *head, None, ptrs, 1, v['n_outer'], b, b,
+                                0, 0, 0, 0, None, None, None, None)
+  if name == 'wb2_det_wind_suite_step':
+    return h.wb2_det_wind_suite_step(plan, *head, None, ptrs, 1, v['n_outer'],
+                                     n_pair, b, b, b, b, None)
+  if name == 'wb2_ens_partials_maps':
+    return h.wb2_ens_partials_maps(v['dtype'], 0, b, None, b, None, 5, 128,
+                                   v['n_outer'], *run, *run_tail, b, None,
+                                   None)
+  if name == 'wb2_ens_partials_addr':
+    return h.wb2_ens_partials_addr(v['dtype'], 0, b, b, 5, 128, v['n_outer'],
+                                   *run, *run_tail, b, None)
+  if name == 'wb2_ens_partials_gather':
+    return h.wb2_ens_partials_gather(v['dtype'], 0, b, b, None, 5,
+                                     v['n_outer'], *run, *run_tail, b, None,
+                                     None)
+  if name == 'wb2_ens_threshold_partials':
+    return h.wb2_ens_threshold_partials(v['dtype'], 0, b, None, b, None, b,
+                                        None, 5, 128, v['n_outer'], *run,
+                                        *run_tail, b, None)
+  assert name == 'wb2_energy_score', name
+  return h.wb2_energy_score(v['dtype'], 0, b, None, b, None, 5, 128,
+                            v['n_outer'], plan, b, b, b, None)
+
+
+@pytest.mark.parametrize('entry,case', [
+    (e, c) for e in sorted(_REJECT_ENTRIES) for c in _REJECT_CASES
+    if c == 'empty' or _reject_words(e, c) is not None])
+def test_plan_entry_points_reject_before_any_launch(lib, entry, case):
+  """Every entry point that launches over a reduction plan, without a device:
+  no slabs is a no-op whatever the pointers are, and an unknown dtype, a null
+  table, n_seg = 0, n_chunk = 12, an n_ctile off by one from the tile width and
+  n_outer = 2^31 are refused with the words a caller is told to look for."""
+  h = lib.load()
+  if case == 'empty':
+    assert _reject_call(lib, h, entry, case) == 0
+    if entry in ('wb2_stream_partials_ex', 'wb2_stream_partials_addr'):
+      # these two look at their slab list first, empty launch or not
+      args = (lib.MODE_DET, lib.WB2_F32, 0, None) + (
+          (None,) if entry.endswith('_ex') else (1,)) + (
+              0, 8, 16, None, None, None, lib.WB2_F64, None, 0.0, None, None, 8,
+              1, None, None, 1, 1, None, None)
+      assert getattr(h, entry)(*args) < 0
+      assert b'null pointer' in h.wb2_last_error()
+    return
+  words = _reject_words(entry, case)
+  rc = _reject_call(lib, h, entry, case)
+  assert rc < 0 and words in h.wb2_last_error(), h.wb2_last_error()

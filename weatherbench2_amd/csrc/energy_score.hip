@@ -258,52 +258,28 @@ int wb2_energy_score(int dtype, int skipna, const void* ens,
   WB2_REQUIRE(n_member >= 1 && n_member <= kEnergyMaxMembers,
               "n_member=%d (1 ... %d)", n_member, kEnergyMaxMembers);
   const wb2_plan_tables& t = *plan;
-  WB2_REQUIRE(t.w_row && t.chunk_row0 && t.chunk_nrow && t.seg_col0 &&
-                  t.seg_eoff && t.band_chunk0 && t.coef_band && t.coef_seg &&
-                  t.region_wf && t.region_wsum,
-              "null table in the plan");
-  WB2_REQUIRE(t.n_row > 0 && t.n_col > 0 && t.n_chunk > 0 && t.n_seg > 0 &&
-                  t.n_ts >= t.n_seg && t.n_band > 0 && t.n_region > 0,
-              "bad sizes in the plan");
-  WB2_REQUIRE(t.n_chunk % 8 == 0, "n_chunk=%d must be a multiple of 8",
-              t.n_chunk);
-  WB2_REQUIRE(t.n_ctile == (t.n_col + kWave - 1) / kWave,
-              "n_ctile=%d does not match ceil(n_col / 64): the energy-score "
-              "pass uses the ensemble tile width (wb2_ens_tile_cols)",
-              t.n_ctile);
   WB2_REQUIRE(!t.wfield || t.wfield_dtype == WB2_F64,
               "the energy-score pass reads a float64 weight field");
   int32_t block = 0, n_block = 0, k = 0;
   if (wb2_energy_layout(n_member, skipna, t.wfield != nullptr, &block, &n_block,
                         &k) != 0)
     return -1;
-  WB2_REQUIRE(n_outer * n_block < (1ll << 31), "n_outer=%lld too large",
-              (long long)n_outer);
+  // (the ensemble tile width, wb2_ens_tile_cols; n_block virtual slabs each)
+  int rc = check_partials_plan(t, n_outer * n_block, kWave);
+  if (rc == 0) rc = check_fold_plan(t, plan_nwf(t));
+  if (rc != 0) return rc;
   EnsParams p{};
   p.ens = ens;
   p.truth = truth;
   p.ens_slab = reinterpret_cast<const long long*>(ens_slab);
   p.truth_slab = reinterpret_cast<const long long*>(truth_slab);
-  p.w_row = t.w_row;
-  p.w_col = t.w_col;
-  p.wfield = static_cast<const double*>(t.wfield);
-  p.chunk_row0 = t.chunk_row0;
-  p.chunk_nrow = t.chunk_nrow;
-  p.seg_col0 = t.seg_col0;
-  p.seg_eoff = t.seg_eoff;
+  fill_plan_fields(p, t);
   p.partials = partials;
   p.member_stride = member_stride;
   p.n_outer = n_outer;
   p.n_member = n_member;
-  p.n_row = t.n_row;
-  p.n_col = t.n_col;
-  p.n_chunk = t.n_chunk;
-  p.n_ctile = t.n_ctile;
-  p.n_seg = t.n_seg;
-  p.n_ts = t.n_ts;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool sk = skipna != 0, wf = t.wfield != nullptr;
-  int rc;
   if (dtype == WB2_F32)
     rc = block != 4 ? launch_energy<float, WB2_ENERGY_B>(p, n_block, sk, wf, s)
                     : launch_energy<float, 4>(p, n_block, sk, wf, s);
@@ -312,11 +288,8 @@ int wb2_energy_score(int dtype, int skipna, const void* ens,
                     : launch_energy<double, 4>(p, n_block, sk, wf, s);
   if (rc != 0) return rc;
   // spatial means of every (virtual slab, slot): the generic combine
-  rc = combine_slots(WB2_MODE_GAUSS, skipna, k, partials, n_outer * n_block,
-                     t.n_chunk, wf ? 2 : 1, t.n_seg, t.seg_eoff, t.n_ts,
-                     t.band_chunk0, t.n_band, t.coef_band, t.coef_seg,
-                     t.region_wf, t.region_wsum, t.n_region, nullptr, means,
-                     stream);
+  rc = combine_slots(t, WB2_MODE_GAUSS, skipna, k, plan_nwf(t), partials,
+                     n_outer * n_block, nullptr, means, stream);
   if (rc != 0) return rc;
   const long long n = (long long)t.n_region * n_outer;
   WB2_REQUIRE(n < (1ll << 31), "n_region * n_outer too large");

@@ -288,7 +288,53 @@ int launch_ens_npad(const EnsParams& p, bool skipna, bool wf,
   return launch_ens<T, 0, 0>(p, skipna, wf, stream);  // any size, no sort
 }
 
+// The one body behind the ensemble partials entry points: `q.e` comes with the
+// slabs' addressing, the member count and the maps filled in (`slabs_given`:
+// none of the pointers that entry point needs is null), `q.thr` with the
+// threshold operand of wb2_ens_threshold_partials (NULL: the K3 kernels).
+// `max_member`: the member cap of the gathered form, 0 = none.
+int ens_partials(const wb2_plan_tables& t, int dtype, int skipna, EnsThrParams q,
+                 bool slabs_given, int max_member, int64_t n_outer,
+                 double* partials, void* stream) {
+  EnsParams& p = q.e;
+  WB2_REQUIRE(dtype == WB2_F32 || dtype == WB2_F64, "unknown dtype %d", dtype);
+  WB2_EMPTY_OK(n_outer);
+  WB2_REQUIRE(slabs_given && partials, "null pointer argument");
+  WB2_REQUIRE(p.n_member >= 1, "n_member=%d", p.n_member);
+  WB2_REQUIRE(max_member == 0 || p.n_member <= max_member,
+              "n_member=%d: gathered ensembles go through the register sort "
+              "(<= %d members of this dtype)", p.n_member, max_member);
+  if (int rc = check_partials_plan(t, n_outer, kWave)) return rc;
+  WB2_REQUIRE(!t.wfield || t.wfield_dtype == WB2_F64,
+              "the ensemble kernels read a float64 weight field");
+  fill_plan_fields(p, t);
+  p.partials = partials;
+  p.n_outer = n_outer;
+  const bool sk = skipna != 0, wf = t.wfield != nullptr;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (!q.thr)
+    return dtype == WB2_F32 ? launch_ens_npad<float>(p, sk, wf, s)
+                            : launch_ens_npad<double>(p, sk, wf, s);
+  return dtype == WB2_F32 ? launch_ens_threshold<float>(q, sk, wf, s)
+                          : launch_ens_threshold<double>(q, sk, wf, s);
+}
+
 }  // namespace
+
+int ens_partials_addr(const wb2_plan_tables& t, int dtype, int skipna,
+                      const int64_t* ens_addr, const int64_t* truth_addr,
+                      int32_t n_member, int64_t member_stride, int64_t n_outer,
+                      double* partials, void* stream) {
+  EnsThrParams q{};  // ens, truth NULL: the tables hold byte addresses
+  q.e.ens_scale = q.e.truth_scale = 1;
+  q.e.ens_slab = reinterpret_cast<const long long*>(ens_addr);
+  q.e.truth_slab = reinterpret_cast<const long long*>(truth_addr);
+  q.e.member_stride = member_stride;
+  q.e.n_member = n_member;
+  return ens_partials(t, dtype, skipna, q, ens_addr && truth_addr, 0,
+                      n_outer, partials, stream);
+}
+
 }  // namespace wb2
 
 extern "C" {
@@ -331,50 +377,19 @@ int wb2_ens_partials_maps(int dtype, int skipna, const void* ens,
                           double* maps, void* stream) {
   WB2_TRACE();
   using namespace wb2;
-  WB2_REQUIRE(dtype == WB2_F32 || dtype == WB2_F64, "unknown dtype %d", dtype);
-  WB2_EMPTY_OK(n_outer);
-  WB2_REQUIRE(ens && truth && w_row && chunk_row0 && chunk_nrow && seg_col0 &&
-                  seg_eoff && partials,
-              "null pointer argument");
-  WB2_REQUIRE(n_member >= 1, "n_member=%d", n_member);
-  WB2_REQUIRE(n_outer >= 0 && n_row > 0 && n_col > 0 && n_chunk > 0 &&
-                  n_seg > 0 && n_ts >= n_seg,
-              "bad sizes");
-  WB2_REQUIRE(n_chunk % 8 == 0, "n_chunk=%d must be a multiple of 8", n_chunk);
-  WB2_REQUIRE(n_outer < (1ll << 31), "n_outer=%lld too large",
-              (long long)n_outer);
-  WB2_REQUIRE(n_ctile == (n_col + kWave - 1) / kWave,
-              "n_ctile=%d does not match ceil(n_col / 64)", n_ctile);
-  if (n_outer == 0) return 0;
-  EnsParams p{};
-  p.ens = ens;
-  p.truth = truth;
-  p.ens_slab = reinterpret_cast<const long long*>(ens_slab);
-  p.truth_slab = reinterpret_cast<const long long*>(truth_slab);
-  p.w_row = w_row;
-  p.w_col = w_col;
-  p.wfield = wfield;
-  p.chunk_row0 = chunk_row0;
-  p.chunk_nrow = chunk_nrow;
-  p.seg_col0 = seg_col0;
-  p.seg_eoff = seg_eoff;
-  p.partials = partials;
-  p.maps = maps;
-  p.member_stride = member_stride;
-  p.ens_scale = p.truth_scale =
+  WB2_PLAN_OF_ARGS(t, WB2_F64);
+  EnsThrParams q{};
+  q.e.ens = ens;
+  q.e.truth = truth;
+  q.e.ens_slab = reinterpret_cast<const long long*>(ens_slab);
+  q.e.truth_slab = reinterpret_cast<const long long*>(truth_slab);
+  q.e.ens_scale = q.e.truth_scale =
       (long long)n_row * n_col * (dtype == WB2_F32 ? 4 : 8);
-  p.n_outer = n_outer;
-  p.n_member = n_member;
-  p.n_row = n_row;
-  p.n_col = n_col;
-  p.n_chunk = n_chunk;
-  p.n_ctile = n_ctile;
-  p.n_seg = n_seg;
-  p.n_ts = n_ts;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == WB2_F32)
-    return launch_ens_npad<float>(p, skipna != 0, wfield != nullptr, s);
-  return launch_ens_npad<double>(p, skipna != 0, wfield != nullptr, s);
+  q.e.member_stride = member_stride;
+  q.e.n_member = n_member;
+  q.e.maps = maps;
+  return ens_partials(t, dtype, skipna, q, ens && truth, 0, n_outer, partials,
+                      stream);
 }
 
 int wb2_ens_partials_addr(int dtype, int skipna, const int64_t* ens_addr,
@@ -388,48 +403,10 @@ int wb2_ens_partials_addr(int dtype, int skipna, const int64_t* ens_addr,
                           int32_t n_seg, int32_t n_ts, double* partials,
                           void* stream) {
   WB2_TRACE();
-  using namespace wb2;
-  WB2_REQUIRE(dtype == WB2_F32 || dtype == WB2_F64, "unknown dtype %d", dtype);
-  WB2_EMPTY_OK(n_outer);
-  WB2_REQUIRE(ens_addr && truth_addr && w_row && chunk_row0 && chunk_nrow &&
-                  seg_col0 && seg_eoff && partials,
-              "null pointer argument");
-  WB2_REQUIRE(n_member >= 1 && n_outer >= 0 && n_row > 0 && n_col > 0 &&
-                  n_chunk > 0 && n_seg > 0 && n_ts >= n_seg,
-              "bad sizes");
-  WB2_REQUIRE(n_chunk % 8 == 0, "n_chunk=%d must be a multiple of 8", n_chunk);
-  WB2_REQUIRE(n_outer < (1ll << 31), "n_outer=%lld too large",
-              (long long)n_outer);
-  WB2_REQUIRE(n_ctile == (n_col + kWave - 1) / kWave,
-              "n_ctile=%d does not match ceil(n_col / 64)", n_ctile);
-  if (n_outer == 0) return 0;
-  EnsParams p{};
-  p.ens = nullptr;    // the tables hold byte addresses
-  p.truth = nullptr;
-  p.ens_scale = p.truth_scale = 1;
-  p.ens_slab = reinterpret_cast<const long long*>(ens_addr);
-  p.truth_slab = reinterpret_cast<const long long*>(truth_addr);
-  p.w_row = w_row;
-  p.w_col = w_col;
-  p.wfield = wfield;
-  p.chunk_row0 = chunk_row0;
-  p.chunk_nrow = chunk_nrow;
-  p.seg_col0 = seg_col0;
-  p.seg_eoff = seg_eoff;
-  p.partials = partials;
-  p.member_stride = member_stride;
-  p.n_outer = n_outer;
-  p.n_member = n_member;
-  p.n_row = n_row;
-  p.n_col = n_col;
-  p.n_chunk = n_chunk;
-  p.n_ctile = n_ctile;
-  p.n_seg = n_seg;
-  p.n_ts = n_ts;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == WB2_F32)
-    return launch_ens_npad<float>(p, skipna != 0, wfield != nullptr, s);
-  return launch_ens_npad<double>(p, skipna != 0, wfield != nullptr, s);
+  WB2_PLAN_OF_ARGS(t, WB2_F64);
+  return wb2::ens_partials_addr(t, dtype, skipna, ens_addr, truth_addr,
+                                n_member, member_stride, n_outer, partials,
+                                stream);
 }
 
 int wb2_ens_partials_gather(int dtype, int skipna, const int64_t* member_ptr,
@@ -445,52 +422,18 @@ int wb2_ens_partials_gather(int dtype, int skipna, const int64_t* member_ptr,
                             void* stream) {
   WB2_TRACE();
   using namespace wb2;
-  WB2_REQUIRE(dtype == WB2_F32 || dtype == WB2_F64, "unknown dtype %d", dtype);
-  WB2_EMPTY_OK(n_outer);
-  WB2_REQUIRE(member_ptr && truth && w_row && chunk_row0 && chunk_nrow &&
-                  seg_col0 && seg_eoff && partials,
-              "null pointer argument");
-  const int max_member = dtype == WB2_F32 ? 128 : 64;
-  WB2_REQUIRE(n_member >= 1 && n_member <= max_member,
-              "n_member=%d: gathered ensembles go through the register sort "
-              "(<= %d members of this dtype)", n_member, max_member);
-  WB2_REQUIRE(n_outer >= 0 && n_row > 0 && n_col > 0 && n_chunk > 0 &&
-                  n_seg > 0 && n_ts >= n_seg,
-              "bad sizes");
-  WB2_REQUIRE(n_chunk % 8 == 0, "n_chunk=%d must be a multiple of 8", n_chunk);
-  WB2_REQUIRE(n_outer < (1ll << 31), "n_outer=%lld too large",
-              (long long)n_outer);
-  WB2_REQUIRE(n_ctile == (n_col + kWave - 1) / kWave,
-              "n_ctile=%d does not match ceil(n_col / 64)", n_ctile);
-  if (n_outer == 0) return 0;
-  EnsParams p{};
-  p.ens = truth;  // unused with member_ptr; any valid address
-  p.truth = truth;
-  p.ens_scale = p.truth_scale =
+  WB2_PLAN_OF_ARGS(t, WB2_F64);
+  EnsThrParams q{};
+  q.e.ens = truth;  // unused with member_ptr; any valid address
+  q.e.truth = truth;
+  q.e.truth_slab = reinterpret_cast<const long long*>(truth_slab);
+  q.e.member_ptr = reinterpret_cast<const long long*>(member_ptr);
+  q.e.ens_scale = q.e.truth_scale =
       (long long)n_row * n_col * (dtype == WB2_F32 ? 4 : 8);
-  p.truth_slab = reinterpret_cast<const long long*>(truth_slab);
-  p.member_ptr = reinterpret_cast<const long long*>(member_ptr);
-  p.w_row = w_row;
-  p.w_col = w_col;
-  p.wfield = wfield;
-  p.chunk_row0 = chunk_row0;
-  p.chunk_nrow = chunk_nrow;
-  p.seg_col0 = seg_col0;
-  p.seg_eoff = seg_eoff;
-  p.partials = partials;
-  p.maps = maps;
-  p.n_outer = n_outer;
-  p.n_member = n_member;
-  p.n_row = n_row;
-  p.n_col = n_col;
-  p.n_chunk = n_chunk;
-  p.n_ctile = n_ctile;
-  p.n_seg = n_seg;
-  p.n_ts = n_ts;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == WB2_F32)
-    return launch_ens_npad<float>(p, skipna != 0, wfield != nullptr, s);
-  return launch_ens_npad<double>(p, skipna != 0, wfield != nullptr, s);
+  q.e.n_member = n_member;
+  q.e.maps = maps;
+  return ens_partials(t, dtype, skipna, q, member_ptr && truth,
+                      dtype == WB2_F32 ? 128 : 64, n_outer, partials, stream);
 }
 
 int wb2_ens_threshold_partials(
@@ -504,48 +447,18 @@ int wb2_ens_threshold_partials(
     int32_t n_ts, double* partials, void* stream) {
   WB2_TRACE();
   using namespace wb2;
-  WB2_REQUIRE(dtype == WB2_F32 || dtype == WB2_F64, "unknown dtype %d", dtype);
-  WB2_EMPTY_OK(n_outer);
-  WB2_REQUIRE(ens && truth && threshold && w_row && chunk_row0 && chunk_nrow &&
-                  seg_col0 && seg_eoff && partials,
-              "null pointer argument");
-  WB2_REQUIRE(n_member >= 1, "n_member=%d", n_member);
-  WB2_REQUIRE(n_outer >= 0 && n_outer < (1ll << 31) && n_row > 0 && n_col > 0 &&
-                  n_chunk > 0 && n_seg > 0 && n_ts >= n_seg,
-              "bad sizes");
-  WB2_REQUIRE(n_chunk % 8 == 0, "n_chunk=%d must be a multiple of 8", n_chunk);
-  WB2_REQUIRE(n_ctile == (n_col + kWave - 1) / kWave,
-              "n_ctile=%d does not match ceil(n_col / 64)", n_ctile);
-  if (n_outer == 0) return 0;
+  WB2_PLAN_OF_ARGS(t, WB2_F64);
   EnsThrParams q{};
-  EnsParams& p = q.e;
-  p.ens = ens;
-  p.truth = truth;
-  p.ens_slab = reinterpret_cast<const long long*>(ens_slab);
-  p.truth_slab = reinterpret_cast<const long long*>(truth_slab);
-  p.w_row = w_row;
-  p.w_col = w_col;
-  p.wfield = wfield;
-  p.chunk_row0 = chunk_row0;
-  p.chunk_nrow = chunk_nrow;
-  p.seg_col0 = seg_col0;
-  p.seg_eoff = seg_eoff;
-  p.partials = partials;
-  p.member_stride = member_stride;
-  p.n_outer = n_outer;
-  p.n_member = n_member;
-  p.n_row = n_row;
-  p.n_col = n_col;
-  p.n_chunk = n_chunk;
-  p.n_ctile = n_ctile;
-  p.n_seg = n_seg;
-  p.n_ts = n_ts;
+  q.e.ens = ens;
+  q.e.truth = truth;
+  q.e.ens_slab = reinterpret_cast<const long long*>(ens_slab);
+  q.e.truth_slab = reinterpret_cast<const long long*>(truth_slab);
+  q.e.member_stride = member_stride;
+  q.e.n_member = n_member;
   q.thr = threshold;
   q.thr_slab = reinterpret_cast<const long long*>(thr_slab);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == WB2_F32)
-    return launch_ens_threshold<float>(q, skipna != 0, wfield != nullptr, s);
-  return launch_ens_threshold<double>(q, skipna != 0, wfield != nullptr, s);
+  return ens_partials(t, dtype, skipna, q, ens && truth && threshold, 0,
+                      n_outer, partials, stream);
 }
 
 int wb2_ens_threshold_maps(int dtype, int skipna, const void* ens,

@@ -19,12 +19,14 @@
 //      tables: the table of chunk k travels while the kernels of chunk k - 1
 //      run; the host waits only when it is kRing chunks ahead of the GPU);
 //   2. every recorded launch -- wb2_det_suite_step / wb2_det_wind_suite_step,
-//      or wb2_ens_partials_addr + wb2_ens_combine for an ensemble pass --
+//      or the bodies of wb2_ens_partials_addr + wb2_ens_combine for an
+//      ensemble pass --
 //      i.e. the kernels of the generic path, bit for bit; launches marked
 //      `side` (the one-slab SEEPS passes: latency-bound) run on a second
 //      stream beside the big one and join before step 3;
 //   3. one wb2_gather_accumulate[_rows] per sink (eval config).
 #include "common.hpp"
+#include "reduce_common.hpp"
 #include "trace.hpp"
 #include "wb2hip.h"
 
@@ -400,19 +402,12 @@ int wb2_program_replay(void* program, const int64_t* ptrs, int32_t n_ptrs,
       slabs[j] = dev + la.table_offset + (long long)j * la.n_outer;
     double* metrics = p->arena + la.arena_offset;
     if (la.ensemble) {
-      const wb2_plan_tables& t = la.plan;
-      int rc = wb2_ens_partials_addr(
-          la.dtype, la.skipna, slabs[0], slabs[1], la.n_member,
-          la.member_stride, la.n_outer, t.n_row, t.n_col, t.w_row, t.w_col,
-          static_cast<const double*>(t.wfield), t.chunk_row0, t.chunk_nrow,
-          t.n_chunk, t.n_ctile, t.seg_col0, t.seg_eoff, t.n_seg, t.n_ts,
-          la.partials, ls);
+      int rc = ens_partials_addr(la.plan, la.dtype, la.skipna, slabs[0],
+                                 slabs[1], la.n_member, la.member_stride,
+                                 la.n_outer, la.partials, ls);
       if (rc != 0) return rc;
-      return wb2_ens_combine(la.skipna, la.partials, la.n_outer, t.n_chunk,
-                             t.wfield ? 2 : 1, t.n_seg, t.seg_eoff, t.n_ts,
-                             t.band_chunk0, t.n_band, t.coef_band, t.coef_seg,
-                             t.region_wf, t.region_wsum, t.n_region, nullptr,
-                             metrics, ls);
+      return combine_mode(la.plan, WB2_MODE_ENS, la.skipna, plan_nwf(la.plan),
+                          la.partials, la.n_outer, nullptr, metrics, ls);
     }
     if (la.n_pair > 0) {
       const long long n_det =

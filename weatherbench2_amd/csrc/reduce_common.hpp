@@ -2,6 +2,7 @@
 #pragma once
 
 #include "common.hpp"
+#include "wb2hip.h"
 
 #include <cstdint>
 
@@ -16,15 +17,107 @@
 
 namespace wb2 {
 
-// wb2_det_combine with the slot count given (stream_reduce.hip)
-int combine_slots(int mode, int skipna, int k_slots, const double* partials,
-                  int64_t n_outer, int32_t n_chunk, int32_t nwf, int32_t n_seg,
-                  const int32_t* seg_eoff, int32_t n_ts,
-                  const int32_t* band_chunk0, int32_t n_band,
-                  const double* coef_band, const double* coef_seg,
-                  const int32_t* region_wf, const double* region_wsum,
-                  int32_t n_region, double* sums, double* metrics,
-                  void* stream);
+// ---- the reduction plan on the host ------------------------------------------
+// Behind the C ABI a plan travels as ONE wb2_plan_tables: the struct entry
+// points pass theirs on, the long forms collect their arguments into one.
+
+// The partials part of a plan from the arguments of a long-form entry point
+// (they all carry these names); `field_dtype`: what `wfield` holds.
+#define WB2_PLAN_OF_ARGS(t, field_dtype) \
+  wb2_plan_tables t{};                   \
+  t.n_row = n_row;                       \
+  t.n_col = n_col;                       \
+  t.n_chunk = n_chunk;                   \
+  t.n_ctile = n_ctile;                   \
+  t.n_seg = n_seg;                       \
+  t.n_ts = n_ts;                         \
+  t.w_row = w_row;                       \
+  t.w_col = w_col;                       \
+  t.wfield = wfield;                     \
+  t.wfield_dtype = field_dtype;          \
+  t.chunk_row0 = chunk_row0;             \
+  t.chunk_nrow = chunk_nrow;             \
+  t.seg_col0 = seg_col0;                 \
+  t.seg_eoff = seg_eoff
+
+inline int plan_nwf(const wb2_plan_tables& t) { return t.wfield ? 2 : 1; }
+
+// What a partials launch over `n_slab` slabs (n_outer, or the virtual slabs of
+// the energy-score pass) needs of a plan; `tile_cols`: the columns of one
+// column tile of the kernel that is launched.  Every size message opens with
+// "bad sizes": the copies this check replaced reported n_chunk % 8 and the slab
+// count either under those words or under "multiple of 8" / "too large", and a
+// caller that looks for either finds it.
+inline int check_partials_plan(const wb2_plan_tables& t, int64_t n_slab,
+                               int tile_cols) {
+  WB2_REQUIRE(t.w_row && t.chunk_row0 && t.chunk_nrow && t.seg_col0 &&
+                  t.seg_eoff,
+              "null pointer argument: a null table in the plan");
+  WB2_REQUIRE(t.n_row > 0 && t.n_col > 0 && t.n_chunk > 0 && t.n_seg > 0 &&
+                  t.n_ts >= t.n_seg,
+              "bad sizes: n_row=%d n_col=%d n_chunk=%d n_seg=%d n_ts=%d",
+              t.n_row, t.n_col, t.n_chunk, t.n_seg, t.n_ts);
+  WB2_REQUIRE(t.n_chunk % 8 == 0,
+              "bad sizes: n_chunk=%d must be a multiple of 8", t.n_chunk);
+  WB2_REQUIRE(n_slab < (1ll << 31),
+              "bad sizes: n_outer too large (a launch over %lld slabs)",
+              (long long)n_slab);
+  WB2_REQUIRE(t.n_ctile == (t.n_col + tile_cols - 1) / tile_cols,
+              "n_ctile=%d does not match ceil(n_col / %d): the tile width is "
+              "wb2_tile_cols_ex() of this launch (inputs 16-byte aligned iff "
+              "it was asked so), wb2_ens_tile_cols() for the ensemble kernels",
+              t.n_ctile, tile_cols);
+  return 0;
+}
+
+// What the fold of partials with `nwf` weight sets needs of a plan.
+inline int check_fold_plan(const wb2_plan_tables& t, int nwf) {
+  WB2_REQUIRE(t.seg_eoff && t.band_chunk0 && t.coef_band && t.coef_seg &&
+                  t.region_wf && t.region_wsum,
+              "null pointer argument: a null table in the plan");
+  WB2_REQUIRE(t.n_chunk > 0 && t.n_seg > 0 && t.n_ts >= t.n_seg &&
+                  (nwf == 1 || nwf == 2) && t.n_band > 0 && t.n_region > 0,
+              "bad sizes: n_chunk=%d n_seg=%d n_ts=%d nwf=%d n_band=%d "
+              "n_region=%d",
+              t.n_chunk, t.n_seg, t.n_ts, nwf, t.n_band, t.n_region);
+  return 0;
+}
+
+// The plan's part of a kernel-parameter struct (StreamParams, EnsParams).
+template <typename P>
+void fill_plan_fields(P& p, const wb2_plan_tables& t) {
+  p.w_row = t.w_row;
+  p.w_col = t.w_col;
+  p.wfield = static_cast<decltype(p.wfield)>(t.wfield);
+  p.chunk_row0 = t.chunk_row0;
+  p.chunk_nrow = t.chunk_nrow;
+  p.seg_col0 = t.seg_col0;
+  p.seg_eoff = t.seg_eoff;
+  p.n_row = t.n_row;
+  p.n_col = t.n_col;
+  p.n_chunk = t.n_chunk;
+  p.n_ctile = t.n_ctile;
+  p.n_seg = t.n_seg;
+  p.n_ts = t.n_ts;
+}
+
+// The fold of `partials` ([n_outer][n_chunk][nwf][n_ts][k_slots]) into every
+// region (stream_reduce.hip).  combine_slots: the slot count given (the
+// energy-score pass folds 2 x block member sums per virtual slab: a generic
+// mode whose slot count is not a function of the mode alone); combine_mode:
+// the slot count of `mode` -- the body of wb2_det_combine.
+int combine_slots(const wb2_plan_tables& t, int mode, int skipna, int k_slots,
+                  int nwf, const double* partials, int64_t n_outer,
+                  double* sums, double* metrics, void* stream);
+int combine_mode(const wb2_plan_tables& t, int mode, int skipna, int nwf,
+                 const double* partials, int64_t n_outer, double* sums,
+                 double* metrics, void* stream);
+
+// The body of wb2_ens_partials_addr (ensemble.hip).
+int ens_partials_addr(const wb2_plan_tables& t, int dtype, int skipna,
+                      const int64_t* ens_addr, const int64_t* truth_addr,
+                      int32_t n_member, int64_t member_stride, int64_t n_outer,
+                      double* partials, void* stream);
 
 // ---- many sums at once -------------------------------------------------------
 // Sums N per-lane doubles v[0..N) across the 64 lanes of a wave with a HALVING

@@ -1815,98 +1815,77 @@ int mode_nin(int mode) {
 namespace wb2 {
 namespace {
 
-// The one body behind wb2_stream_partials[_ex] (in[] + slab NUMBERS) and
-// wb2_stream_partials_addr (slab ADDRESSES, in == nullptr).
-int stream_partials_impl(int mode, int dtype, int skipna, const void* const* in,
-                         const int64_t* const* slab, int addr_aligned16,
-                         int64_t n_outer, int32_t n_row, int32_t n_col,
-                         const double* w_row, const double* w_col,
-                         const void* wfield, int wfield_dtype,
-                         const double* aux, double scalar,
-                         const int32_t* chunk_row0, const int32_t* chunk_nrow,
-                         int32_t n_chunk, int32_t n_ctile,
-                         const int32_t* seg_col0, const int32_t* seg_eoff,
-                         int32_t n_seg, int32_t n_ts, double* partials,
-                         void* stream) {
+// The StreamParams of a launch over plan `t` whose inputs are given by base +
+// slab NUMBERS (in[]) or by slab ADDRESSES (in == nullptr); what only the
+// per-variable kernel reads (aux, scalar, unaligned) is left to its launch.
+int stream_params(const wb2_plan_tables& t, int mode, int dtype,
+                  const void* const* in, const int64_t* const* slab,
+                  int64_t n_outer, double* partials, StreamParams& p) {
   const bool by_addr = in == nullptr;
-  WB2_REQUIRE(mode == WB2_MODE_DET || mode == WB2_MODE_DET_ACC ||
-                  mode == WB2_MODE_WIND || mode == WB2_MODE_GAUSS ||
-                  mode == WB2_MODE_GAUSS_THR || mode == WB2_MODE_SEEPS,
-              "unknown mode %d", mode);
-  WB2_REQUIRE(mode != WB2_MODE_SEEPS || aux != nullptr,
-              "WB2_MODE_SEEPS needs the p1 field in `aux`");
-  WB2_REQUIRE(dtype == WB2_F32 || dtype == WB2_F64, "unknown dtype %d", dtype);
-  WB2_REQUIRE(!wfield || wfield_dtype == WB2_F64 ||
-                  (wfield_dtype == WB2_F32 && field_f32_supported(dtype, mode)),
-              "a float32 weight field goes with float32 inputs of the modes "
-              "DET / DET_ACC / WIND (wfield_dtype=%d dtype=%d mode=%d)",
-              wfield_dtype, dtype, mode);
-  WB2_EMPTY_OK(n_outer);
-  WB2_REQUIRE((in || slab) && w_row && chunk_row0 && chunk_nrow && seg_col0 &&
-                  seg_eoff && partials,
-              "null pointer argument");
-  WB2_REQUIRE(n_outer >= 0 && n_row > 0 && n_col > 0 && n_chunk > 0 &&
-                  n_seg > 0,
-              "bad sizes: n_outer=%lld n_row=%d n_col=%d n_chunk=%d n_seg=%d",
-              (long long)n_outer, n_row, n_col, n_chunk, n_seg);
-  if (n_outer == 0) return 0;
-  WB2_REQUIRE(n_chunk % 8 == 0, "n_chunk=%d must be a multiple of 8", n_chunk);
-  WB2_REQUIRE(n_outer < (1ll << 31), "n_outer=%lld too large",
-              (long long)n_outer);
-  StreamParams p{};
-  const int nin = mode_nin(mode);
-  const long long elem = dtype == WB2_F32 ? 4 : 8;
-  bool aligned = by_addr ? addr_aligned16 != 0 : true;
-  for (int i = 0; i < nin; ++i) {
+  for (int i = 0; i < mode_nin(mode); ++i) {
     if (by_addr) {
       WB2_REQUIRE(slab[i] != nullptr, "address table %d is null", i);
-      p.in[i] = nullptr;
       p.slab[i] = reinterpret_cast<const long long*>(slab[i]);
       continue;
     }
     WB2_REQUIRE(in[i] != nullptr, "input %d is null", i);
     p.in[i] = in[i];
     p.slab[i] = slab ? reinterpret_cast<const long long*>(slab[i]) : nullptr;
-    aligned = aligned && (reinterpret_cast<uintptr_t>(in[i]) % 16 == 0);
   }
-  p.slab_step_bytes = by_addr ? 1 : (long long)n_row * n_col * elem;
-  if (wfield) aligned = aligned && reinterpret_cast<uintptr_t>(wfield) % 16 == 0;
-  const int vec = vec_width(mode, dtype, skipna != 0, wfield != nullptr, n_col);
-  const int threads = threads_for(n_col, vec);
-  p.unaligned = !aligned || ((long long)n_col * elem) % 16 != 0;
-  p.w_row = w_row;
-  p.w_col = w_col;
-  p.wfield = wfield;
-  p.wfield_f32 = wfield && wfield_dtype == WB2_F32;
-  p.aux = aux;
-  p.scalar = scalar;
-  p.chunk_row0 = chunk_row0;
-  p.chunk_nrow = chunk_nrow;
-  p.seg_col0 = seg_col0;
-  p.seg_eoff = seg_eoff;
-  p.n_ts = n_ts;
+  p.slab_step_bytes =
+      by_addr ? 1 : (long long)t.n_row * t.n_col * (dtype == WB2_F32 ? 4 : 8);
+  fill_plan_fields(p, t);
+  p.wfield_f32 = t.wfield && t.wfield_dtype == WB2_F32;
   p.partials = partials;
   p.n_outer = n_outer;
-  p.n_row = n_row;
-  p.n_col = n_col;
-  p.n_chunk = n_chunk;
-  p.n_ctile = (n_col + kWave * vec - 1) / (kWave * vec);
-  WB2_REQUIRE(p.n_ctile == n_ctile,
-              "n_ctile=%d does not match the launch geometry (%d): inputs "
-              "must be 16-byte aligned iff wb2_tile_cols_ex() was asked so",
-              n_ctile, p.n_ctile);
-  p.n_seg = n_seg;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == WB2_F32)
-    return launch_stream_mode<float, WB2_F32_VEC>(p, mode, vec, skipna != 0,
-                                        wfield != nullptr, threads, s);
-  return launch_stream_mode<double, 2>(p, mode, vec, skipna != 0,
-                                       wfield != nullptr, threads, s);
+  return 0;
 }
 
+// The one body behind wb2_stream_partials[_ex] (in[] + slab NUMBERS) and
+// wb2_stream_partials_addr (slab ADDRESSES, in == nullptr).
+int stream_partials_impl(const wb2_plan_tables& t, int mode, int dtype,
+                         int skipna, const void* const* in,
+                         const int64_t* const* slab, int addr_aligned16,
+                         int64_t n_outer, double* partials, void* stream) {
+  WB2_REQUIRE(mode == WB2_MODE_DET || mode == WB2_MODE_DET_ACC ||
+                  mode == WB2_MODE_WIND || mode == WB2_MODE_GAUSS ||
+                  mode == WB2_MODE_GAUSS_THR || mode == WB2_MODE_SEEPS,
+              "unknown mode %d", mode);
+  WB2_REQUIRE(mode != WB2_MODE_SEEPS || t.aux != nullptr,
+              "WB2_MODE_SEEPS needs the p1 field in `aux`");
+  WB2_REQUIRE(dtype == WB2_F32 || dtype == WB2_F64, "unknown dtype %d", dtype);
+  WB2_REQUIRE(!t.wfield || t.wfield_dtype == WB2_F64 ||
+                  (t.wfield_dtype == WB2_F32 && field_f32_supported(dtype, mode)),
+              "a float32 weight field goes with float32 inputs of the modes "
+              "DET / DET_ACC / WIND (wfield_dtype=%d dtype=%d mode=%d)",
+              t.wfield_dtype, dtype, mode);
+  WB2_EMPTY_OK(n_outer);
+  WB2_REQUIRE((in || slab) && partials, "null pointer argument");
+  const bool wf = t.wfield != nullptr;
+  const int vec = vec_width(mode, dtype, skipna != 0, wf, t.n_col);
+  if (int rc = check_partials_plan(t, n_outer, kWave * vec)) return rc;
+  StreamParams p{};
+  if (int rc = stream_params(t, mode, dtype, in, slab, n_outer, partials, p))
+    return rc;
+  bool aligned = in ? true : addr_aligned16 != 0;
+  for (int i = 0; in && i < mode_nin(mode); ++i)
+    aligned = aligned && reinterpret_cast<uintptr_t>(in[i]) % 16 == 0;
+  if (wf) aligned = aligned && reinterpret_cast<uintptr_t>(t.wfield) % 16 == 0;
+  const long long elem = dtype == WB2_F32 ? 4 : 8;
+  p.unaligned = !aligned || ((long long)t.n_col * elem) % 16 != 0;
+  p.aux = t.aux;
+  p.scalar = t.scalar;
+  const int threads = threads_for(t.n_col, vec);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dtype == WB2_F32)
+    return launch_stream_mode<float, WB2_F32_VEC>(p, mode, vec, skipna != 0, wf,
+                                                  threads, s);
+  return launch_stream_mode<double, 2>(p, mode, vec, skipna != 0, wf, threads,
+                                       s);
+}
 
 // K1p launch: the pairs of a launch (stream_pair_kernel).  `p` is filled as for
-// the per-variable kernel over the same tables (stream_partials_impl).
+// the per-variable kernel over the same tables (stream_params).
 template <typename T, int VEC, bool ACC>
 int launch_pairs_flags(const StreamParams& p, const PairParams& pp, bool skipna,
                        bool wf, hipStream_t stream) {
@@ -1948,77 +1927,36 @@ bool pairs_supported(int mode, int dtype, bool skipna, bool wf, int n_col) {
          vec_width(WB2_MODE_WIND, dtype, skipna, wf, n_col) == w;
 }
 
-int stream_pairs_impl(int mode, int dtype, int skipna, const void* const* in,
-                      const int64_t* const* slab, int addr_aligned16,
-                      int64_t n_outer, int64_t n_pair, int32_t n_row,
-                      int32_t n_col, const double* w_row, const double* w_col,
-                      const void* wfield, int wfield_dtype,
-                      const int32_t* chunk_row0, const int32_t* chunk_nrow,
-                      int32_t n_chunk, int32_t n_ctile, const int32_t* seg_col0,
-                      const int32_t* seg_eoff, int32_t n_seg, int32_t n_ts,
+int stream_pairs_impl(const wb2_plan_tables& t, int mode, int dtype, int skipna,
+                      const void* const* in, const int64_t* const* slab,
+                      int addr_aligned16, int64_t n_outer, int64_t n_pair,
                       double* partials, double* wind_partials, void* stream) {
   WB2_REQUIRE(n_pair >= 0 && 2 * n_pair <= n_outer,
               "n_pair=%lld does not fit n_outer=%lld", (long long)n_pair,
               (long long)n_outer);
   const int64_t n_single = n_outer - 2 * n_pair;
-  // the slabs outside the pairs: the per-variable kernel, as ever
-  int rc = stream_partials_impl(mode, dtype, skipna, in, slab, addr_aligned16,
-                                n_single, n_row, n_col, w_row, w_col, wfield,
-                                wfield_dtype, nullptr, 0.0, chunk_row0,
-                                chunk_nrow, n_chunk, n_ctile, seg_col0, seg_eoff,
-                                n_seg, n_ts, partials, stream);
+  // the slabs outside the pairs: the per-variable kernel, as ever -- without
+  // the mode-specific operands, which a launch with pairs does not have
+  wb2_plan_tables singles = t;
+  singles.aux = nullptr;
+  singles.scalar = 0.0;
+  int rc = stream_partials_impl(singles, mode, dtype, skipna, in, slab,
+                                addr_aligned16, n_single, partials, stream);
   if (rc != 0 || n_pair == 0) return rc;
   WB2_REQUIRE(mode == WB2_MODE_DET || mode == WB2_MODE_DET_ACC,
               "wind-vector pairs ride on WB2_MODE_DET / WB2_MODE_DET_ACC "
               "(mode=%d)", mode);
-  WB2_REQUIRE(dtype == WB2_F32 || dtype == WB2_F64, "unknown dtype %d", dtype);
-  WB2_REQUIRE((in || slab) && w_row && chunk_row0 && chunk_nrow && seg_col0 &&
-                  seg_eoff && partials && wind_partials,
+  WB2_REQUIRE((in || slab) && partials && wind_partials,
               "null pointer argument");
-  WB2_REQUIRE(n_row > 0 && n_col > 0 && n_chunk > 0 && n_chunk % 8 == 0 &&
-                  n_seg > 0 && n_outer < (1ll << 31),
-              "bad sizes");
-  const bool by_addr = in == nullptr;
-  const int nin = mode_nin(mode);
-  const long long elem = dtype == WB2_F32 ? 4 : 8;
-  StreamParams p{};
-  for (int i = 0; i < nin; ++i) {
-    if (by_addr) {
-      WB2_REQUIRE(slab[i] != nullptr, "address table %d is null", i);
-      p.slab[i] = reinterpret_cast<const long long*>(slab[i]);
-      continue;
-    }
-    WB2_REQUIRE(in[i] != nullptr, "input %d is null", i);
-    p.in[i] = in[i];
-    p.slab[i] = slab ? reinterpret_cast<const long long*>(slab[i]) : nullptr;
-  }
-  WB2_REQUIRE(pairs_supported(mode, dtype, skipna != 0, wfield != nullptr, n_col),
-              "no pair kernel for this launch (n_col=%d too narrow for the "
-              "wide loads): ask wb2_pairs_supported first", n_col);
   const int vec = dtype == WB2_F32 ? 4 : 2;
-  p.slab_step_bytes = by_addr ? 1 : (long long)n_row * n_col * elem;
-  p.w_row = w_row;
-  p.w_col = w_col;
-  p.wfield = wfield;
-  p.wfield_f32 = wfield && wfield_dtype == WB2_F32;
-  WB2_REQUIRE(!wfield || wfield_dtype == WB2_F64 ||
-                  (wfield_dtype == WB2_F32 && dtype == WB2_F32),
-              "a float32 weight field goes with float32 inputs");
-  p.chunk_row0 = chunk_row0;
-  p.chunk_nrow = chunk_nrow;
-  p.seg_col0 = seg_col0;
-  p.seg_eoff = seg_eoff;
-  p.n_ts = n_ts;
-  p.partials = partials;
-  p.n_outer = n_outer;
-  p.n_row = n_row;
-  p.n_col = n_col;
-  p.n_chunk = n_chunk;
-  p.n_ctile = (n_col + kWave * vec - 1) / (kWave * vec);
-  WB2_REQUIRE(p.n_ctile == n_ctile,
-              "n_ctile=%d does not match the launch geometry (%d)", n_ctile,
-              p.n_ctile);
-  p.n_seg = n_seg;
+  if ((rc = check_partials_plan(t, n_outer, kWave * vec)) != 0) return rc;
+  const bool wf = t.wfield != nullptr;
+  WB2_REQUIRE(pairs_supported(mode, dtype, skipna != 0, wf, t.n_col),
+              "no pair kernel for this launch (n_col=%d too narrow for the "
+              "wide loads): ask wb2_pairs_supported first", t.n_col);
+  StreamParams p{};
+  rc = stream_params(t, mode, dtype, in, slab, n_outer, partials, p);
+  if (rc != 0) return rc;
   PairParams pp{};
   pp.wind_partials = wind_partials;
   pp.first = n_single;
@@ -2026,16 +1964,10 @@ int stream_pairs_impl(int mode, int dtype, int skipna, const void* const* in,
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool acc = mode == WB2_MODE_DET_ACC;
   if (dtype == WB2_F32)
-    rc = acc ? launch_pairs_flags<float, 4, true>(p, pp, skipna != 0,
-                                                  wfield != nullptr, s)
-             : launch_pairs_flags<float, 4, false>(p, pp, skipna != 0,
-                                                   wfield != nullptr, s);
-  else
-    rc = acc ? launch_pairs_flags<double, 2, true>(p, pp, skipna != 0,
-                                                   wfield != nullptr, s)
-             : launch_pairs_flags<double, 2, false>(p, pp, skipna != 0,
-                                                    wfield != nullptr, s);
-  return rc;
+    return acc ? launch_pairs_flags<float, 4, true>(p, pp, skipna != 0, wf, s)
+               : launch_pairs_flags<float, 4, false>(p, pp, skipna != 0, wf, s);
+  return acc ? launch_pairs_flags<double, 2, true>(p, pp, skipna != 0, wf, s)
+             : launch_pairs_flags<double, 2, false>(p, pp, skipna != 0, wf, s);
 }
 
 }  // namespace
@@ -2099,11 +2031,11 @@ int wb2_stream_partials_ex(int mode, int dtype, int skipna,
   WB2_TRACE();
   using namespace wb2;
   WB2_REQUIRE(in != nullptr, "null pointer argument");
-  return stream_partials_impl(mode, dtype, skipna, in, slab, 0, n_outer, n_row,
-                              n_col, w_row, w_col, wfield, wfield_dtype, aux,
-                              scalar,
-                              chunk_row0, chunk_nrow, n_chunk, n_ctile,
-                              seg_col0, seg_eoff, n_seg, n_ts, partials, stream);
+  WB2_PLAN_OF_ARGS(t, wfield_dtype);
+  t.aux = aux;
+  t.scalar = scalar;
+  return stream_partials_impl(t, mode, dtype, skipna, in, slab, 0, n_outer,
+                              partials, stream);
 }
 
 int wb2_stream_partials_addr(int mode, int dtype, int skipna,
@@ -2120,12 +2052,11 @@ int wb2_stream_partials_addr(int mode, int dtype, int skipna,
   WB2_TRACE();
   using namespace wb2;
   WB2_REQUIRE(slab_addr != nullptr, "null pointer argument");
-  return stream_partials_impl(mode, dtype, skipna, nullptr, slab_addr,
-                              aligned16, n_outer, n_row, n_col, w_row, w_col,
-                              wfield, wfield_dtype, aux, scalar, chunk_row0,
-                              chunk_nrow,
-                              n_chunk, n_ctile, seg_col0, seg_eoff, n_seg, n_ts,
-                              partials, stream);
+  WB2_PLAN_OF_ARGS(t, wfield_dtype);
+  t.aux = aux;
+  t.scalar = scalar;
+  return stream_partials_impl(t, mode, dtype, skipna, nullptr, slab_addr,
+                              aligned16, n_outer, partials, stream);
 }
 
 int wb2_pairs_supported(int mode, int dtype, int skipna, int has_wfield,
@@ -2151,11 +2082,9 @@ int wb2_stream_partials_pairs(int mode, int dtype, int skipna,
   using namespace wb2;
   WB2_EMPTY_OK(n_outer);
   WB2_REQUIRE(in != nullptr || slab != nullptr, "null pointer argument");
-  return stream_pairs_impl(mode, dtype, skipna, in, slab, aligned16, n_outer,
-                           n_pair, n_row, n_col, w_row, w_col, wfield,
-                           wfield_dtype, chunk_row0, chunk_nrow, n_chunk,
-                           n_ctile, seg_col0, seg_eoff, n_seg, n_ts, partials,
-                           wind_partials, stream);
+  WB2_PLAN_OF_ARGS(t, wfield_dtype);
+  return stream_pairs_impl(t, mode, dtype, skipna, in, slab, aligned16, n_outer,
+                           n_pair, partials, wind_partials, stream);
 }
 
 int wb2_det_combine(int mode, int skipna, const double* partials,
@@ -2168,58 +2097,59 @@ int wb2_det_combine(int mode, int skipna, const double* partials,
                     double* metrics, void* stream) {
   WB2_TRACE();
   using namespace wb2;
-  WB2_REQUIRE(mode >= 0 && mode <= WB2_MODE_SEEPS, "unknown mode %d", mode);
-  const int k = mode == WB2_MODE_ENS ? wb2_ens_num_slots(skipna)
-                                     : wb2_num_slots(mode, skipna);
-  return combine_slots(mode, skipna, k, partials, n_outer, n_chunk, nwf, n_seg,
-                       seg_eoff, n_ts, band_chunk0, n_band, coef_band, coef_seg,
-                       region_wf, region_wsum, n_region, sums, metrics, stream);
+  wb2_plan_tables t{};
+  t.n_chunk = n_chunk;
+  t.n_seg = n_seg;
+  t.n_ts = n_ts;
+  t.n_band = n_band;
+  t.n_region = n_region;
+  t.seg_eoff = seg_eoff;
+  t.band_chunk0 = band_chunk0;
+  t.coef_band = coef_band;
+  t.coef_seg = coef_seg;
+  t.region_wf = region_wf;
+  t.region_wsum = region_wsum;
+  return combine_mode(t, mode, skipna, nwf, partials, n_outer, sums, metrics,
+                      stream);
 }
 
 }  // extern "C"
 
 namespace wb2 {
-// The body of wb2_det_combine with the slot count given (the energy-score pass
-// folds 2 x block member sums per virtual slab: a generic mode whose slot
-// count is not a function of the mode alone).
 namespace {
-CombineParams combine_params(int mode, int skipna, int k_slots,
-                             const double* partials, int64_t n_outer,
-                             int32_t n_chunk, int32_t nwf, int32_t n_seg,
-                             const int32_t* seg_eoff, int32_t n_ts,
-                             const int32_t* band_chunk0, int32_t n_band,
-                             const double* coef_band, const double* coef_seg,
-                             const int32_t* region_wf,
-                             const double* region_wsum, int32_t n_region,
-                             double* sums, double* metrics, size_t* lds) {
+// The CombineParams of one fold and the dynamic LDS it takes.
+CombineParams combine_params(const wb2_plan_tables& t, int mode, int skipna,
+                             int k_slots, int nwf, const double* partials,
+                             int64_t n_outer, double* sums, double* metrics,
+                             size_t* lds) {
   CombineParams p{};
   p.partials = partials;
-  p.seg_eoff = seg_eoff;
-  p.band_chunk0 = band_chunk0;
-  p.coef_band = coef_band;
-  p.coef_seg = coef_seg;
-  p.region_wf = region_wf;
-  p.region_wsum = region_wsum;
+  p.seg_eoff = t.seg_eoff;
+  p.band_chunk0 = t.band_chunk0;
+  p.coef_band = t.coef_band;
+  p.coef_seg = t.coef_seg;
+  p.region_wf = t.region_wf;
+  p.region_wsum = t.region_wsum;
   p.sums = sums;
   p.metrics = metrics;
   p.n_outer = n_outer;
-  p.n_chunk = n_chunk;
+  p.n_chunk = t.n_chunk;
   p.nwf = nwf;
-  p.n_seg = n_seg;
-  p.n_ts = n_ts;
-  p.n_band = n_band;
-  p.n_region = n_region;
+  p.n_seg = t.n_seg;
+  p.n_ts = t.n_ts;
+  p.n_band = t.n_band;
+  p.n_region = t.n_region;
   p.K = k_slots;
   p.mode = mode;
   p.skipna = skipna != 0;
   // lanes per cell: as many as keep the 1024 threads busy at a nominal K of 8
   p.group = 1;
   while (p.group < kWave &&
-         (long long)n_band * nwf * n_seg * 8 * (2 * p.group) <= 1024)
+         (long long)t.n_band * nwf * t.n_seg * 8 * (2 * p.group) <= 1024)
     p.group *= 2;
-  *lds = ((size_t)n_band * nwf * n_seg * p.K +
-          (size_t)n_region * p.K * (1 + (size_t)n_band) +
-          (size_t)n_region * ((size_t)n_seg + n_band)) *
+  *lds = ((size_t)t.n_band * nwf * t.n_seg * p.K +
+          (size_t)t.n_region * p.K * (1 + (size_t)t.n_band) +
+          (size_t)t.n_region * ((size_t)t.n_seg + t.n_band)) *
          sizeof(double);
   return p;
 }
@@ -2233,36 +2163,24 @@ int combine_det_and_wind(const wb2_plan_tables& t, int mode, int skipna,
                          const double* partials, int64_t n_outer,
                          const double* wind_partials, int64_t n_pair,
                          double* metrics, double* wind_metrics, void* stream) {
-  const int nwf = t.wfield ? 2 : 1;
+  const int nwf = plan_nwf(t);
   size_t lds_a = 0, lds_b = 0;
-  const CombineParams a = combine_params(
-      mode, skipna, wb2_num_slots(mode, skipna), partials, n_outer, t.n_chunk,
-      nwf, t.n_seg, t.seg_eoff, t.n_ts, t.band_chunk0, t.n_band, t.coef_band,
-      t.coef_seg, t.region_wf, t.region_wsum, t.n_region, nullptr, metrics,
-      &lds_a);
+  const CombineParams a =
+      combine_params(t, mode, skipna, wb2_num_slots(mode, skipna), nwf,
+                     partials, n_outer, nullptr, metrics, &lds_a);
   const CombineParams b = combine_params(
-      WB2_MODE_WIND, skipna, wb2_num_slots(WB2_MODE_WIND, skipna),
-      wind_partials, n_pair, t.n_chunk, nwf, t.n_seg, t.seg_eoff, t.n_ts,
-      t.band_chunk0, t.n_band, t.coef_band, t.coef_seg, t.region_wf,
-      t.region_wsum, t.n_region, nullptr, wind_metrics, &lds_b);
+      t, WB2_MODE_WIND, skipna, wb2_num_slots(WB2_MODE_WIND, skipna), nwf,
+      wind_partials, n_pair, nullptr, wind_metrics, &lds_b);
   const size_t lds = lds_a > lds_b ? lds_a : lds_b;
   if (lds > 64 * 1024 || n_outer <= 0 || n_pair <= 0 ||
       n_outer + n_pair >= (1ll << 31) || !partials || !wind_partials ||
-      !metrics || !wind_metrics || !t.seg_eoff || !t.band_chunk0 ||
-      !t.coef_band || !t.coef_seg || !t.region_wf || !t.region_wsum ||
-      t.n_chunk <= 0 || t.n_seg <= 0 || t.n_ts < t.n_seg || t.n_band <= 0 ||
-      t.n_region <= 0) {  // (the two calls below report what is wrong)
-    int rc = wb2_det_combine(mode, skipna, partials, n_outer, t.n_chunk, nwf,
-                             t.n_seg, t.seg_eoff, t.n_ts, t.band_chunk0,
-                             t.n_band, t.coef_band, t.coef_seg, t.region_wf,
-                             t.region_wsum, t.n_region, nullptr, metrics,
-                             stream);
+      !metrics || !wind_metrics || check_fold_plan(t, nwf) != 0) {
+    // (the two calls below report what is wrong)
+    int rc = combine_mode(t, mode, skipna, nwf, partials, n_outer, nullptr,
+                          metrics, stream);
     if (rc != 0 || n_pair == 0) return rc;
-    return wb2_det_combine(WB2_MODE_WIND, skipna, wind_partials, n_pair,
-                           t.n_chunk, nwf, t.n_seg, t.seg_eoff, t.n_ts,
-                           t.band_chunk0, t.n_band, t.coef_band, t.coef_seg,
-                           t.region_wf, t.region_wsum, t.n_region, nullptr,
-                           wind_metrics, stream);
+    return combine_mode(t, WB2_MODE_WIND, skipna, nwf, wind_partials, n_pair,
+                        nullptr, wind_metrics, stream);
   }
   hipLaunchKernelGGL(det_combine2_kernel, dim3((unsigned)(n_outer + n_pair)),
                      dim3(1024), lds, static_cast<hipStream_t>(stream), a, b);
@@ -2270,34 +2188,31 @@ int combine_det_and_wind(const wb2_plan_tables& t, int mode, int skipna,
   return 0;
 }
 
-int combine_slots(int mode, int skipna, int k_slots, const double* partials,
-                  int64_t n_outer, int32_t n_chunk, int32_t nwf, int32_t n_seg,
-                  const int32_t* seg_eoff, int32_t n_ts,
-                  const int32_t* band_chunk0, int32_t n_band,
-                  const double* coef_band, const double* coef_seg,
-                  const int32_t* region_wf, const double* region_wsum,
-                  int32_t n_region, double* sums, double* metrics,
-                  void* stream) {
+int combine_mode(const wb2_plan_tables& t, int mode, int skipna, int nwf,
+                 const double* partials, int64_t n_outer, double* sums,
+                 double* metrics, void* stream) {
+  WB2_REQUIRE(mode >= 0 && mode <= WB2_MODE_SEEPS, "unknown mode %d", mode);
+  const int k = mode == WB2_MODE_ENS ? wb2_ens_num_slots(skipna)
+                                     : wb2_num_slots(mode, skipna);
+  return combine_slots(t, mode, skipna, k, nwf, partials, n_outer, sums,
+                       metrics, stream);
+}
+
+int combine_slots(const wb2_plan_tables& t, int mode, int skipna, int k_slots,
+                  int nwf, const double* partials, int64_t n_outer,
+                  double* sums, double* metrics, void* stream) {
   WB2_EMPTY_OK(n_outer);
-  WB2_REQUIRE(partials && seg_eoff && band_chunk0 && coef_band && coef_seg &&
-                  region_wf && region_wsum,
-              "null pointer argument");
-  WB2_REQUIRE(n_outer >= 0 && n_chunk > 0 && n_ts >= n_seg &&
-                  (nwf == 1 || nwf == 2) && n_seg > 0 && n_band > 0 &&
-                  n_region > 0,
-              "bad sizes");
-  if (n_outer == 0) return 0;
+  WB2_REQUIRE(partials != nullptr, "null pointer argument");
+  if (int rc = check_fold_plan(t, nwf)) return rc;
   size_t lds = 0;
-  const CombineParams p = combine_params(
-      mode, skipna, k_slots, partials, n_outer, n_chunk, nwf, n_seg, seg_eoff,
-      n_ts, band_chunk0, n_band, coef_band, coef_seg, region_wf, region_wsum,
-      n_region, sums, metrics, &lds);
+  const CombineParams p = combine_params(t, mode, skipna, k_slots, nwf, partials,
+                                         n_outer, sums, metrics, &lds);
   // gfx950: a workgroup may take all 160 KiB of a CU's LDS; beyond the default
   // 64 KiB of dynamic LDS the kernel has to be told once
   WB2_REQUIRE(lds <= 160 * 1024,
               "region decomposition too fine for the combine kernel's LDS "
               "(%zu bytes > 160 KiB): n_band=%d n_seg=%d slots=%d",
-              lds, n_band, n_seg, p.K);
+              lds, t.n_band, t.n_seg, p.K);
   if (lds > 64 * 1024) {
     static std::atomic<size_t> allowed{64 * 1024};
     if (lds > allowed.load()) {
@@ -2325,10 +2240,20 @@ int wb2_ens_combine(int skipna, const double* partials, int64_t n_outer,
                     int32_t n_region, double* sums, double* metrics,
                     void* stream) {
   WB2_TRACE();
-  return wb2_det_combine(WB2_MODE_ENS, skipna, partials, n_outer, n_chunk, nwf,
-                         n_seg, seg_eoff, n_ts, band_chunk0, n_band, coef_band,
-                         coef_seg, region_wf, region_wsum, n_region, sums,
-                         metrics, stream);
+  wb2_plan_tables t{};
+  t.n_chunk = n_chunk;
+  t.n_seg = n_seg;
+  t.n_ts = n_ts;
+  t.n_band = n_band;
+  t.n_region = n_region;
+  t.seg_eoff = seg_eoff;
+  t.band_chunk0 = band_chunk0;
+  t.coef_band = coef_band;
+  t.coef_seg = coef_seg;
+  t.region_wf = region_wf;
+  t.region_wsum = region_wsum;
+  return wb2::combine_mode(t, WB2_MODE_ENS, skipna, nwf, partials, n_outer, sums,
+                           metrics, stream);
 }
 
 int wb2_time_accumulate(const double* values, int64_t n_lead, int64_t n_time,
@@ -2411,17 +2336,11 @@ int wb2_det_suite_step(const wb2_plan_tables* plan, int mode, int dtype,
                 (long long)acc_lead, (long long)acc_time, (long long)acc_tail,
                 nm, t.n_region, (long long)n_outer);
   }
-  int rc = stream_partials_impl(
-      mode, dtype, skipna, in, slab, aligned16, n_outer, t.n_row, t.n_col,
-      t.w_row, t.w_col, t.wfield, t.wfield_dtype, t.aux, t.scalar, t.chunk_row0,
-      t.chunk_nrow, t.n_chunk, t.n_ctile, t.seg_col0, t.seg_eoff, t.n_seg,
-      t.n_ts, partials, stream);
+  int rc = stream_partials_impl(t, mode, dtype, skipna, in, slab, aligned16,
+                                n_outer, partials, stream);
   if (rc != 0) return rc;
-  rc = wb2_det_combine(mode, skipna, partials, n_outer, t.n_chunk,
-                       t.wfield ? 2 : 1, t.n_seg, t.seg_eoff, t.n_ts,
-                       t.band_chunk0, t.n_band, t.coef_band, t.coef_seg,
-                       t.region_wf, t.region_wsum, t.n_region, nullptr, metrics,
-                       stream);
+  rc = combine_mode(t, mode, skipna, plan_nwf(t), partials, n_outer, nullptr,
+                    metrics, stream);
   if (rc != 0 || sum == nullptr) return rc;
   return wb2_time_accumulate_scatter(WB2_F64, metrics, acc_lead, acc_time,
                                      acc_tail, acc_skipna, dst, sum, count,
@@ -2442,12 +2361,8 @@ int wb2_det_wind_suite_step(const wb2_plan_tables* plan, int mode, int dtype,
   WB2_REQUIRE(metrics != nullptr && (n_pair == 0 || wind_metrics != nullptr),
               "metrics is null");
   const wb2_plan_tables& t = *plan;
-  int rc = stream_pairs_impl(mode, dtype, skipna, in, slab, aligned16, n_outer,
-                             n_pair, t.n_row, t.n_col, t.w_row, t.w_col,
-                             t.wfield, t.wfield_dtype, t.chunk_row0,
-                             t.chunk_nrow, t.n_chunk, t.n_ctile, t.seg_col0,
-                             t.seg_eoff, t.n_seg, t.n_ts, partials,
-                             wind_partials, stream);
+  int rc = stream_pairs_impl(t, mode, dtype, skipna, in, slab, aligned16,
+                             n_outer, n_pair, partials, wind_partials, stream);
   if (rc != 0) return rc;
   return combine_det_and_wind(t, mode, skipna, partials, n_outer, wind_partials,
                               n_pair, metrics, wind_metrics, stream);

@@ -283,6 +283,23 @@ def stream_reduce(plan: ReductionPlan, mode: int,
                         scalar, aligned, inputs=inputs, slabs=slabs)
 
 
+def _check_address_tables(plan, addr, n_outer):
+  for a in addr:
+    if (a.dtype != torch.int64 or a.device != plan.device or
+        a.numel() != n_outer or not a.is_contiguous()):
+      raise ValueError('address tables are contiguous int64[n_outer] on the '
+                       'plan device')
+
+
+def _fold_args(plan, seg_eoff, n_ts):
+  """The plan's arguments of wb2_det_combine / wb2_ens_combine, between
+  `n_outer` and `sums`."""
+  return (plan.n_chunk, plan.nwf, plan.n_seg, _lib.ptr(seg_eoff), n_ts,
+          _lib.ptr(plan.band_chunk0), plan.n_band, _lib.ptr(plan.coef_band),
+          _lib.ptr(plan.coef_seg), _lib.ptr(plan.region_wf),
+          _lib.ptr(plan.region_wsum), plan.n_region)
+
+
 def stream_reduce_addr(plan: ReductionPlan, mode: int, dtype: torch.dtype,
                        addr: t.Sequence[torch.Tensor], aligned16: bool,
                        n_outer: int, skipna: bool, want_sums: bool = False,
@@ -296,11 +313,7 @@ def stream_reduce_addr(plan: ReductionPlan, mode: int, dtype: torch.dtype,
   (torch's allocator is stream-ordered).  Same return value as stream_reduce."""
   if dtype not in _DTYPES:
     raise TypeError(f'unsupported dtype {dtype}')
-  for a in addr:
-    if (a.dtype != torch.int64 or a.device != plan.device or
-        a.numel() != n_outer or not a.is_contiguous()):
-      raise ValueError('address tables are contiguous int64[n_outer] on the '
-                       'plan device')
+  _check_address_tables(plan, addr, n_outer)
   return _stream_launch(plan, mode, dtype, n_outer, skipna, want_sums, aux,
                         scalar, bool(aligned16), addr=addr)
 
@@ -311,14 +324,7 @@ def _stream_launch(plan, mode, dtype, n_outer, skipna, want_sums, aux, scalar,
   dev = plan.device
   code = _DTYPES[dtype]
   k = lib.wb2_num_slots(mode, int(skipna))
-  # the 2-D weight field as float32 where its values are float32 numbers and
-  # the launch has the instantiation (float32 inputs, DET / DET_ACC / WIND):
-  # the same bits, half the field bytes per point
-  field, field_code = plan.wfield, _lib.WB2_F64
-  if (dtype == torch.float32 and mode in _FIELD_F32_MODES and
-      getattr(plan, 'wfield32', None) is not None and
-      os.environ.get('WB2HIP_FIELD_F32', '1') != '0'):
-    field, field_code = plan.wfield32, _lib.WB2_F32
+  field, field_code = _suite_field(plan, dtype, mode)
   aligned = aligned and (field is None or field.data_ptr() % 16 == 0)
   tile = lib.wb2_tile_cols_ex(mode, code, int(skipna),
                               int(plan.wfield is not None), plan.n_col,
@@ -352,12 +358,9 @@ def _stream_launch(plan, mode, dtype, n_outer, skipna, want_sums, aux, scalar,
   sums = (torch.empty((n_outer, plan.n_region, k), dtype=torch.float64,
                       device=dev) if want_sums else None)
   _lib.check(lib.wb2_det_combine(
-      mode, int(skipna), _lib.ptr(partials), n_outer, plan.n_chunk, plan.nwf,
-      plan.n_seg, _lib.ptr(seg_eoff), n_ts, _lib.ptr(plan.band_chunk0),
-      plan.n_band,
-      _lib.ptr(plan.coef_band), _lib.ptr(plan.coef_seg),
-      _lib.ptr(plan.region_wf), _lib.ptr(plan.region_wsum), plan.n_region,
-      _lib.ptr(sums), _lib.ptr(metrics), stream), 'wb2_det_combine')
+      mode, int(skipna), _lib.ptr(partials), n_outer,
+      *_fold_args(plan, seg_eoff, n_ts), _lib.ptr(sums), _lib.ptr(metrics),
+      stream), 'wb2_det_combine')
   return metrics, sums
 
 
@@ -395,11 +398,7 @@ def stream_reduce_pairs(plan: ReductionPlan, mode: int, dtype: torch.dtype,
   (metrics[NMETRIC, n_region, n_outer], wind[NMETRIC, n_region, n_pair]) --
   the bits of stream_reduce_addr over the slabs plus a MODE_WIND pass over the
   pairs, from one read (wb2_det_wind_suite_step)."""
-  for a in addr:
-    if (a.dtype != torch.int64 or a.device != plan.device or
-        a.numel() != n_outer or not a.is_contiguous()):
-      raise ValueError('address tables are contiguous int64[n_outer] on the '
-                       'plan device')
+  _check_address_tables(plan, addr, n_outer)
   step = PairSuiteStep(plan, mode, dtype, skipna, n_outer, n_pair,
                        aligned=bool(aligned16))
   return step.run(None, list(addr))
@@ -642,6 +641,15 @@ def gather_pointers(base: torch.Tensor, index: np.ndarray, slab_elems: int):
   return ptrs
 
 
+def _ens_plan_args(plan, seg_eoff, n_ts, n_ctile):
+  """The plan's arguments of the ensemble partials entry points, between
+  `n_outer` and `partials`."""
+  return (plan.n_row, plan.n_col, _lib.ptr(plan.w_row), _lib.ptr(plan.w_col),
+          _lib.ptr(plan.wfield), _lib.ptr(plan.chunk_row0),
+          _lib.ptr(plan.chunk_nrow), plan.n_chunk, n_ctile,
+          _lib.ptr(plan.seg_col0), _lib.ptr(seg_eoff), plan.n_seg, n_ts)
+
+
 def ensemble_reduce(plan: ReductionPlan, ens: torch.Tensor,
                     member_stride: int, n_member: int,
                     ens_slab: t.Optional[torch.Tensor], truth: torch.Tensor,
@@ -701,32 +709,23 @@ def ensemble_reduce(plan: ReductionPlan, ens: torch.Tensor,
   if maps is not None and (maps.dtype != torch.float64 or maps.numel() !=
                            6 * n_outer * plan.n_row * plan.n_col):
     raise ValueError('maps must be float64[6, n_outer, n_row * n_col]')
+  tail = (n_outer, *_ens_plan_args(plan, seg_eoff, n_ts, n_ctile),
+          _lib.ptr(partials))
   if addresses is not None:
     base = addresses.data_ptr()
     _lib.check(lib.wb2_ens_partials_addr(
         _DTYPES[dtype], int(skipna), base, base + 8 * n_outer, n_member,
-        member_stride, n_outer, plan.n_row, plan.n_col, _lib.ptr(plan.w_row),
-        _lib.ptr(plan.w_col), _lib.ptr(plan.wfield), _lib.ptr(plan.chunk_row0),
-        _lib.ptr(plan.chunk_nrow), plan.n_chunk, n_ctile,
-        _lib.ptr(plan.seg_col0), _lib.ptr(seg_eoff), plan.n_seg, n_ts,
-        _lib.ptr(partials), stream), 'wb2_ens_partials_addr')
+        member_stride, *tail, stream), 'wb2_ens_partials_addr')
   elif member_ptrs is not None:
     _lib.check(lib.wb2_ens_partials_gather(
         _DTYPES[dtype], int(skipna), _lib.ptr(member_ptrs), _lib.ptr(truth),
-        _lib.ptr(truth_slab), n_member, n_outer, plan.n_row, plan.n_col,
-        _lib.ptr(plan.w_row), _lib.ptr(plan.w_col), _lib.ptr(plan.wfield),
-        _lib.ptr(plan.chunk_row0), _lib.ptr(plan.chunk_nrow), plan.n_chunk,
-        n_ctile, _lib.ptr(plan.seg_col0), _lib.ptr(seg_eoff), plan.n_seg, n_ts,
-        _lib.ptr(partials), _lib.ptr(maps), stream), 'wb2_ens_partials_gather')
+        _lib.ptr(truth_slab), n_member, *tail, _lib.ptr(maps), stream),
+               'wb2_ens_partials_gather')
   else:
     _lib.check(lib.wb2_ens_partials_maps(
         _DTYPES[dtype], int(skipna), _lib.ptr(ens), _lib.ptr(ens_slab),
-        _lib.ptr(truth), _lib.ptr(truth_slab), n_member, member_stride,
-        n_outer, plan.n_row, plan.n_col, _lib.ptr(plan.w_row),
-        _lib.ptr(plan.w_col), _lib.ptr(plan.wfield), _lib.ptr(plan.chunk_row0),
-        _lib.ptr(plan.chunk_nrow), plan.n_chunk, n_ctile,
-        _lib.ptr(plan.seg_col0), _lib.ptr(seg_eoff), plan.n_seg, n_ts,
-        _lib.ptr(partials), _lib.ptr(maps), stream), 'wb2_ens_partials_maps')
+        _lib.ptr(truth), _lib.ptr(truth_slab), n_member, member_stride, *tail,
+        _lib.ptr(maps), stream), 'wb2_ens_partials_maps')
   if _LAUNCH_HOOK is not None:
     _LAUNCH_HOOK('end', 'ens_partials')
   metrics = torch.empty((_lib.NMETRIC_ENS, plan.n_region, n_outer),
@@ -734,11 +733,9 @@ def ensemble_reduce(plan: ReductionPlan, ens: torch.Tensor,
   sums = (torch.empty((n_outer, plan.n_region, k), dtype=torch.float64,
                       device=dev) if want_sums else None)
   _lib.check(lib.wb2_ens_combine(
-      int(skipna), _lib.ptr(partials), n_outer, plan.n_chunk, plan.nwf,
-      plan.n_seg, _lib.ptr(seg_eoff), n_ts, _lib.ptr(plan.band_chunk0),
-      plan.n_band, _lib.ptr(plan.coef_band), _lib.ptr(plan.coef_seg),
-      _lib.ptr(plan.region_wf), _lib.ptr(plan.region_wsum), plan.n_region,
-      _lib.ptr(sums), _lib.ptr(metrics), stream), 'wb2_ens_combine')
+      int(skipna), _lib.ptr(partials), n_outer,
+      *_fold_args(plan, seg_eoff, n_ts), _lib.ptr(sums), _lib.ptr(metrics),
+      stream), 'wb2_ens_combine')
   return metrics, sums
 
 
@@ -1440,21 +1437,17 @@ def ensemble_threshold_reduce(plan: ReductionPlan, ens: torch.Tensor,
   _lib.check(lib.wb2_ens_threshold_partials(
       _DTYPES[dtype], int(skipna), _lib.ptr(ens), _lib.ptr(ens_slab),
       _lib.ptr(truth), _lib.ptr(truth_slab), _lib.ptr(thr), _lib.ptr(thr_slab),
-      n_member, member_stride, n_outer, plan.n_row, plan.n_col,
-      _lib.ptr(plan.w_row), _lib.ptr(plan.w_col), _lib.ptr(plan.wfield),
-      _lib.ptr(plan.chunk_row0), _lib.ptr(plan.chunk_nrow), plan.n_chunk,
-      n_ctile, _lib.ptr(plan.seg_col0), _lib.ptr(seg_eoff), plan.n_seg, n_ts,
-      _lib.ptr(partials), stream), 'wb2_ens_threshold_partials')
+      n_member, member_stride, n_outer,
+      *_ens_plan_args(plan, seg_eoff, n_ts, n_ctile), _lib.ptr(partials),
+      stream), 'wb2_ens_threshold_partials')
   metrics = torch.empty((_lib.GENERIC_KQ[mode], plan.n_region, n_outer),
                         dtype=torch.float64, device=dev)
   sums = (torch.empty((n_outer, plan.n_region, k), dtype=torch.float64,
                       device=dev) if want_sums else None)
   _lib.check(lib.wb2_det_combine(
-      mode, int(skipna), _lib.ptr(partials), n_outer, plan.n_chunk, plan.nwf,
-      plan.n_seg, _lib.ptr(seg_eoff), n_ts, _lib.ptr(plan.band_chunk0),
-      plan.n_band, _lib.ptr(plan.coef_band), _lib.ptr(plan.coef_seg),
-      _lib.ptr(plan.region_wf), _lib.ptr(plan.region_wsum), plan.n_region,
-      _lib.ptr(sums), _lib.ptr(metrics), stream), 'wb2_det_combine')
+      mode, int(skipna), _lib.ptr(partials), n_outer,
+      *_fold_args(plan, seg_eoff, n_ts), _lib.ptr(sums), _lib.ptr(metrics),
+      stream), 'wb2_det_combine')
   return (metrics, sums) if want_sums else metrics
 
 

@@ -1302,6 +1302,89 @@ int wb2_time_bin_stats(int stat_mask, int dtype, int skipna, const void* in,
 int wb2_time_window_geometry(int dtype, int wide, int32_t* tile_points,
                              int32_t* steps_ahead, int32_t* max_grid_outer);
 
+/*
+ * K14: day-of-year climatology from one read (scripts/compute_climatology.py,
+ * weatherbench2/utils.py:73-287).  The reference stacks the years, pads the
+ * day-of-year axis cyclically, builds a W-wide window and takes a weighted mean
+ * or std over (window, year).  The weights do not depend on the year and the
+ * padding wraps inside each year's row, so the statistic is a cyclic weighted
+ * combination of per-day-of-year moments; nothing is read W times.
+ *
+ * Semantics:
+ *   explicit  per hour and point, A the sorted union of the days of year
+ *             present (n of them; 365 must be among them), X[y, a] the sample
+ *             of year y or NaN; a NaN X[y, a] is replaced by X[y, doy 365]
+ *             (fillna: day 366 of a common year, gap days and data NaNs
+ *             alike).  Over the entries that are not NaN, positions mod n,
+ *             H = W / 2, k = -H .. H:
+ *               mean[a] = S_y S_k w[k+H] X[y, a+k] / S_y S_k w[k+H]
+ *               std[a]  = sqrt(S w (X - mean[a])^2 / S w)
+ *             NaN where no entry is left.
+ *   fast      m[a], s[a] the NaN-skipping mean and ddof=0 std of the group of
+ *             day a (no fill, no year alignment); the result at a is the
+ *             NaN-skipping plain mean over i = -H .. H of
+ *             v[(a - i) mod n] * w[i+H].
+ *   weights   create_window_weights(W): odd W, linspace up and down, divided
+ *             by its mean (the caller passes them).
+ *
+ * The data is T[n_outer][n_time][n_point] with K13's slab table (NULL = the
+ * identity), T = float32 or float64; 16-byte loads where `in`, the outputs and
+ * n_point allow, scalar loads otherwise.
+ *
+ * wb2_group_moments: group g holds member[group_begin[g] .. group_begin[g+1])
+ * (DEV int32; `group_begin_host` is the caller's HOST copy of the n_group + 1
+ * offsets, on which 0 = begin[0] <= ... <= begin[n_group] = n_member is checked
+ * before anything is enqueued; the kernel cuts a device list that disagrees to
+ * the members and never follows it out of them).  member[j] is a time step; a
+ * value outside [0, n_time) is an absent sample (NaN, nothing is read).
+ * fill[j] (DEV int32, or NULL) is the time step of the substitute, outside
+ * [0, n_time) for none.  pivot (DEV float64 [n_outer][n_point], or NULL = 0).
+ * Per group, for each member in order: read x; if it is NaN and has a fill,
+ * read the fill step instead; if it is still NaN, skip it; otherwise y =
+ * double(x) - pivot, count += 1, sum += y, sumsq += y * y (float64, no FMA
+ * contraction, starting from +0.0).  count, sum, sumsq: DEV float64
+ * [n_outer][n_group][n_point]; an empty group gives 0, 0, 0.  A thread owns 4
+ * float32 or 2 float64 adjacent points and requests members_ahead members
+ * before it combines any; a workgroup handles one point tile of one group; the
+ * grid is tiles x groups x outer.  No atomics, no LDS.
+ * wb2_first_finite: pivot[o][i] = the first sample of the point, in member
+ * order, that is neither NaN nor +-inf, 0.0 if there is none.
+ * wb2_cycle_smooth: groups are g = c * n_pos + a: n_cycle independent cycles
+ * of n_pos positions.  WB2_SMOOTH_EXPLICIT: W0, W1, W2 = S_k w[k+H] * (count,
+ * sum, sumsq)[(a + k) mod n_pos] in the order k = -H .. H; m = W1 / W0; mean =
+ * pivot + m; v = W2 / W0 - m * m; std = sqrt(v < 0 ? 0 : v) (a NaN v stays
+ * NaN); W0 == 0 gives NaN.  WB2_SMOOTH_FAST: per position pivot + S / C and
+ * sqrt(max-as-above(Q / C - (S / C)^2)), NaN where C == 0; then, for each of
+ * the two, the sum in the order i = -H .. H of the products value[(a - i) mod
+ * n_pos] * w[i+H] that are not NaN, divided by their number (NaN if none).
+ * weights: DEV float64[n_w], n_w odd and positive; H >= n_pos is legal.  Either
+ * of mean, std (DEV float64 [n_outer][n_cycle * n_pos][n_point]) may be NULL.
+ * wb2_climatology_geometry: points per workgroup tile of wb2_group_moments
+ * (wide != 0: 16-byte loads), the members requested ahead and the outer
+ * indices per grid row (more are split over a further grid dimension).
+ * Zero sizes of n_outer, n_point, n_group, n_cycle or n_pos are a no-op.
+ */
+#define WB2_SMOOTH_EXPLICIT 0
+#define WB2_SMOOTH_FAST 1
+int wb2_group_moments(int dtype, const void* in, const int64_t* slab,
+                      int64_t n_outer, int32_t n_time, int64_t n_point,
+                      const int32_t* group_begin,
+                      const int32_t* group_begin_host, int32_t n_group,
+                      const int32_t* member, const int32_t* fill,
+                      int32_t n_member, const double* pivot, double* count,
+                      double* sum, double* sumsq, void* stream);
+int wb2_first_finite(int dtype, const void* in, const int64_t* slab,
+                     int64_t n_outer, int32_t n_time, int64_t n_point,
+                     const int32_t* member, int32_t n_member, double* pivot,
+                     void* stream);
+int wb2_cycle_smooth(int mode, const double* count, const double* sum,
+                     const double* sumsq, const double* pivot, int64_t n_outer,
+                     int32_t n_cycle, int32_t n_pos, int64_t n_point,
+                     const double* weights, int32_t n_w, double* mean,
+                     double* std, void* stream);
+int wb2_climatology_geometry(int dtype, int wide, int32_t* tile_points,
+                             int32_t* members_ahead, int32_t* max_grid_outer);
+
 #ifdef __cplusplus
 }
 #endif

@@ -214,6 +214,15 @@ _SIGNATURES = {
                                   _vp]),
     'wb2_time_window_geometry': (_int, [_int, _int, _c.POINTER(_i32),
                                         _c.POINTER(_i32), _c.POINTER(_i32)]),
+    'wb2_group_moments': (_int, [_int, _vp, _vp, _i64, _i32, _i64, _vp,
+                                 _c.POINTER(_i32), _i32, _vp, _vp, _i32, _vp,
+                                 _vp, _vp, _vp, _vp]),
+    'wb2_first_finite': (_int, [_int, _vp, _vp, _i64, _i32, _i64, _vp, _i32,
+                                _vp, _vp]),
+    'wb2_cycle_smooth': (_int, [_int, _vp, _vp, _vp, _vp, _i64, _i32, _i32,
+                                _i64, _vp, _i32, _vp, _vp, _vp]),
+    'wb2_climatology_geometry': (_int, [_int, _int, _c.POINTER(_i32),
+                                        _c.POINTER(_i32), _c.POINTER(_i32)]),
 }
 
 _lib = None

@@ -1410,6 +1410,144 @@ def time_bin_stats(x: torch.Tensor, slab: t.Optional[torch.Tensor],
   return outs
 
 
+SMOOTH_MODES = ('explicit', 'fast')  # WB2_SMOOTH_*, in order
+
+
+def climatology_geometry(dtype: torch.dtype, wide: bool = False) -> dict:
+  """Extents of the K14 moments kernel: `tile_points` adjacent points per
+  workgroup, `members_ahead` members a thread requests before it combines
+  any, `max_grid_outer` outer indices per grid row."""
+  import ctypes
+  tile, ahead, outer = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+  _lib.check(_lib.load().wb2_climatology_geometry(
+      _DTYPES[dtype], int(wide), ctypes.byref(tile), ctypes.byref(ahead),
+      ctypes.byref(outer)), 'wb2_climatology_geometry')
+  return {'tile_points': tile.value, 'members_ahead': ahead.value,
+          'max_grid_outer': outer.value}
+
+
+def _check_series(x, slab, n_outer, n_time, lists):
+  if x.dtype not in _DTYPES:
+    raise TypeError('the input must be float32 or float64')
+  if slab is not None and (slab.dtype != torch.int64
+                           or slab.numel() != n_outer * n_time):
+    raise ValueError('the slab table must hold n_outer * n_time int64')
+  for name, a in lists.items():
+    if a is not None and (a.dtype != torch.int32 or a.dim() != 1
+                          or not a.is_contiguous() or a.device != x.device):
+      raise ValueError(f'{name} must be a contiguous 1-D int32 tensor on the '
+                       'device of the input')
+
+
+def group_moments(x: torch.Tensor, slab: t.Optional[torch.Tensor],
+                  n_outer: int, n_time: int, n_point: int, group_begin,
+                  member: torch.Tensor, fill: t.Optional[torch.Tensor] = None,
+                  pivot: t.Optional[torch.Tensor] = None) -> tuple:
+  """K14 moments: float64 (count, sum, sumsq), each [n_outer, n_group,
+  n_point], of the groups of time steps of the series x[o, :, i], about
+  `pivot` (float64 [n_outer, n_point], None = 0), from ONE launch and one
+  read of `x`.  `group_begin` is a HOST sequence of n_group + 1 offsets into
+  `member` (int32 device tensor of time steps, in time order; a step outside
+  [0, n_time) is an absent sample); `fill` (int32 device tensor like `member`,
+  or None) names the step read in the place of a NaN, negative for none.
+  `slab` as for `time_bin_stats`."""
+  import numpy as np
+  lib = _lib.load()
+  _check_series(x, slab, n_outer, n_time, {'member': member, 'fill': fill})
+  begin = np.ascontiguousarray(group_begin, dtype=np.int32)
+  if begin.ndim != 1 or begin.size < 1:
+    raise ValueError('group_begin must hold n_group + 1 offsets')
+  n_group, n_member = begin.size - 1, int(member.numel())
+  if fill is not None and fill.numel() != n_member:
+    raise ValueError('fill must have one entry per member')
+  if pivot is not None and (pivot.dtype != torch.float64
+                            or pivot.numel() != n_outer * n_point
+                            or not pivot.is_contiguous()
+                            or pivot.device != x.device):
+    raise ValueError('pivot must be a contiguous float64 [n_outer, n_point] '
+                     'on the device of the input')
+  begin_dev = torch.from_numpy(begin).to(x.device)
+  outs = tuple(torch.empty((n_outer, n_group, n_point), dtype=torch.float64,
+                           device=x.device) for _ in range(3))
+  import ctypes
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('begin', 'group_moments')
+  _lib.check(lib.wb2_group_moments(
+      _DTYPES[x.dtype], _lib.ptr(x), _lib.ptr(slab), n_outer, n_time, n_point,
+      _lib.ptr(begin_dev), begin.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+      n_group, _lib.ptr(member), _lib.ptr(fill), n_member, _lib.ptr(pivot),
+      _lib.ptr(outs[0]), _lib.ptr(outs[1]), _lib.ptr(outs[2]),
+      current_stream_ptr(x.device)), 'wb2_group_moments')
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('end', 'group_moments')
+  return outs
+
+
+def first_finite(x: torch.Tensor, slab: t.Optional[torch.Tensor],
+                 n_outer: int, n_time: int, n_point: int,
+                 member: torch.Tensor) -> torch.Tensor:
+  """K14 pivot plane: float64 [n_outer, n_point], the first sample of every
+  point, in the order of `member`, that is neither NaN nor +-inf; 0.0 if there
+  is none."""
+  lib = _lib.load()
+  _check_series(x, slab, n_outer, n_time, {'member': member})
+  pivot = torch.empty((n_outer, n_point), dtype=torch.float64, device=x.device)
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('begin', 'first_finite')
+  _lib.check(lib.wb2_first_finite(
+      _DTYPES[x.dtype], _lib.ptr(x), _lib.ptr(slab), n_outer, n_time, n_point,
+      _lib.ptr(member), int(member.numel()), _lib.ptr(pivot),
+      current_stream_ptr(x.device)), 'wb2_first_finite')
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('end', 'first_finite')
+  return pivot
+
+
+def cycle_smooth(mode: str, moments, pivot: t.Optional[torch.Tensor],
+                 n_cycle: int, n_pos: int, weights: torch.Tensor,
+                 want: t.Sequence[str] = ('mean', 'std')) -> dict:
+  """K14 smoothing: {'mean' / 'std': float64 [n_outer, n_cycle * n_pos,
+  n_point]} from the moments (count, sum, sumsq) of `group_moments`, whose
+  groups are n_cycle cycles of n_pos positions, with the float64 device
+  `weights` of an odd window; `mode` is 'explicit' or 'fast' (see
+  include/wb2hip.h)."""
+  lib = _lib.load()
+  if mode not in SMOOTH_MODES:
+    raise ValueError(f'mode must be one of {SMOOTH_MODES}: {mode!r}')
+  names = list(dict.fromkeys(want))
+  if not names or any(s not in ('mean', 'std') for s in names):
+    raise ValueError(f"want must be some of ('mean', 'std'): {want}")
+  count, total, sumsq = moments
+  n_outer, n_group, n_point = count.shape
+  for a in (count, total, sumsq):
+    if (a.dtype != torch.float64 or not a.is_contiguous()
+        or a.shape != count.shape):
+      raise ValueError('the moments must be contiguous float64 planes of one '
+                       'shape')
+  if n_group != n_cycle * n_pos:
+    raise ValueError(f'{n_group} groups are not {n_cycle} cycles of {n_pos}')
+  if (weights.dtype != torch.float64 or weights.dim() != 1
+      or not weights.is_contiguous() or weights.device != count.device):
+    raise ValueError('weights must be a contiguous float64 vector on the '
+                     'device of the moments')
+  if pivot is not None and (pivot.dtype != torch.float64
+                            or pivot.numel() != n_outer * n_point
+                            or not pivot.is_contiguous()):
+    raise ValueError('pivot must be a contiguous float64 [n_outer, n_point]')
+  outs = {s: torch.empty_like(count) for s in names}
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('begin', 'cycle_smooth')
+  _lib.check(lib.wb2_cycle_smooth(
+      SMOOTH_MODES.index(mode), _lib.ptr(count), _lib.ptr(total),
+      _lib.ptr(sumsq), _lib.ptr(pivot), n_outer, n_cycle, n_pos, n_point,
+      _lib.ptr(weights), int(weights.numel()), _lib.ptr(outs.get('mean')),
+      _lib.ptr(outs.get('std')), current_stream_ptr(count.device)),
+             'wb2_cycle_smooth')
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('end', 'cycle_smooth')
+  return outs
+
+
 def ensemble_threshold_reduce(plan: ReductionPlan, ens: torch.Tensor,
                               member_stride: int, n_member: int, ens_slab,
                               truth: torch.Tensor, truth_slab,

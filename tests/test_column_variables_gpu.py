@@ -315,6 +315,36 @@ def test_level_counts_around_the_in_flight_depth(dtype):
         _check_against_numpy(label, variables, coords, dtype)
 
 
+# One column more than the 32768 outer indices of a grid row
+# (csrc/launch_common.hpp; the column geometry call does not report it): the
+# last column lies in the second grid plane.  Every column holds its own random
+# data, so a plane that reads or writes the columns of plane 0 is caught.
+SPLIT_COLUMNS = 32769
+
+
+@pytest.mark.parametrize('dtype,n_lon', [(np.float32, 3), (np.float32, 4),
+                                         (np.float64, 3)])
+def test_columns_beyond_one_grid_row(dtype, n_lon):
+  """Two levels; 3 points (narrow, with a tail) and 4 float32 points (one
+  16-byte lane) for the integral, transport and gradient-ratio modes; 2 x n_lon
+  slabs, the smallest np.gradient accepts, for the eddy mode with its zonal
+  means and the in-place cumulative mode behind the stencil (65538 slabs).
+  Columns 0, 32767, 32768 and the last are also compared with the same columns
+  computed on their own."""
+  at = [0, 32767, 32768, SPLIT_COLUMNS - 1]
+  for labels, dims, sizes in (
+      (FLAT, ('time', 'level', 'cell'),
+       dict(time=SPLIT_COLUMNS, level=2, cell=n_lon)),
+      (GRID, ('time', 'level', 'latitude', 'longitude'),
+       dict(time=SPLIT_COLUMNS, level=2, latitude=2, longitude=n_lon))):
+    variables, coords = _fields(dims, sizes, dtype, n_lon), _coords(sizes)
+    few = {k: (d, a[at]) for k, (d, a) in variables.items()}
+    for label in labels:
+      res = _check_against_numpy(label, variables, coords, dtype)
+      alone = _make(label).compute(_dataset(few, coords)).values
+      assert np.array_equal(res.values[at], alone, equal_nan=True), label
+
+
 def test_one_level():
   """The integrals and the vertical velocity give zeros (even where the field
   is NaN), LapseRate raises like np.gradient."""

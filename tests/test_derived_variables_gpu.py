@@ -382,6 +382,79 @@ def test_relative_humidity_reads_the_pressure_coordinate_by_name():
 
 
 # ---------------------------------------------------------------------------
+# more slabs than one grid row holds
+# ---------------------------------------------------------------------------
+# One slab more than the 32768 outer indices of a grid row
+# (csrc/launch_common.hpp; these kernels' geometry calls do not report it):
+# the last slab lies in the second grid plane.  3 points: narrow, with a tail;
+# 4 float32 points: one 16-byte lane.  Every slab holds its own random data, so
+# a plane that reads or writes the slabs of plane 0 is caught.
+SPLIT_SLABS = 32769
+SPLIT_CASES = [(np.float32, 3), (np.float32, 4), (np.float64, 3)]
+SPLIT_CHECKED = (0, 32767, 32768, SPLIT_SLABS - 1)
+
+
+@pytest.mark.parametrize('dtype,n_point', SPLIT_CASES)
+def test_pointwise_slabs_beyond_one_grid_row(dtype, n_point):
+  """WindSpeed straight through the launch (the class folds contiguous slabs
+  into one), bit for bit; RelativeHumidity, whose pressure is one value per
+  slab, through the class with the tolerance of its neighbours."""
+  import torch
+  from weatherbench2_amd import engine
+  dims = ('level', 'cell')
+  u, v = _wind((SPLIT_SLABS, n_point), dtype, seed=n_point)
+  _, want = derived_np.compute('WindSpeed', {'u_name': 'u', 'v_name': 'v'},
+                               {'u': (dims, u), 'v': (dims, v)}, {})
+  got = engine.derived_pointwise(
+      'wind_speed', torch.from_numpy(u).cuda(), None,
+      torch.from_numpy(v).cuda(), None, SPLIT_SLABS, n_point).cpu().numpy()
+  assert got.dtype == want.dtype and got.shape == want.shape
+  for o in SPLIT_CHECKED:
+    assert np.array_equal(got[o], want[o], equal_nan=True), o
+  assert np.array_equal(got, want, equal_nan=True)
+  rs = np.random.RandomState(n_point)
+  shape = (SPLIT_SLABS, 1, n_point)
+  dims = ('level', 'latitude', 'longitude')
+  variables = {
+      'temperature': (dims, (250 + 40 * rs.random_sample(shape)).astype(dtype)),
+      'specific_humidity': (dims, (1e-3 + 9e-3 * rs.random_sample(shape)
+                                   ).astype(dtype))}
+  coords = {'level': np.linspace(300.0, 1000.0, SPLIT_SLABS)}
+  name, fields = dc.fields_of('relative_humidity')
+  as64 = {k: (d, a.astype(np.float64)) for k, (d, a) in variables.items()}
+  _, np64 = derived_np.compute(name, fields, as64, coords)
+  _, np_in = derived_np.compute(name, fields, variables, coords)
+  res = _make('relative_humidity').compute(_dataset(variables, coords))
+  got = res.values
+  assert res.dims == dims and got.dtype == np_in.dtype
+  for o in SPLIT_CHECKED + (slice(None),):
+    err = np.abs(got[o].astype(np.float64) - np64[o]).max()
+    if dtype == np.float32:
+      noise = np.abs(np_in[o].astype(np.float64) - np64[o]).max()
+      assert err <= 4 * noise, (o, err / noise)
+    else:
+      assert err <= 1e-9 * np.sqrt(np.mean(np64[o] ** 2)), o
+
+
+@pytest.mark.parametrize('dtype,n_lon', SPLIT_CASES)
+def test_stencil_slabs_beyond_one_grid_row(dtype, n_lon):
+  """Slabs of 2 x n_lon, the smallest np.gradient accepts, on both layouts."""
+  for dims in (('level', 'latitude', 'longitude'),
+               ('level', 'longitude', 'latitude')):
+    sizes = dict(level=SPLIT_SLABS, latitude=2, longitude=n_lon)
+    variables, coords = _stencil_case(dims, sizes, dtype, n_lon,
+                                      np.array([-30.0, 40.0]))
+    for label in ('divergence', 'ageostrophic_wind_speed'):
+      _check_against_numpy(label, variables, coords, dtype)
+      at = (0, 32767, 32768, SPLIT_SLABS - 1)
+      few = {k: (d, a[list(at)]) for k, (d, a) in variables.items()}
+      got = _make(label).compute(_dataset(variables, coords)).values[list(at)]
+      want = _make(label).compute(_dataset(
+          few, dict(coords, level=coords['level'][list(at)]))).values
+      assert np.array_equal(got, want, equal_nan=True), (label, dims)
+
+
+# ---------------------------------------------------------------------------
 # 9. evaluate_chunks keeps windows and programs
 # ---------------------------------------------------------------------------
 def _derived():

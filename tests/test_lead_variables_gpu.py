@@ -193,6 +193,30 @@ def test_point_counts_around_the_vector_and_the_tile(dtype):
                    (n_point, n_lead, mode, w))
 
 
+@pytest.mark.parametrize('dtype,n_point', [(np.float32, 3), (np.float32, 4),
+                                           (np.float64, 3)])
+def test_outer_indices_beyond_one_grid_row(dtype, n_point):
+  """One outer index more than the 32768 of a grid row
+  (csrc/launch_common.hpp; the lead geometry call does not report it): the last
+  one lies in the second grid plane.  Two leads of 3 points (narrow, with a
+  tail) or 4 float32 points (one 16-byte lane) through two ring windows, three
+  leads through a window that re-reads; every outer index holds its own random
+  series, so a plane that reads or writes the series of plane 0 is caught."""
+  import torch
+  n_outer = 32769
+  for n_lead, launches in ((2, (('diff_sum', 1), ('sum', 2))),
+                           (3, (('sum', 3), ('diff_sum', 2)))):
+    host = _series((n_outer, n_lead, n_point), dtype, n_point + n_lead)
+    x = torch.from_numpy(host).cuda()
+    for mode, w in launches:
+      got = _launch(mode, x, w, True)
+      want = _expect(mode, host, w, True)
+      assert np.isfinite(want[:, -1]).all()
+      for o in (0, 32767, 32768, n_outer - 1):
+        _bit_equal(got[o], want[o], (mode, w, o))
+      _bit_equal(got, want, (mode, w))
+
+
 @pytest.mark.parametrize('dtype', [np.float32, np.float64])
 def test_a_base_misaligned_by_slicing(dtype):
   """A field that starts one element into its buffer is 4- or 8-byte aligned

@@ -142,6 +142,27 @@ def test_c_abi_over_series_lengths_tiles_and_outer_counts(dtype, skipna):
                             f'n_outer={n_outer}')
 
 
+@pytest.mark.parametrize('dtype,n_inner', [(np.float32, 3), (np.float32, 4),
+                                           (np.float64, 3)])
+def test_c_abi_outer_indices_beyond_one_grid_row(dtype, n_inner):
+  """One outer index more than the 32768 of a grid row
+  (csrc/launch_common.hpp; the quantile geometry call does not report it): the
+  last one lies in the second grid plane.  Series of two samples of 3 points
+  (narrow, with a tail) or 4 float32 points (one 16-byte lane); every outer
+  index holds its own random data, so a plane that reads or writes the series
+  of plane 0 is caught.  (The resident kernel: a streaming series over this
+  many outer indices would be a gigabyte.)"""
+  import torch
+  n_outer = 32769
+  host = _series((n_outer, 2, n_inner), dtype, n_inner)
+  for skipna in (False, True):
+    got = _select(torch.from_numpy(host).cuda(), Q, skipna)
+    want = qn.quantile(host, Q, 1, skipna)
+    for o in (0, 32767, 32768, n_outer - 1):
+      qn.assert_bit_equal(got[:, o], want[:, o], f'outer index {o}')
+    qn.assert_bit_equal(got, want, 'every outer index')
+
+
 @pytest.mark.parametrize('skipna', [False, True])
 @pytest.mark.parametrize('dtype', [np.float32, np.float64])
 def test_c_abi_long_streaming_series(dtype, skipna):

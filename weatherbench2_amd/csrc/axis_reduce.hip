@@ -19,6 +19,7 @@
 //               (coalesced), then a fixed-order wave + LDS tree.
 
 #include "common.hpp"
+#include "launch_common.hpp"
 #include "trace.hpp"
 #include "wb2hip.h"
 
@@ -74,7 +75,7 @@ __global__ void __launch_bounds__(256) axis_strided_kernel(const AxisParams p) {
   const int sp = (int)(blockIdx.x / n_tblk);
   const long long t =
       ((long long)(blockIdx.x - sp * n_tblk) * blockDim.x + threadIdx.x) * VEC;
-  const long long l = blockIdx.y + (long long)blockIdx.z * gridDim.y;
+  const long long l = outer_index();
   if (t >= p.n_tail || l >= p.n_lead) return;
   const long long r0 = (long long)sp * p.slice;
   const long long r1 = r0 + p.slice < p.n_red ? r0 + p.slice : p.n_red;
@@ -133,7 +134,7 @@ __global__ void __launch_bounds__(256) axis_strided_kernel(const AxisParams p) {
 template <typename T, int VEC, bool SKIPNA, bool SQ>
 __global__ void __launch_bounds__(256) axis_contig_kernel(const AxisParams p) {
   __shared__ double lds[3][4];
-  const long long l = blockIdx.y + (long long)blockIdx.z * gridDim.y;
+  const long long l = outer_index();
   const int sp = blockIdx.x;
   if (l >= p.n_lead) return;  // workgroup-uniform
   const long long r0 = (long long)sp * p.slice;
@@ -225,27 +226,20 @@ __global__ void __launch_bounds__(256)
 }  // namespace
 }  // namespace wb2
 
-// (dtype, vector width, skipna, want_sq) -> template instance of WB2_K
-#define WB2_AXIS_L(T, V, S, Q) \
-  hipLaunchKernelGGL((WB2_K<T, V, S, Q>), grid, dim3(256), 0, s, p)
-#define WB2_AXIS_FLAGS(T, V)                              \
-  do {                                                    \
-    if (skipna) {                                         \
-      if (sumsq) WB2_AXIS_L(T, V, true, true);            \
-      else WB2_AXIS_L(T, V, true, false);                 \
-    } else {                                              \
-      if (sumsq) WB2_AXIS_L(T, V, false, true);           \
-      else WB2_AXIS_L(T, V, false, false);                \
-    }                                                     \
+// (skipna, want_sq) -> the instance of the kernel template K for the field
+// (T, V) of the enclosing for_field lambda
+#define WB2_AXIS_L(K, S, Q) \
+  hipLaunchKernelGGL((K<T, V, S, Q>), grid, dim3(256), 0, s, p)
+#define WB2_AXIS_FLAGS(K)                      \
+  do {                                         \
+    if (skipna) {                              \
+      if (sumsq) WB2_AXIS_L(K, true, true);    \
+      else WB2_AXIS_L(K, true, false);         \
+    } else {                                   \
+      if (sumsq) WB2_AXIS_L(K, false, true);   \
+      else WB2_AXIS_L(K, false, false);        \
+    }                                          \
   } while (0)
-#define WB2_AXIS_DISPATCH                                 \
-  if (dtype == WB2_F32) {                                 \
-    if (vec) WB2_AXIS_FLAGS(float, 4);                    \
-    else WB2_AXIS_FLAGS(float, 1);                        \
-  } else {                                                \
-    if (vec) WB2_AXIS_FLAGS(double, 2);                   \
-    else WB2_AXIS_FLAGS(double, 1);                       \
-  }
 
 extern "C" {
 
@@ -285,9 +279,9 @@ int wb2_axis_moments(int dtype, const void* x, int64_t n_lead, int64_t n_red,
   WB2_REQUIRE(n_red % w_repeat == 0 || !w_red,
               "n_red=%lld is not a multiple of w_repeat=%lld",
               (long long)n_red, (long long)w_repeat);
-  const long long gy = n_lead < 32768 ? n_lead : 32768;
-  const long long gz = (n_lead + gy - 1) / gy;
-  WB2_REQUIRE(gz <= 65535, "n_lead=%lld too large", (long long)n_lead);
+  dim3 grid;  // (grid.x follows once the kernel is known)
+  WB2_REQUIRE(outer_grid(n_lead, 1, &grid), "n_lead=%lld too large",
+              (long long)n_lead);
   hipStream_t s = static_cast<hipStream_t>(stream);
   AxisParams p{};
   p.x = x;
@@ -312,26 +306,30 @@ int wb2_axis_moments(int dtype, const void* x, int64_t n_lead, int64_t n_red,
   }
   p.skipna = skipna;
   p.want_sq = sumsq != nullptr;
-  const int elt = dtype == WB2_F32 ? 4 : 8;
-  const int wide = 16 / elt;
-  const bool aligned = reinterpret_cast<uintptr_t>(x) % 16 == 0;
+  const int wide = wide_lanes(dtype);
+  const bool aligned = aligned16(x);
   if (n_tail > 1) {
     const bool vec = aligned && n_tail % wide == 0;
-    const long long per_blk = 256ll * (vec ? wide : 1);
-    const long long gx = ((n_tail + per_blk - 1) / per_blk) * n_split;
+    const long long gx = point_tiles(n_tail, vec ? wide : 1, 256) * n_split;
     WB2_REQUIRE(gx < (1ll << 31), "n_tail=%lld too large", (long long)n_tail);
-    const dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)gz);
-#define WB2_K axis_strided_kernel
-    WB2_AXIS_DISPATCH
-#undef WB2_K
+    grid.x = (unsigned)gx;
+    for_field(dtype, vec, [&](auto t, auto v) {
+      using T = decltype(t);
+      constexpr int V = decltype(v)::value;
+      WB2_AXIS_FLAGS(axis_strided_kernel);
+    });
   } else {
     // every run start must be 16-byte aligned for the wide loads
     const bool vec = aligned && n_red % wide == 0 && p.w_repeat % wide == 0;
-    const dim3 grid((unsigned)n_split, (unsigned)gy, (unsigned)gz);
-#define WB2_K axis_contig_kernel
-    WB2_AXIS_DISPATCH
-#undef WB2_K
+    grid.x = (unsigned)n_split;
+    for_field(dtype, vec, [&](auto t, auto v) {
+      using T = decltype(t);
+      constexpr int V = decltype(v)::value;
+      WB2_AXIS_FLAGS(axis_contig_kernel);
+    });
   }
+#undef WB2_AXIS_FLAGS
+#undef WB2_AXIS_L
   WB2_HIP_OK(hipGetLastError());
   if (n_split == 1) return 0;
   hipLaunchKernelGGL(axis_combine_kernel, dim3((unsigned)((n_out + 255) / 256)),

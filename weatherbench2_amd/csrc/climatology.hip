@@ -42,6 +42,7 @@
 
 #include "common.hpp"
 #include "derived_common.hpp"
+#include "launch_common.hpp"
 #include "trace.hpp"
 #include "wb2hip.h"
 
@@ -50,7 +51,6 @@ namespace {
 
 constexpr int kMomThreads = 256;
 constexpr int kAhead = 4;  // members loaded before any is combined
-constexpr long long kMomGridOuter = 32768;  // outer indices per grid row
 
 struct MomentParams {
   const void* in;
@@ -71,7 +71,7 @@ __global__ void __launch_bounds__(kMomThreads)
   const int g = (int)(blockIdx.x / p.n_tile);
   const long long q = (tile * kMomThreads + threadIdx.x) * VEC;
   if (q >= p.n_point) return;
-  const long long o = blockIdx.y + (long long)blockIdx.z * gridDim.y;
+  const long long o = outer_index();
   if (o >= p.n_outer) return;
   constexpr int U = kAhead;
   const long long row = o * p.n_time;
@@ -86,7 +86,7 @@ __global__ void __launch_bounds__(kMomThreads)
     piv[e] = p.pivot ? p.pivot[o * p.n_point + q + e] : 0.0;
     cnt[e] = sum[e] = sq[e] = 0.0;
   }
-  const T nan = (T)__builtin_nanf("");
+  const T nan = quiet_nan<T>();
   for (int j0 = begin; j0 < end; j0 += U) {
     T cur[U][VEC];
     int fl[U];
@@ -151,7 +151,7 @@ __global__ void __launch_bounds__(kMomThreads)
     first_finite_kernel(const PivotParams p) {
   const long long q = ((long long)blockIdx.x * kMomThreads + threadIdx.x) * VEC;
   if (q >= p.n_point) return;
-  const long long o = blockIdx.y + (long long)blockIdx.z * gridDim.y;
+  const long long o = outer_index();
   if (o >= p.n_outer) return;
   const long long row = o * p.n_time;
   const T* in = static_cast<const T*>(p.in) + q;
@@ -205,7 +205,7 @@ __global__ void __launch_bounds__(kMomThreads)
   const int g = (int)(blockIdx.x / p.n_tile);
   const long long q = tile * kMomThreads + threadIdx.x;
   if (q >= p.n_point) return;
-  const long long o = blockIdx.y + (long long)blockIdx.z * gridDim.y;
+  const long long o = outer_index();
   if (o >= p.n_outer) return;
   const int n_group = p.n_cycle * p.n_pos;
   const int c = g / p.n_pos, a = g % p.n_pos;
@@ -259,15 +259,6 @@ __global__ void __launch_bounds__(kMomThreads)
   if (p.std) p.std[out] = std;
 }
 
-// grid rows of outer indices; false if the problem does not fit a grid
-inline bool outer_grid(long long n_outer, long long blocks_x, dim3* grid) {
-  const long long gy = n_outer < kMomGridOuter ? n_outer : kMomGridOuter;
-  const long long gz = (n_outer + gy - 1) / gy;
-  if (blocks_x >= (1ll << 31) || gz > 65535) return false;
-  *grid = dim3((unsigned)blocks_x, (unsigned)gy, (unsigned)gz);
-  return true;
-}
-
 }  // namespace
 }  // namespace wb2
 
@@ -279,9 +270,9 @@ int wb2_climatology_geometry(int dtype, int wide, int32_t* tile_points,
   WB2_REQUIRE(dtype == WB2_F32 || dtype == WB2_F64, "unknown dtype %d", dtype);
   WB2_REQUIRE(tile_points && members_ahead && max_grid_outer,
               "null pointer argument");
-  *tile_points = kMomThreads * (wide ? (dtype == WB2_F32 ? 4 : 2) : 1);
+  *tile_points = kMomThreads * (wide ? wide_lanes(dtype) : 1);
   *members_ahead = kAhead;
-  *max_grid_outer = (int32_t)kMomGridOuter;
+  *max_grid_outer = (int32_t)kGridOuter;
   return 0;
 }
 
@@ -313,9 +304,9 @@ int wb2_group_moments(int dtype, const void* in, const int64_t* slab,
     WB2_REQUIRE(group_begin_host[g] <= group_begin_host[g + 1],
                 "group_begin does not fit the members: it decreases at group "
                 "%d", g);
-  const int w = dtype == WB2_F32 ? 4 : 2;
-  const bool wide = n_point % w == 0 && aligned16(in) && aligned16(count) &&
-                    aligned16(sum) && aligned16(sumsq) &&
+  const int w = wide_lanes(dtype);
+  const bool wide = n_point % w == 0 &&
+                    all_aligned16(in, count, sum, sumsq) &&
                     reinterpret_cast<uintptr_t>(pivot) % 8 == 0;
   const int vec = wide ? w : 1;
   MomentParams p{};
@@ -330,7 +321,7 @@ int wb2_group_moments(int dtype, const void* in, const int64_t* slab,
   p.out[2] = sumsq;
   p.n_outer = n_outer;
   p.n_point = n_point;
-  p.n_tile = ((n_point + vec - 1) / vec + kMomThreads - 1) / kMomThreads;
+  p.n_tile = point_tiles(n_point, vec, kMomThreads);
   p.n_time = n_time;
   p.n_group = n_group;
   p.n_member = n_member;
@@ -339,15 +330,12 @@ int wb2_group_moments(int dtype, const void* in, const int64_t* slab,
                                                     &grid),
               "bad sizes");
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define WB2_M(T, V)                                                    \
-  hipLaunchKernelGGL((group_moments_kernel<T, V>), grid, dim3(kMomThreads), \
-                     0, s, p)
-  if (dtype == WB2_F32) {
-    if (wide) WB2_M(float, 4); else WB2_M(float, 1);
-  } else {
-    if (wide) WB2_M(double, 2); else WB2_M(double, 1);
-  }
-#undef WB2_M
+  for_field(dtype, wide, [&](auto t, auto v) {
+    using T = decltype(t);
+    constexpr int V = decltype(v)::value;
+    hipLaunchKernelGGL((group_moments_kernel<T, V>), grid, dim3(kMomThreads),
+                       0, s, p);
+  });
   WB2_HIP_OK(hipGetLastError());
   return 0;
 }
@@ -367,8 +355,8 @@ int wb2_first_finite(int dtype, const void* in, const int64_t* slab,
   WB2_REQUIRE(pivot, "null pointer argument");
   WB2_REQUIRE((in || n_time == 0) && (member || n_member == 0),
               "null pointer argument");
-  const int w = dtype == WB2_F32 ? 4 : 2;
-  const bool wide = n_point % w == 0 && aligned16(in) && aligned16(pivot);
+  const int w = wide_lanes(dtype);
+  const bool wide = n_point % w == 0 && all_aligned16(in, pivot);
   const int vec = wide ? w : 1;
   PivotParams p{};
   p.in = in;
@@ -377,21 +365,18 @@ int wb2_first_finite(int dtype, const void* in, const int64_t* slab,
   p.pivot = pivot;
   p.n_outer = n_outer;
   p.n_point = n_point;
-  p.n_tile = ((n_point + vec - 1) / vec + kMomThreads - 1) / kMomThreads;
+  p.n_tile = point_tiles(n_point, vec, kMomThreads);
   p.n_time = n_time;
   p.n_member = n_member;
   dim3 grid;
   WB2_REQUIRE(outer_grid(n_outer, p.n_tile, &grid), "bad sizes");
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define WB2_P(T, V)                                                   \
-  hipLaunchKernelGGL((first_finite_kernel<T, V>), grid, dim3(kMomThreads), \
-                     0, s, p)
-  if (dtype == WB2_F32) {
-    if (wide) WB2_P(float, 4); else WB2_P(float, 1);
-  } else {
-    if (wide) WB2_P(double, 2); else WB2_P(double, 1);
-  }
-#undef WB2_P
+  for_field(dtype, wide, [&](auto t, auto v) {
+    using T = decltype(t);
+    constexpr int V = decltype(v)::value;
+    hipLaunchKernelGGL((first_finite_kernel<T, V>), grid, dim3(kMomThreads),
+                       0, s, p);
+  });
   WB2_HIP_OK(hipGetLastError());
   return 0;
 }
@@ -424,7 +409,7 @@ int wb2_cycle_smooth(int mode, const double* count, const double* sum,
   p.std = std;
   p.n_outer = n_outer;
   p.n_point = n_point;
-  p.n_tile = (n_point + kMomThreads - 1) / kMomThreads;
+  p.n_tile = point_tiles(n_point, 1, kMomThreads);
   p.n_cycle = n_cycle;
   p.n_pos = n_pos;
   p.n_w = n_w;

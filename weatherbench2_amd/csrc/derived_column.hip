@@ -23,6 +23,7 @@
 
 #include "common.hpp"
 #include "derived_common.hpp"
+#include "launch_common.hpp"
 #include "trace.hpp"
 #include "wb2hip.h"
 
@@ -47,10 +48,6 @@ struct ColumnParams {
   double scale;
 };
 
-__device__ __forceinline__ long long column_of() {
-  return blockIdx.y + (long long)blockIdx.z * gridDim.y;
-}
-
 // INTEGRAL / TRANSPORT / EDDY: out[c][point] of dtype O
 template <typename T, typename O, int VEC, int MODE>
 __global__ void __launch_bounds__(kColumnThreads)
@@ -58,7 +55,7 @@ __global__ void __launch_bounds__(kColumnThreads)
   const long long q =
       ((long long)blockIdx.x * kColumnThreads + threadIdx.x) * VEC;
   if (q >= p.n_point) return;
-  const long long c = column_of();
+  const long long c = outer_index();
   if (c >= p.n_column) return;
   constexpr int NIN = MODE == WB2_COLUMN_INTEGRAL ? 1
                       : MODE == WB2_COLUMN_TRANSPORT ? 3 : 2;
@@ -163,7 +160,7 @@ __global__ void __launch_bounds__(kColumnThreads)
   const long long q =
       ((long long)blockIdx.x * kColumnThreads + threadIdx.x) * VEC;
   if (q >= p.n_point) return;
-  const long long c = column_of();
+  const long long c = outer_index();
   if (c >= p.n_column) return;
   constexpr int U = kColumnAhead;
   const int n_level = p.n_level;
@@ -229,7 +226,7 @@ __global__ void __launch_bounds__(kColumnThreads)
   const long long q =
       ((long long)blockIdx.x * kColumnThreads + threadIdx.x) * VEC;
   if (q >= p.n_point) return;
-  const long long c = column_of();
+  const long long c = outer_index();
   if (c >= p.n_column) return;
   constexpr int U = kColumnAhead;
   const int n_level = p.n_level;
@@ -317,7 +314,7 @@ int wb2_derived_column_geometry(int dtype, int wide, int32_t* tile_points,
   using namespace wb2;
   WB2_REQUIRE(dtype == WB2_F32 || dtype == WB2_F64, "unknown dtype %d", dtype);
   WB2_REQUIRE(tile_points && levels_ahead, "null pointer argument");
-  *tile_points = kColumnThreads * (wide ? (dtype == WB2_F32 ? 4 : 2) : 1);
+  *tile_points = kColumnThreads * (wide ? wide_lanes(dtype) : 1);
   *levels_ahead = kColumnAhead;
   return 0;
 }
@@ -369,7 +366,7 @@ int wb2_derived_column(int mode, int dtype, int out_dtype,
   WB2_REQUIRE((n_point + kColumnThreads - 1) / kColumnThreads < (1ll << 31),
               "bad sizes");
   ColumnParams p{};
-  const int w = dtype == WB2_F32 ? 4 : 2;
+  const int w = wide_lanes(dtype);
   bool wide = n_point % w == 0 && aligned16(out);
   for (int k = 0; k < n_in; ++k) {
     p.in[k] = inputs[k];
@@ -393,46 +390,43 @@ int wb2_derived_column(int mode, int dtype, int out_dtype,
   p.uniform = level_uniform;
   p.n_mean = n_mean;
   p.scale = scale;
-  const int vec = wide ? w : 1;
-  const long long gx =
-      ((n_point + vec - 1) / vec + kColumnThreads - 1) / kColumnThreads;
-  const long long gy = n_column < 32768 ? n_column : 32768;
-  const dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)((n_column + gy - 1) / gy));
+  dim3 grid;
+  WB2_REQUIRE(outer_grid(n_column,
+                         point_tiles(n_point, wide ? w : 1, kColumnThreads),
+                         &grid),
+              "bad sizes");
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define WB2_L(K) hipLaunchKernelGGL((K), grid, dim3(kColumnThreads), 0, s, p)
-#define WB2_INTEGRAL(M)                                                       \
-  do {                                                                        \
-    if (dtype == WB2_F64) {                                                   \
-      if (wide) WB2_L((column_integral_kernel<double, double, 2, M>));        \
-      else WB2_L((column_integral_kernel<double, double, 1, M>));             \
-    } else if (out_dtype == WB2_F64) {                                        \
-      if (wide) WB2_L((column_integral_kernel<float, double, 4, M>));         \
-      else WB2_L((column_integral_kernel<float, double, 1, M>));              \
-    } else {                                                                  \
-      if (wide) WB2_L((column_integral_kernel<float, float, 4, M>));          \
-      else WB2_L((column_integral_kernel<float, float, 1, M>));               \
-    }                                                                         \
-  } while (0)
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(kColumnThreads), 0, s, p);
+  };
+  // the three reducing modes: T the fields' dtype, O the promoted one
+  auto integral = [&](auto m) {
+    constexpr int M = decltype(m)::value;
+    for_field(dtype, wide, [&](auto t, auto v) {
+      using T = decltype(t);
+      constexpr int V = decltype(v)::value;
+      if constexpr (std::is_same<T, double>::value)
+        launch(column_integral_kernel<double, double, V, M>);
+      else if (out_dtype == WB2_F64)
+        launch(column_integral_kernel<float, double, V, M>);
+      else
+        launch(column_integral_kernel<float, float, V, M>);
+    });
+  };
   if (mode == WB2_COLUMN_INTEGRAL) {
-    WB2_INTEGRAL(WB2_COLUMN_INTEGRAL);
+    integral(std::integral_constant<int, WB2_COLUMN_INTEGRAL>{});
   } else if (mode == WB2_COLUMN_TRANSPORT) {
-    WB2_INTEGRAL(WB2_COLUMN_TRANSPORT);
+    integral(std::integral_constant<int, WB2_COLUMN_TRANSPORT>{});
   } else if (mode == WB2_COLUMN_EDDY) {
-    WB2_INTEGRAL(WB2_COLUMN_EDDY);
+    integral(std::integral_constant<int, WB2_COLUMN_EDDY>{});
   } else if (ratio) {
-    if (dtype == WB2_F32) {
-      if (wide) WB2_L((column_gradient_ratio_kernel<float, 4>));
-      else WB2_L((column_gradient_ratio_kernel<float, 1>));
-    } else {
-      if (wide) WB2_L((column_gradient_ratio_kernel<double, 2>));
-      else WB2_L((column_gradient_ratio_kernel<double, 1>));
-    }
+    for_field(dtype, wide, [&](auto t, auto v) {
+      launch(column_gradient_ratio_kernel<decltype(t), decltype(v)::value>);
+    });
   } else {
-    if (wide) WB2_L((column_cumulative_kernel<2>));
-    else WB2_L((column_cumulative_kernel<1>));
+    if (wide) launch(column_cumulative_kernel<2>);
+    else launch(column_cumulative_kernel<1>);
   }
-#undef WB2_INTEGRAL
-#undef WB2_L
   WB2_HIP_OK(hipGetLastError());
   return 0;
 }
@@ -453,14 +447,16 @@ int wb2_derived_zonal_mean(int dtype, int lat_rows, const void* in,
   WB2_REQUIRE(blocks < (1ll << 31), "bad sizes");
   const long long* tab = reinterpret_cast<const long long*>(slab);
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define WB2_L(T, R)                                                          \
-  hipLaunchKernelGGL((zonal_mean_kernel<T, R>), dim3((unsigned)blocks),      \
-                     dim3(256), 0, s, static_cast<const T*>(in), tab,        \
-                     (long long)n_slab, (int)n_row, (int)n_col,              \
-                     static_cast<T*>(out))
-  if (dtype == WB2_F32) { if (lat_rows) WB2_L(float, true); else WB2_L(float, false); }
-  else { if (lat_rows) WB2_L(double, true); else WB2_L(double, false); }
-#undef WB2_L
+  for_field(dtype, false, [&](auto t, auto) {
+    using T = decltype(t);
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, s,
+                         static_cast<const T*>(in), tab, (long long)n_slab,
+                         (int)n_row, (int)n_col, static_cast<T*>(out));
+    };
+    if (lat_rows) launch(zonal_mean_kernel<T, true>);
+    else launch(zonal_mean_kernel<T, false>);
+  });
   WB2_HIP_OK(hipGetLastError());
   return 0;
 }

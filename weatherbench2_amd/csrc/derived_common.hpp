@@ -70,8 +70,4 @@ __device__ __forceinline__ T gradient_at(T lo, T mid, T hi, bool diff_form,
   return (T)((a * (double)lo + b * (double)mid) + c * (double)hi);
 }
 
-inline bool aligned16(const void* p) {
-  return reinterpret_cast<uintptr_t>(p) % 16 == 0;
-}
-
 }  // namespace wb2

@@ -14,6 +14,7 @@
 
 #include "common.hpp"
 #include "derived_common.hpp"
+#include "launch_common.hpp"
 #include "trace.hpp"
 #include "wb2hip.h"
 
@@ -38,7 +39,7 @@ template <typename T, int VEC>
 __global__ void __launch_bounds__(256) wind_speed_kernel(const PointParams p) {
   const long long q = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * VEC;
   if (q >= p.n_point) return;
-  const long long o = blockIdx.y + (long long)blockIdx.z * gridDim.y;
+  const long long o = outer_index();
   if (o >= p.n_slab) return;
   const long long as = p.a_slab ? p.a_slab[o] : o;
   const long long bs = p.b_slab ? p.b_slab[o] : o;
@@ -61,7 +62,7 @@ __global__ void __launch_bounds__(256)
     relative_humidity_kernel(const PointParams p) {
   const long long q = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * VEC;
   if (q >= p.n_point) return;
-  const long long o = blockIdx.y + (long long)blockIdx.z * gridDim.y;
+  const long long o = outer_index();
   if (o >= p.n_slab) return;
   const long long as = p.a_slab ? p.a_slab[o] : o;
   const long long bs = p.b_slab ? p.b_slab[o] : o;
@@ -243,12 +244,6 @@ __global__ void __launch_bounds__(kStencilThreads)
   }
 }
 
-dim3 point_grid(long long n_point, int vec, long long n_y) {
-  const long long gx = (n_point / vec + 255) / 256;
-  const long long gy = n_y < 32768 ? n_y : 32768;
-  return dim3((unsigned)gx, (unsigned)gy, (unsigned)((n_y + gy - 1) / gy));
-}
-
 }  // namespace
 }  // namespace wb2
 
@@ -283,31 +278,28 @@ int wb2_derived_pointwise(int mode, int dtype, int out_dtype, const void* a,
   p.out = out;
   p.n_slab = n_slab;
   p.n_point = n_point;
-  const int w = dtype == WB2_F32 ? 4 : 2;
-  const bool wide = n_point % w == 0 && aligned16(a) && aligned16(b) &&
-                    aligned16(out);
-  const dim3 grid = point_grid(n_point, wide ? w : 1, n_slab);
+  const int w = wide_lanes(dtype);
+  const bool wide = n_point % w == 0 && all_aligned16(a, b, out);
+  dim3 grid;
+  WB2_REQUIRE(outer_grid(n_slab, point_tiles(n_point, wide ? w : 1, 256),
+                         &grid),
+              "bad sizes");
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define WB2_L(K) hipLaunchKernelGGL((K), grid, dim3(256), 0, s, p)
-  if (!rh) {
-    if (dtype == WB2_F32) {
-      if (wide) WB2_L((wind_speed_kernel<float, 4>));
-      else WB2_L((wind_speed_kernel<float, 1>));
-    } else {
-      if (wide) WB2_L((wind_speed_kernel<double, 2>));
-      else WB2_L((wind_speed_kernel<double, 1>));
-    }
-  } else if (dtype == WB2_F64) {
-    if (wide) WB2_L((relative_humidity_kernel<double, double, 2>));
-    else WB2_L((relative_humidity_kernel<double, double, 1>));
-  } else if (out_dtype == WB2_F64) {
-    if (wide) WB2_L((relative_humidity_kernel<float, double, 4>));
-    else WB2_L((relative_humidity_kernel<float, double, 1>));
-  } else {
-    if (wide) WB2_L((relative_humidity_kernel<float, float, 4>));
-    else WB2_L((relative_humidity_kernel<float, float, 1>));
-  }
-#undef WB2_L
+  for_field(dtype, wide, [&](auto t, auto v) {
+    using T = decltype(t);
+    constexpr int V = decltype(v)::value;
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, p);
+    };
+    if (!rh)
+      launch(wind_speed_kernel<T, V>);
+    else if constexpr (std::is_same<T, double>::value)
+      launch(relative_humidity_kernel<double, double, V>);
+    else if (out_dtype == WB2_F64)
+      launch(relative_humidity_kernel<float, double, V>);
+    else
+      launch(relative_humidity_kernel<float, float, V>);
+  });
   WB2_HIP_OK(hipGetLastError());
   return 0;
 }
@@ -317,7 +309,7 @@ int wb2_derived_stencil_geometry(int dtype, int wide, int32_t* tile_cols,
   using namespace wb2;
   WB2_REQUIRE(dtype == WB2_F32 || dtype == WB2_F64, "unknown dtype %d", dtype);
   WB2_REQUIRE(tile_cols && chunk_rows, "null pointer argument");
-  *tile_cols = kStencilThreads * (wide ? (dtype == WB2_F32 ? 4 : 2) : 1);
+  *tile_cols = kStencilThreads * (wide ? wide_lanes(dtype) : 1);
   *chunk_rows = kStencilRows;
   return 0;
 }
@@ -347,7 +339,7 @@ int wb2_derived_stencil(int mode, int dtype, int lat_rows,
               (int)n_col);
   StencilParams p{};
   const int n_in = mode >= WB2_STENCIL_AGEO_U ? 4 : 2;
-  const int w = dtype == WB2_F32 ? 4 : 2;
+  const int w = wide_lanes(dtype);
   bool wide = n_col % w == 0 && aligned16(out);
   for (int k = 0; k < n_in; ++k) {
     p.in[k] = inputs[k];
@@ -372,18 +364,16 @@ int wb2_derived_stencil(int mode, int dtype, int lat_rows,
                   (unsigned)(n_slab < 65535 ? n_slab : 65535));
   WB2_REQUIRE(grid.y <= 65535, "bad sizes: %d rows", (int)n_row);
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define WB2_L(T, V)                                                           \
-  do {                                                                        \
-    if (lat_rows)                                                             \
-      hipLaunchKernelGGL((stencil_kernel<T, V, true>), grid,                  \
-                         dim3(kStencilThreads), 0, s, p);                     \
-    else                                                                      \
-      hipLaunchKernelGGL((stencil_kernel<T, V, false>), grid,                 \
-                         dim3(kStencilThreads), 0, s, p);                     \
-  } while (0)
-  if (dtype == WB2_F32) { if (wide) WB2_L(float, 4); else WB2_L(float, 1); }
-  else { if (wide) WB2_L(double, 2); else WB2_L(double, 1); }
-#undef WB2_L
+  for_field(dtype, wide, [&](auto t, auto v) {
+    using T = decltype(t);
+    constexpr int V = decltype(v)::value;
+    if (lat_rows)
+      hipLaunchKernelGGL((stencil_kernel<T, V, true>), grid,
+                         dim3(kStencilThreads), 0, s, p);
+    else
+      hipLaunchKernelGGL((stencil_kernel<T, V, false>), grid,
+                         dim3(kStencilThreads), 0, s, p);
+  });
   WB2_HIP_OK(hipGetLastError());
   return 0;
 }

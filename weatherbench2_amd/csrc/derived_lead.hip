@@ -24,6 +24,7 @@
 
 #include "common.hpp"
 #include "derived_common.hpp"
+#include "launch_common.hpp"
 #include "trace.hpp"
 #include "wb2hip.h"
 
@@ -45,15 +46,6 @@ struct LeadParams {
   int n_lead, window, clamp;
 };
 
-__device__ __forceinline__ long long outer_of() {
-  return blockIdx.y + (long long)blockIdx.z * gridDim.y;
-}
-
-template <typename T>
-__device__ __forceinline__ T quiet_nan() {
-  return (T)__builtin_nanf("");
-}
-
 constexpr int lead_block(int w) {  // the least common multiple of w and Ahead
   int b = w;
   while (b % kLeadAhead) b += w;
@@ -66,7 +58,7 @@ __global__ void __launch_bounds__(kLeadThreads)
   const long long q =
       ((long long)blockIdx.x * kLeadThreads + threadIdx.x) * VEC;
   if (q >= p.n_point) return;
-  const long long o = outer_of();
+  const long long o = outer_index();
   if (o >= p.n_outer) return;
   constexpr bool DIFF = MODE == WB2_LEAD_DIFF_SUM;
   constexpr int U = kLeadAhead;
@@ -127,7 +119,7 @@ __global__ void __launch_bounds__(kLeadThreads)
     lead_window_reread_kernel(const LeadParams p) {
   const long long q = (long long)blockIdx.x * kLeadThreads + threadIdx.x;
   if (q >= p.n_point) return;
-  const long long o = outer_of();
+  const long long o = outer_index();
   if (o >= p.n_outer) return;
   constexpr bool DIFF = MODE == WB2_LEAD_DIFF_SUM;
   const int n_lead = p.n_lead, w = p.window;
@@ -166,7 +158,7 @@ int wb2_derived_lead_geometry(int dtype, int wide, int32_t* tile_points,
   WB2_REQUIRE(dtype == WB2_F32 || dtype == WB2_F64, "unknown dtype %d", dtype);
   WB2_REQUIRE(tile_points && leads_ahead && windows && n_windows,
               "null pointer argument");
-  *tile_points = kLeadThreads * (wide ? (dtype == WB2_F32 ? 4 : 2) : 1);
+  *tile_points = kLeadThreads * (wide ? wide_lanes(dtype) : 1);
   *leads_ahead = kLeadAhead;
   *windows = kLeadWindows;
   *n_windows = kNumLeadWindows;
@@ -200,53 +192,45 @@ int wb2_derived_lead_window(int mode, int dtype, const void* in,
   p.clamp = clamp_negative;
   bool ring = false;
   for (int k = 0; k < kNumLeadWindows; ++k) ring = ring || kLeadWindows[k] == window;
-  const int w = dtype == WB2_F32 ? 4 : 2;
-  const bool wide = ring && n_point % w == 0 && aligned16(in) && aligned16(out);
-  const int vec = wide ? w : 1;
-  const long long gx =
-      ((n_point + vec - 1) / vec + kLeadThreads - 1) / kLeadThreads;
-  const long long gy = n_outer < 32768 ? n_outer : 32768;
-  const dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)((n_outer + gy - 1) / gy));
+  const int w = wide_lanes(dtype);
+  const bool wide = ring && n_point % w == 0 && all_aligned16(in, out);
+  dim3 grid;
+  WB2_REQUIRE(outer_grid(n_outer,
+                         point_tiles(n_point, wide ? w : 1, kLeadThreads),
+                         &grid),
+              "bad sizes");
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define WB2_L(K) hipLaunchKernelGGL((K), grid, dim3(kLeadThreads), 0, s, p)
-#define WB2_MODE(T, V, W)                                                     \
-  do {                                                                        \
-    if (mode == WB2_LEAD_DIFF_SUM)                                            \
-      WB2_L((lead_window_kernel<T, V, W, WB2_LEAD_DIFF_SUM>));                \
-    else                                                                      \
-      WB2_L((lead_window_kernel<T, V, W, WB2_LEAD_SUM>));                     \
-  } while (0)
-#define WB2_WIDTH(W)                                                          \
-  do {                                                                        \
-    if (dtype == WB2_F32) {                                                   \
-      if (wide) WB2_MODE(float, 4, W); else WB2_MODE(float, 1, W);            \
-    } else {                                                                  \
-      if (wide) WB2_MODE(double, 2, W); else WB2_MODE(double, 1, W);          \
-    }                                                                         \
-  } while (0)
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(kLeadThreads), 0, s, p);
+  };
+  auto launch_ring = [&](auto window_of) {
+    constexpr int W = decltype(window_of)::value;
+    for_field(dtype, wide, [&](auto t, auto v) {
+      using T = decltype(t);
+      constexpr int V = decltype(v)::value;
+      if (mode == WB2_LEAD_DIFF_SUM)
+        launch(lead_window_kernel<T, V, W, WB2_LEAD_DIFF_SUM>);
+      else
+        launch(lead_window_kernel<T, V, W, WB2_LEAD_SUM>);
+    });
+  };
+  // (a switch and not a loop: the window is a template argument)
   switch (ring ? window : 0) {
-    case 1: WB2_WIDTH(1); break;
-    case 2: WB2_WIDTH(2); break;
-    case 4: WB2_WIDTH(4); break;
-    case 6: WB2_WIDTH(6); break;
-    case 8: WB2_WIDTH(8); break;
-    case 24: WB2_WIDTH(24); break;
+    case 1: launch_ring(std::integral_constant<int, 1>{}); break;
+    case 2: launch_ring(std::integral_constant<int, 2>{}); break;
+    case 4: launch_ring(std::integral_constant<int, 4>{}); break;
+    case 6: launch_ring(std::integral_constant<int, 6>{}); break;
+    case 8: launch_ring(std::integral_constant<int, 8>{}); break;
+    case 24: launch_ring(std::integral_constant<int, 24>{}); break;
     default:
-      if (dtype == WB2_F32) {
+      for_field(dtype, false, [&](auto t, auto) {
+        using T = decltype(t);
         if (mode == WB2_LEAD_DIFF_SUM)
-          WB2_L((lead_window_reread_kernel<float, WB2_LEAD_DIFF_SUM>));
+          launch(lead_window_reread_kernel<T, WB2_LEAD_DIFF_SUM>);
         else
-          WB2_L((lead_window_reread_kernel<float, WB2_LEAD_SUM>));
-      } else {
-        if (mode == WB2_LEAD_DIFF_SUM)
-          WB2_L((lead_window_reread_kernel<double, WB2_LEAD_DIFF_SUM>));
-        else
-          WB2_L((lead_window_reread_kernel<double, WB2_LEAD_SUM>));
-      }
+          launch(lead_window_reread_kernel<T, WB2_LEAD_SUM>);
+      });
   }
-#undef WB2_WIDTH
-#undef WB2_MODE
-#undef WB2_L
   WB2_HIP_OK(hipGetLastError());
   return 0;
 }

@@ -52,6 +52,7 @@
 
 #include "common.hpp"
 #include "derived_common.hpp"
+#include "launch_common.hpp"
 #include "trace.hpp"
 #include "wb2hip.h"
 
@@ -83,10 +84,6 @@ template <> struct QKey<double> { typedef unsigned long long type; };
 
 template <typename T>
 constexpr int q_tile() { return kQRowBytes / (int)sizeof(T); }
-
-__device__ __forceinline__ long long q_outer_of() {
-  return blockIdx.y + (long long)blockIdx.z * gridDim.y;
-}
 
 // ---- shared device functions ----------------------------------------------
 template <typename T>
@@ -214,7 +211,7 @@ __global__ void __launch_bounds__(kQResThreads)
   constexpr int RPP = kQResThreads / LPR;  // rows per pass of the workgroup
   extern __shared__ __attribute__((aligned(16))) unsigned char q_lds[];
   K* keys = reinterpret_cast<K*>(q_lds);  // [n_red][P]
-  const long long o = q_outer_of();
+  const long long o = outer_index();
   if (o >= p.n_outer) return;
   const long long i0 = (long long)blockIdx.x * P;
   const int valid = p.n_inner - i0 < P ? (int)(p.n_inner - i0) : P;
@@ -324,7 +321,7 @@ __global__ void __launch_bounds__(kQStrThreads)
   __shared__ K s_lo[P], s_hi[P];
   __shared__ K s_above[P][kQTargets];
   __shared__ int s_start;
-  const long long o = q_outer_of();
+  const long long o = outer_index();
   if (o >= p.n_outer) return;
   const long long i0 = (long long)blockIdx.x * P;
   const int valid = p.n_inner - i0 < P ? (int)(p.n_inner - i0) : P;
@@ -506,15 +503,12 @@ int wb2_quantile_select(int dtype, int skipna, const void* in,
                 "quantile %d = %g is not in [0, 1]", (int)j, q[j]);
   const int tile = dtype == WB2_F32 ? q_tile<float>() : q_tile<double>();
   const long long gx = (n_inner + tile - 1) / tile;
-  const long long gy = n_outer < 32768 ? n_outer : 32768;
-  const long long gz = (n_outer + gy - 1) / gy;
-  WB2_REQUIRE(n_red < (1ll << 31) && gx < (1ll << 31) && gz < 65536,
+  dim3 grid;
+  WB2_REQUIRE(n_red < (1ll << 31) && outer_grid(n_outer, gx, &grid),
               "bad sizes");
-  const dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)gz);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool resident = n_red <= kQLdsBytes / kQRowBytes;
-  const int w = dtype == WB2_F32 ? 4 : 2;
-  const bool wide = n_inner % w == 0 && aligned16(in);
+  const bool wide = n_inner % wide_lanes(dtype) == 0 && aligned16(in);
   if (resident) {
     static const hipError_t allowed = [] {
       hipError_t e = allow_lds(quantile_resident_kernel<float, 4>);
@@ -538,23 +532,16 @@ int wb2_quantile_select(int dtype, int skipna, const void* in,
     p.n_q = n_q - j0 < kQMaxQ ? n_q - j0 : kQMaxQ;
     for (int j = 0; j < p.n_q; ++j) p.q[j] = q[j0 + j];
     p.out = out + (long long)j0 * n_outer * n_inner;
-#define WB2_Q(K, THREADS, LDS) \
-  hipLaunchKernelGGL((K), grid, dim3(THREADS), (LDS), s, p)
-    if (resident) {
-      if (dtype == WB2_F32) {
-        if (wide) WB2_Q((quantile_resident_kernel<float, 4>), kQResThreads, lds);
-        else WB2_Q((quantile_resident_kernel<float, 1>), kQResThreads, lds);
-      } else {
-        if (wide) WB2_Q((quantile_resident_kernel<double, 2>), kQResThreads, lds);
-        else WB2_Q((quantile_resident_kernel<double, 1>), kQResThreads, lds);
-      }
-    } else {
-      if (dtype == WB2_F32)
-        WB2_Q((quantile_stream_kernel<float>), kQStrThreads, 0);
+    for_field(dtype, wide, [&](auto t, auto v) {
+      using T = decltype(t);
+      constexpr int V = decltype(v)::value;
+      if (resident)
+        hipLaunchKernelGGL((quantile_resident_kernel<T, V>), grid,
+                           dim3(kQResThreads), lds, s, p);
       else
-        WB2_Q((quantile_stream_kernel<double>), kQStrThreads, 0);
-    }
-#undef WB2_Q
+        hipLaunchKernelGGL((quantile_stream_kernel<T>), grid,
+                           dim3(kQStrThreads), 0, s, p);
+    });
     WB2_HIP_OK(hipGetLastError());
   }
   return 0;

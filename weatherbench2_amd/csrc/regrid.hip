@@ -36,6 +36,7 @@
 
 #include "common.hpp"
 #include "derived_common.hpp"
+#include "launch_common.hpp"
 #include "trace.hpp"
 #include "wb2hip.h"
 
@@ -45,7 +46,6 @@ namespace {
 constexpr int kRegridThreads = 256;
 constexpr int kBand = 8;               // band entries requested before combining
 constexpr int kRegridLds = 64 * 1024;  // bytes of LDS a workgroup may ask for
-constexpr int kGridSlabs = 32768;      // slabs per grid row (gridDim.y)
 
 struct RegridParams {
   const void* in;
@@ -62,10 +62,6 @@ struct RegridParams {
   const double* lat_w;
   const unsigned char* lat_nan;
 };
-
-__device__ __forceinline__ long long slab_of() {
-  return blockIdx.y + (long long)blockIdx.z * gridDim.y;
-}
 
 __device__ __forceinline__ double regrid_nan() { return __builtin_nan(""); }
 
@@ -87,7 +83,7 @@ template <typename T, int VEC, int MODE>
 __global__ void __launch_bounds__(kRegridThreads)
     regrid_rows_kernel(const RegridParams p) {
   extern __shared__ __align__(16) double regrid_lds[];
-  const long long o = slab_of();
+  const long long o = outer_index();
   if (o >= p.n_slab) return;
   constexpr bool MEAN = MODE == WB2_REGRID_NANMEAN;
   const int c = blockIdx.x;
@@ -179,7 +175,7 @@ __global__ void __launch_bounds__(kRegridThreads)
     regrid_cols_kernel(const RegridParams p, const int n_ctile) {
   extern __shared__ __align__(16) unsigned char regrid_lds_raw[];
   T* rows = reinterpret_cast<T*>(regrid_lds_raw);
-  const long long o = slab_of();
+  const long long o = outer_index();
   if (o >= p.n_slab) return;
   constexpr bool MEAN = MODE == WB2_REGRID_NANMEAN;
   const int a = blockIdx.x / n_ctile;
@@ -268,7 +264,7 @@ __global__ void __launch_bounds__(kRegridThreads)
 template <typename T, int MODE>
 __global__ void __launch_bounds__(kRegridThreads)
     regrid_cell_kernel(const RegridParams p, const int lat_rows) {
-  const long long o = slab_of();
+  const long long o = outer_index();
   if (o >= p.n_slab) return;
   constexpr bool MEAN = MODE == WB2_REGRID_NANMEAN;
   const long long n_tgt = (long long)p.n_tgt_lon * p.n_tgt_lat;
@@ -313,7 +309,7 @@ __global__ void __launch_bounds__(kRegridThreads)
     regrid_gather_kernel(const U* in, const long long* slab, long long n_slab,
                          long long n_src, const int* index, long long n_tgt,
                          U* out) {
-  const long long o = slab_of();
+  const long long o = outer_index();
   const long long j = (long long)blockIdx.x * kRegridThreads + threadIdx.x;
   if (o >= n_slab || j >= n_tgt) return;
   out[o * n_tgt + j] = in[(slab ? slab[o] : o) * n_src + index[j]];
@@ -323,11 +319,6 @@ int regrid_max_contig(int dtype, int lat_rows) {
   const int elem = dtype == WB2_F32 ? 4 : 8;
   return lat_rows ? kRegridLds / (2 * (int)sizeof(double))
                   : kRegridLds / (kBand * elem);
-}
-
-dim3 slab_grid(long long gx, long long n_slab) {
-  const long long gy = n_slab < kGridSlabs ? n_slab : kGridSlabs;
-  return dim3((unsigned)gx, (unsigned)gy, (unsigned)((n_slab + gy - 1) / gy));
 }
 
 }  // namespace
@@ -342,11 +333,11 @@ int wb2_regrid_geometry(int dtype, int lat_rows, int wide, int32_t* tile_elems,
   WB2_REQUIRE(dtype == WB2_F32 || dtype == WB2_F64, "unknown dtype %d", dtype);
   WB2_REQUIRE(tile_elems && run_targets && band_ahead && max_contig &&
               grid_slabs, "null pointer argument");
-  *tile_elems = kRegridThreads * (wide ? (dtype == WB2_F32 ? 4 : 2) : 1);
+  *tile_elems = kRegridThreads * (wide ? wide_lanes(dtype) : 1);
   *run_targets = 1;
   *band_ahead = kBand;
   *max_contig = regrid_max_contig(dtype, lat_rows);
-  *grid_slabs = kGridSlabs;
+  *grid_slabs = (int32_t)kGridOuter;
   return 0;
 }
 
@@ -374,7 +365,7 @@ int wb2_regrid_separable(int mode, int dtype, int lat_rows, const void* in,
               "null pointer argument");
   // (idx and w are empty, and may be null, where every index is uncovered)
   const long long n_tgt = (long long)n_tgt_lon * n_tgt_lat;
-  WB2_REQUIRE(n_slab <= (long long)kGridSlabs * 65535 &&
+  WB2_REQUIRE(n_slab <= kGridOuter * 65535 &&
               (n_tgt + kRegridThreads - 1) / kRegridThreads < (1ll << 31),
               "bad sizes");
   RegridParams p{};
@@ -394,63 +385,54 @@ int wb2_regrid_separable(int mode, int dtype, int lat_rows, const void* in,
   p.lat_idx = lat_idx;
   p.lat_w = lat_w;
   p.lat_nan = lat_nan;
-  const int vec = dtype == WB2_F32 ? 4 : 2;
   const int elem = dtype == WB2_F32 ? 4 : 8;
   const int n_contig = lat_rows ? n_src_lon : n_src_lat;
-  const bool wide = n_contig % vec == 0 && aligned16(in);
+  const bool wide = n_contig % wide_lanes(dtype) == 0 && aligned16(in);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 block(kRegridThreads);
-#define WB2_MODE(K, ...)                                                      \
-  do {                                                                        \
-    if (mode == WB2_REGRID_NANMEAN)                                           \
-      WB2_L(K, WB2_REGRID_NANMEAN, __VA_ARGS__);                              \
-    else                                                                      \
-      WB2_L(K, WB2_REGRID_LINEAR, __VA_ARGS__);                               \
-  } while (0)
+  dim3 grid;
   if (n_contig > regrid_max_contig(dtype, lat_rows)) {
-    const dim3 grid = slab_grid((n_tgt + kRegridThreads - 1) / kRegridThreads,
-                                n_slab);
-#define WB2_L(K, M, ...)                                                      \
-  do {                                                                        \
-    if (dtype == WB2_F32)                                                     \
-      hipLaunchKernelGGL((K<float, M>), grid, block, 0, s, __VA_ARGS__);      \
-    else                                                                      \
-      hipLaunchKernelGGL((K<double, M>), grid, block, 0, s, __VA_ARGS__);     \
-  } while (0)
-    WB2_MODE(regrid_cell_kernel, p, lat_rows);
-#undef WB2_L
+    WB2_REQUIRE(outer_grid(n_slab, point_tiles(n_tgt, 1, kRegridThreads),
+                           &grid),
+                "bad sizes");
+    for_field(dtype, false, [&](auto t, auto) {
+      using T = decltype(t);
+      if (mode == WB2_REGRID_NANMEAN)
+        hipLaunchKernelGGL((regrid_cell_kernel<T, WB2_REGRID_NANMEAN>), grid,
+                           block, 0, s, p, lat_rows);
+      else
+        hipLaunchKernelGGL((regrid_cell_kernel<T, WB2_REGRID_LINEAR>), grid,
+                           block, 0, s, p, lat_rows);
+    });
+  } else if (lat_rows) {
+    WB2_REQUIRE(outer_grid(n_slab, n_tgt_lat, &grid), "bad sizes");
+    const size_t lds = 2 * sizeof(double) * (size_t)n_src_lon;
+    for_field(dtype, wide, [&](auto t, auto v) {
+      using T = decltype(t);
+      constexpr int V = decltype(v)::value;
+      if (mode == WB2_REGRID_NANMEAN)
+        hipLaunchKernelGGL((regrid_rows_kernel<T, V, WB2_REGRID_NANMEAN>),
+                           grid, block, lds, s, p);
+      else
+        hipLaunchKernelGGL((regrid_rows_kernel<T, V, WB2_REGRID_LINEAR>),
+                           grid, block, lds, s, p);
+    });
   } else {
-#define WB2_L(K, M, ...)                                                      \
-  do {                                                                        \
-    if (dtype == WB2_F32) {                                                   \
-      if (wide)                                                               \
-        hipLaunchKernelGGL((K<float, 4, M>), grid, block, lds, s,             \
-                           __VA_ARGS__);                                      \
-      else                                                                    \
-        hipLaunchKernelGGL((K<float, 1, M>), grid, block, lds, s,             \
-                           __VA_ARGS__);                                      \
-    } else {                                                                  \
-      if (wide)                                                               \
-        hipLaunchKernelGGL((K<double, 2, M>), grid, block, lds, s,            \
-                           __VA_ARGS__);                                      \
-      else                                                                    \
-        hipLaunchKernelGGL((K<double, 1, M>), grid, block, lds, s,            \
-                           __VA_ARGS__);                                      \
-    }                                                                         \
-  } while (0)
-    if (lat_rows) {
-      const dim3 grid = slab_grid(n_tgt_lat, n_slab);
-      const size_t lds = 2 * sizeof(double) * (size_t)n_src_lon;
-      WB2_MODE(regrid_rows_kernel, p);
-    } else {
-      const int n_ctile = (n_tgt_lat + kRegridThreads - 1) / kRegridThreads;
-      const dim3 grid = slab_grid((long long)n_tgt_lon * n_ctile, n_slab);
-      const size_t lds = (size_t)kBand * elem * (size_t)n_src_lat;
-      WB2_MODE(regrid_cols_kernel, p, n_ctile);
-    }
-#undef WB2_L
+    const int n_ctile = (int)point_tiles(n_tgt_lat, 1, kRegridThreads);
+    WB2_REQUIRE(outer_grid(n_slab, (long long)n_tgt_lon * n_ctile, &grid),
+                "bad sizes");
+    const size_t lds = (size_t)kBand * elem * (size_t)n_src_lat;
+    for_field(dtype, wide, [&](auto t, auto v) {
+      using T = decltype(t);
+      constexpr int V = decltype(v)::value;
+      if (mode == WB2_REGRID_NANMEAN)
+        hipLaunchKernelGGL((regrid_cols_kernel<T, V, WB2_REGRID_NANMEAN>),
+                           grid, block, lds, s, p, n_ctile);
+      else
+        hipLaunchKernelGGL((regrid_cols_kernel<T, V, WB2_REGRID_LINEAR>),
+                           grid, block, lds, s, p, n_ctile);
+    });
   }
-#undef WB2_MODE
   WB2_HIP_OK(hipGetLastError());
   return 0;
 }
@@ -467,11 +449,12 @@ int wb2_regrid_gather(int elem_size, const void* in, const int64_t* slab,
   WB2_REQUIRE(n_src >= 1 && n_src < (1ll << 31),
               "bad sizes: a source slab of %lld elements", (long long)n_src);
   WB2_REQUIRE(in && out && index, "null pointer argument");
-  WB2_REQUIRE(n_slab <= (long long)kGridSlabs * 65535 &&
+  WB2_REQUIRE(n_slab <= kGridOuter * 65535 &&
               (n_tgt + kRegridThreads - 1) / kRegridThreads < (1ll << 31),
               "bad sizes");
-  const dim3 grid = slab_grid((n_tgt + kRegridThreads - 1) / kRegridThreads,
-                              n_slab);
+  dim3 grid;
+  WB2_REQUIRE(outer_grid(n_slab, point_tiles(n_tgt, 1, kRegridThreads), &grid),
+              "bad sizes");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const long long* table = reinterpret_cast<const long long*>(slab);
 #define WB2_G(U)                                                              \

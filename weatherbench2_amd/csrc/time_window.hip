@@ -25,6 +25,7 @@
 
 #include "common.hpp"
 #include "derived_common.hpp"
+#include "launch_common.hpp"
 #include "trace.hpp"
 #include "wb2hip.h"
 
@@ -33,7 +34,6 @@ namespace {
 
 constexpr int kBinThreads = 256;
 constexpr int kStepsAhead = 4;  // time steps loaded before any is combined
-constexpr long long kBinGridOuter = 32768;  // outer indices per grid row
 
 struct BinParams {
   const void* in;
@@ -44,11 +44,6 @@ struct BinParams {
   int n_time, n_bin, bins_per_group;
 };
 
-template <typename T>
-__device__ __forceinline__ T bin_nan() {
-  return (T)__builtin_nanf("");
-}
-
 template <typename T, int VEC, bool SKIPNA>
 __global__ void __launch_bounds__(kBinThreads)
     time_bin_kernel(const BinParams p) {
@@ -56,7 +51,7 @@ __global__ void __launch_bounds__(kBinThreads)
   const int group = (int)(blockIdx.x / p.n_tile);
   const long long q = (tile * kBinThreads + threadIdx.x) * VEC;
   if (q >= p.n_point) return;
-  const long long o = blockIdx.y + (long long)blockIdx.z * gridDim.y;
+  const long long o = outer_index();
   if (o >= p.n_outer) return;
   constexpr int U = kStepsAhead;
   const long long row = o * p.n_time;
@@ -117,10 +112,10 @@ __global__ void __launch_bounds__(kBinThreads)
     for (int e = 0; e < VEC; ++e) {
       const int n = SKIPNA ? count[e] : end - begin;
       const bool none = !valid || (SKIPNA ? count[e] == 0 : nan[e]);
-      r[0][e] = valid ? sum[e] : bin_nan<T>();
-      r[1][e] = !valid || n == 0 ? bin_nan<T>() : sum[e] / T(n);
-      r[2][e] = none ? bin_nan<T>() : mn[e];
-      r[3][e] = none ? bin_nan<T>() : mx[e];
+      r[0][e] = valid ? sum[e] : quiet_nan<T>();
+      r[1][e] = !valid || n == 0 ? quiet_nan<T>() : sum[e] / T(n);
+      r[2][e] = none ? quiet_nan<T>() : mn[e];
+      r[3][e] = none ? quiet_nan<T>() : mx[e];
     }
     const long long at = (o * p.n_bin + b) * p.n_point + q;
 #pragma unroll
@@ -140,9 +135,9 @@ int wb2_time_window_geometry(int dtype, int wide, int32_t* tile_points,
   WB2_REQUIRE(dtype == WB2_F32 || dtype == WB2_F64, "unknown dtype %d", dtype);
   WB2_REQUIRE(tile_points && steps_ahead && max_grid_outer,
               "null pointer argument");
-  *tile_points = kBinThreads * (wide ? (dtype == WB2_F32 ? 4 : 2) : 1);
+  *tile_points = kBinThreads * (wide ? wide_lanes(dtype) : 1);
   *steps_ahead = kStepsAhead;
-  *max_grid_outer = (int32_t)kBinGridOuter;
+  *max_grid_outer = (int32_t)kGridOuter;
   return 0;
 }
 
@@ -167,7 +162,7 @@ int wb2_time_bin_stats(int stat_mask, int dtype, int skipna, const void* in,
     WB2_REQUIRE(!(stat_mask >> s & 1) || out[s],
                 "statistic %d is asked for but has no output", s);
   WB2_REQUIRE(in && bin_range, "null pointer argument");
-  const int w = dtype == WB2_F32 ? 4 : 2;
+  const int w = wide_lanes(dtype);
   bool wide = n_point % w == 0 && aligned16(in);
   for (int s = 0; s < 4; ++s)
     if (stat_mask >> s & 1) wide = wide && aligned16(out[s]);
@@ -179,34 +174,27 @@ int wb2_time_bin_stats(int stat_mask, int dtype, int skipna, const void* in,
   for (int s = 0; s < 4; ++s) p.out[s] = (stat_mask >> s & 1) ? out[s] : nullptr;
   p.n_outer = n_outer;
   p.n_point = n_point;
-  p.n_tile = ((n_point + vec - 1) / vec + kBinThreads - 1) / kBinThreads;
+  p.n_tile = point_tiles(n_point, vec, kBinThreads);
   p.n_time = n_time;
   p.n_bin = n_bin;
   p.bins_per_group = bins_per_group;
   const long long n_group =
       ((long long)n_bin + bins_per_group - 1) / bins_per_group;
-  const long long gy = n_outer < kBinGridOuter ? n_outer : kBinGridOuter;
-  const long long gz = (n_outer + gy - 1) / gy;
-  WB2_REQUIRE(p.n_tile < (1ll << 31) && p.n_tile * n_group < (1ll << 31) &&
-                  gz <= 65535,
+  dim3 grid;
+  WB2_REQUIRE(p.n_tile < (1ll << 31) &&
+                  outer_grid(n_outer, p.n_tile * n_group, &grid),
               "bad sizes");
-  const dim3 grid((unsigned)(p.n_tile * n_group), (unsigned)gy, (unsigned)gz);
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define WB2_B(T, V)                                                           \
-  do {                                                                        \
-    if (skipna)                                                               \
-      hipLaunchKernelGGL((time_bin_kernel<T, V, true>), grid,                 \
-                         dim3(kBinThreads), 0, s, p);                         \
-    else                                                                      \
-      hipLaunchKernelGGL((time_bin_kernel<T, V, false>), grid,                \
-                         dim3(kBinThreads), 0, s, p);                         \
-  } while (0)
-  if (dtype == WB2_F32) {
-    if (wide) WB2_B(float, 4); else WB2_B(float, 1);
-  } else {
-    if (wide) WB2_B(double, 2); else WB2_B(double, 1);
-  }
-#undef WB2_B
+  for_field(dtype, wide, [&](auto t, auto v) {
+    using T = decltype(t);
+    constexpr int V = decltype(v)::value;
+    if (skipna)
+      hipLaunchKernelGGL((time_bin_kernel<T, V, true>), grid,
+                         dim3(kBinThreads), 0, s, p);
+    else
+      hipLaunchKernelGGL((time_bin_kernel<T, V, false>), grid,
+                         dim3(kBinThreads), 0, s, p);
+  });
   WB2_HIP_OK(hipGetLastError());
   return 0;
 }

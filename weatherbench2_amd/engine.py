@@ -5,6 +5,7 @@ every FLOP of the hot path runs in libwb2hip.so.
 """
 from __future__ import annotations
 
+import ctypes
 import os
 import threading
 import typing as t
@@ -30,6 +31,45 @@ def set_launch_hook(hook):
   global _LAUNCH_HOOK
   old, _LAUNCH_HOOK = _LAUNCH_HOOK, hook
   return old
+
+
+def _launch(kernel: str, c_name: str, *args) -> None:
+  """One entry point of the library between the hook's 'begin' and 'end' of
+  `kernel`; a nonzero return raises (and leaves the bracket open, as a failed
+  launch always did)."""
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('begin', kernel)
+  _lib.check(getattr(_lib.load(), c_name)(*args), c_name)
+  if _LAUNCH_HOOK is not None:
+    _LAUNCH_HOOK('end', kernel)
+
+
+def _require_float(*tensors) -> None:
+  """The tensors (None: absent) share one of the kernels' two dtypes."""
+  first = tensors[0]
+  if first.dtype not in _DTYPES or any(
+      x is not None and x.dtype != first.dtype for x in tensors):
+    raise TypeError('the input must be float32 or float64' if len(tensors) == 1
+                    else 'inputs must share a float32/float64 dtype')
+
+
+def _check_slab(slab, n: int, what: str) -> None:
+  """A slab table is None or `n` int64; `what` spells n in the message."""
+  if slab is not None and (slab.dtype != torch.int64 or slab.numel() != n):
+    raise ValueError(f'the slab table must hold {what} int64')
+
+
+_I32 = ctypes.c_int32
+
+
+def _geometry(c_name: str, ins, outs) -> dict:
+  """{name: value} of the out-parameters `outs` = [(name, ctypes type)], in
+  order, of the geometry entry point `c_name` called with the integers `ins`
+  (a pointer has no value and is returned as it is)."""
+  vals = [ctype() for _, ctype in outs]
+  _lib.check(getattr(_lib.load(), c_name)(
+      *ins, *[ctypes.byref(v) for v in vals]), c_name)
+  return {name: getattr(v, 'value', v) for (name, _), v in zip(outs, vals)}
 
 
 def current_stream_ptr(device) -> int:
@@ -418,7 +458,6 @@ class PairSuiteStep:
 
   def __init__(self, plan: ReductionPlan, mode: int, dtype: torch.dtype,
                skipna: bool, n_outer: int, n_pair: int, aligned: bool = True):
-    import ctypes
     lib = _lib.load()
     if dtype not in _DTYPES:
       raise TypeError(f'unsupported dtype {dtype}')
@@ -498,7 +537,6 @@ class SuiteStep:
                skipna: bool, n_outer: int, aligned: bool = True,
                aux: t.Optional[torch.Tensor] = None, scalar: float = 0.0,
                by_address: bool = False):
-    import ctypes
     lib = _lib.load()
     if dtype not in _DTYPES:
       raise TypeError(f'unsupported dtype {dtype}')
@@ -767,7 +805,6 @@ def energy_score(plan: ReductionPlan, ens: torch.Tensor, member_stride: int,
   """wb2_energy_score: (score, spread, skill)[3, n_region, n_outer] float64 of
   a member-major ensemble (`member_stride` elements between members) in one
   read of the members.  Asynchronous on the current stream."""
-  import ctypes
   lib = _lib.load()
   dev = plan.device
   dtype = ens.dtype
@@ -795,15 +832,11 @@ def energy_score(plan: ReductionPlan, ens: torch.Tensor, member_stride: int,
                       dtype=torch.float64, device=dev)
   out = torch.empty((3, plan.n_region, n_outer), dtype=torch.float64,
                     device=dev)
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('begin', 'energy_score')
-  _lib.check(lib.wb2_energy_score(
-      _DTYPES[dtype], int(skipna), _lib.ptr(ens), _lib.ptr(ens_slab),
-      _lib.ptr(truth), _lib.ptr(truth_slab), n_member, member_stride, n_outer,
-      ctypes.byref(tables), _lib.ptr(partials), _lib.ptr(means), _lib.ptr(out),
-      current_stream_ptr(dev)), 'wb2_energy_score')
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('end', 'energy_score')
+  _launch('energy_score', 'wb2_energy_score', _DTYPES[dtype], int(skipna),
+          _lib.ptr(ens), _lib.ptr(ens_slab), _lib.ptr(truth),
+          _lib.ptr(truth_slab), n_member, member_stride, n_outer,
+          ctypes.byref(tables), _lib.ptr(partials), _lib.ptr(means),
+          _lib.ptr(out), current_stream_ptr(dev))
   del keep
   return out
 
@@ -853,7 +886,6 @@ class _SpectrumPlans(threading.local):
     self.plans = {}
 
   def get(self, dtype_code: int, n_lon: int, n_rows: int):
-    import ctypes
     key = (dtype_code, n_lon, n_rows, torch.cuda.current_device())
     hit = self.plans.get(key)
     if hit is None:
@@ -1018,35 +1050,25 @@ def derived_pointwise(mode: str, a: torch.Tensor, a_slab, b: torch.Tensor,
   """K8 pointwise maps: [n_slab, n_point] of `out_dtype` (the input dtype when
   None).  Slab o of `a` / `b` starts `table[o] * n_point` elements after the
   tensor's first element (identity when the table is None)."""
-  lib = _lib.load()
   dev = a.device
-  if a.dtype not in _DTYPES or b.dtype != a.dtype:
-    raise TypeError('inputs must share a float32/float64 dtype')
+  _require_float(a, b)
   out_dtype = a.dtype if out_dtype is None else out_dtype
   out = torch.empty((n_slab, n_point), dtype=out_dtype, device=dev)
   if slab_scalar is not None and (slab_scalar.dtype != out_dtype
                                   or slab_scalar.numel() != n_slab):
     raise ValueError('slab_scalar must hold n_slab values of out_dtype')
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('begin', 'derived_pointwise')
-  _lib.check(lib.wb2_derived_pointwise(
-      POINT_MODES[mode], _DTYPES[a.dtype], _DTYPES[out_dtype], _lib.ptr(a),
-      _lib.ptr(a_slab), _lib.ptr(b), _lib.ptr(b_slab), _lib.ptr(slab_scalar),
-      n_slab, n_point, _lib.ptr(out), current_stream_ptr(dev)),
-             'wb2_derived_pointwise')
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('end', 'derived_pointwise')
+  _launch('derived_pointwise', 'wb2_derived_pointwise', POINT_MODES[mode],
+          _DTYPES[a.dtype], _DTYPES[out_dtype], _lib.ptr(a), _lib.ptr(a_slab),
+          _lib.ptr(b), _lib.ptr(b_slab), _lib.ptr(slab_scalar), n_slab,
+          n_point, _lib.ptr(out), current_stream_ptr(dev))
   return out
 
 
 def stencil_geometry(dtype: torch.dtype, wide: bool) -> tuple:
   """(columns per workgroup tile, rows per row chunk) of the stencil kernel."""
-  import ctypes
-  tile, rows = ctypes.c_int32(), ctypes.c_int32()
-  _lib.check(_lib.load().wb2_derived_stencil_geometry(
-      _DTYPES[dtype], int(wide), ctypes.byref(tile), ctypes.byref(rows)),
-             'wb2_derived_stencil_geometry')
-  return tile.value, rows.value
+  return tuple(_geometry('wb2_derived_stencil_geometry',
+                         (_DTYPES[dtype], int(wide)),
+                         [('tile', _I32), ('rows', _I32)]).values())
 
 
 def derived_stencil(mode: str, inputs: t.Sequence[t.Optional[torch.Tensor]],
@@ -1059,12 +1081,9 @@ def derived_stencil(mode: str, inputs: t.Sequence[t.Optional[torch.Tensor]],
   for the ageostrophic modes only), each with an optional slab table;
   `row_coef` / `col_coef` are plan.gradient_tables of the two axes,
   `lat_tables` plan.latitude_tables, all float64 on the device."""
-  lib = _lib.load()
   first = inputs[0]
   dev = first.device
-  if first.dtype not in _DTYPES or any(
-      x is not None and x.dtype != first.dtype for x in inputs):
-    raise TypeError('inputs must share a float32/float64 dtype')
+  _require_float(*inputs)
   n_lat = n_row if lat_rows else n_col
   if (tuple(row_coef.shape) != (4, n_row) or tuple(col_coef.shape) != (4, n_col)
       or tuple(lat_tables.shape) != (2, n_lat)):
@@ -1072,17 +1091,12 @@ def derived_stencil(mode: str, inputs: t.Sequence[t.Optional[torch.Tensor]],
   inputs = list(inputs) + [None] * (4 - len(inputs))
   slabs = list(slabs) + [None] * (4 - len(slabs))
   out = torch.empty((n_slab, n_row, n_col), dtype=torch.float64, device=dev)
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('begin', 'derived_stencil')
-  _lib.check(lib.wb2_derived_stencil(
-      STENCIL_MODES[mode], _DTYPES[first.dtype], int(lat_rows),
-      _lib.ptr_array(inputs), _lib.ptr_array(slabs), n_slab, n_row, n_col,
-      _lib.ptr(row_coef), int(row_uniform), _lib.ptr(col_coef),
-      int(col_uniform), _lib.ptr(lat_tables[0]), _lib.ptr(lat_tables[1]),
-      float(m_per_deg), _lib.ptr(out), current_stream_ptr(dev)),
-             'wb2_derived_stencil')
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('end', 'derived_stencil')
+  _launch('derived_stencil', 'wb2_derived_stencil', STENCIL_MODES[mode],
+          _DTYPES[first.dtype], int(lat_rows), _lib.ptr_array(inputs),
+          _lib.ptr_array(slabs), n_slab, n_row, n_col, _lib.ptr(row_coef),
+          int(row_uniform), _lib.ptr(col_coef), int(col_uniform),
+          _lib.ptr(lat_tables[0]), _lib.ptr(lat_tables[1]), float(m_per_deg),
+          _lib.ptr(out), current_stream_ptr(dev))
   return out
 
 
@@ -1093,12 +1107,9 @@ COLUMN_MODES = {'integral': 0, 'transport': 1, 'gradient_ratio': 2,
 def column_geometry(dtype: torch.dtype, wide: bool) -> tuple:
   """(points per workgroup tile, levels in flight per thread) of the column
   kernel."""
-  import ctypes
-  tile, ahead = ctypes.c_int32(), ctypes.c_int32()
-  _lib.check(_lib.load().wb2_derived_column_geometry(
-      _DTYPES[dtype], int(wide), ctypes.byref(tile), ctypes.byref(ahead)),
-             'wb2_derived_column_geometry')
-  return tile.value, ahead.value
+  return tuple(_geometry('wb2_derived_column_geometry',
+                         (_DTYPES[dtype], int(wide)),
+                         [('tile', _I32), ('ahead', _I32)]).values())
 
 
 def zonal_mean(x: torch.Tensor, slab, n_slab: int, n_row: int, n_col: int,
@@ -1108,14 +1119,9 @@ def zonal_mean(x: torch.Tensor, slab, n_slab: int, n_row: int, n_col: int,
   None), in the dtype of `x`."""
   out = torch.empty((n_slab, n_row if lat_rows else n_col), dtype=x.dtype,
                     device=x.device)
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('begin', 'derived_zonal_mean')
-  _lib.check(_lib.load().wb2_derived_zonal_mean(
-      _DTYPES[x.dtype], int(lat_rows), _lib.ptr(x), _lib.ptr(slab), n_slab,
-      n_row, n_col, _lib.ptr(out), current_stream_ptr(x.device)),
-             'wb2_derived_zonal_mean')
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('end', 'derived_zonal_mean')
+  _launch('derived_zonal_mean', 'wb2_derived_zonal_mean', _DTYPES[x.dtype],
+          int(lat_rows), _lib.ptr(x), _lib.ptr(slab), n_slab, n_row, n_col,
+          _lib.ptr(out), current_stream_ptr(x.device))
   return out
 
 
@@ -1141,7 +1147,6 @@ def derived_column(mode: str, inputs: t.Sequence[torch.Tensor],
     cumulative                   -> `out` itself (float64), integrated in place
       through slabs[0]
   """
-  lib = _lib.load()
   inputs = list(inputs)
   first = out if mode == 'cumulative' else inputs[0]
   dev = first.device
@@ -1166,17 +1171,13 @@ def derived_column(mode: str, inputs: t.Sequence[torch.Tensor],
   elif mode != 'cumulative':
     out = torch.empty((n_column, n_point), dtype=out_dtype, device=dev)
   begin, end = (0, n_level) if levels is None else levels
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('begin', 'derived_column')
-  _lib.check(lib.wb2_derived_column(
-      COLUMN_MODES[mode], _DTYPES[first.dtype], _DTYPES[out_dtype],
-      _lib.ptr_array((inputs + list(means) + [None] * 4)[:4]),
-      _lib.ptr_array((list(slabs) + [None] * 3)[:3]), n_column, n_level,
-      n_point, begin, end, _lib.ptr(spacing), _lib.ptr(level_coef),
-      int(level_uniform), mean_div, n_mean, float(scale), _lib.ptr(out),
-      current_stream_ptr(dev)), 'wb2_derived_column')
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('end', 'derived_column')
+  _launch('derived_column', 'wb2_derived_column', COLUMN_MODES[mode],
+          _DTYPES[first.dtype], _DTYPES[out_dtype],
+          _lib.ptr_array((inputs + list(means) + [None] * 4)[:4]),
+          _lib.ptr_array((list(slabs) + [None] * 3)[:3]), n_column, n_level,
+          n_point, begin, end, _lib.ptr(spacing),
+          _lib.ptr(level_coef), int(level_uniform), mean_div, n_mean,
+          float(scale), _lib.ptr(out), current_stream_ptr(dev))
   return out
 
 
@@ -1186,13 +1187,10 @@ LEAD_MODES = {'diff_sum': 0, 'sum': 1}
 def lead_geometry(dtype: torch.dtype, wide: bool) -> tuple:
   """(points per workgroup tile, leads in flight per thread, the window counts
   that keep their terms in registers) of the lead-window kernel."""
-  import ctypes
-  tile, ahead, n = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-  windows = ctypes.POINTER(ctypes.c_int32)()
-  _lib.check(_lib.load().wb2_derived_lead_geometry(
-      _DTYPES[dtype], int(wide), ctypes.byref(tile), ctypes.byref(ahead),
-      ctypes.byref(windows), ctypes.byref(n)), 'wb2_derived_lead_geometry')
-  return tile.value, ahead.value, tuple(windows[k] for k in range(n.value))
+  g = _geometry('wb2_derived_lead_geometry', (_DTYPES[dtype], int(wide)),
+                [('tile', _I32), ('ahead', _I32),
+                 ('windows', ctypes.POINTER(_I32)), ('n', _I32)])
+  return g['tile'], g['ahead'], tuple(g['windows'][k] for k in range(g['n']))
 
 
 def derived_lead_window(mode: str, x: torch.Tensor,
@@ -1210,23 +1208,15 @@ def derived_lead_window(mode: str, x: torch.Tensor,
     sum       the rolling sum over `window` leads of x, NaN at the first
               `window - 1` leads
   """
-  lib = _lib.load()
-  if x.dtype not in _DTYPES:
-    raise TypeError('the input must be float32 or float64')
-  if slab is not None and (slab.dtype != torch.int64
-                           or slab.numel() != n_outer * n_lead):
-    raise ValueError('the slab table must hold n_outer * n_lead int64')
+  _require_float(x)
+  _check_slab(slab, n_outer * n_lead, 'n_outer * n_lead')
   if window < 1:
     raise ValueError(f'window={window} must be at least one lead')
   out = torch.empty((n_outer, n_lead, n_point), dtype=x.dtype, device=x.device)
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('begin', 'derived_lead_window')
-  _lib.check(lib.wb2_derived_lead_window(
-      LEAD_MODES[mode], _DTYPES[x.dtype], _lib.ptr(x), _lib.ptr(slab), n_outer,
-      n_lead, n_point, min(int(window), 2**31 - 1), int(clamp_negative),
-      _lib.ptr(out), current_stream_ptr(x.device)), 'wb2_derived_lead_window')
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('end', 'derived_lead_window')
+  _launch('derived_lead_window', 'wb2_derived_lead_window', LEAD_MODES[mode],
+          _DTYPES[x.dtype], _lib.ptr(x), _lib.ptr(slab), n_outer, n_lead,
+          n_point, min(int(window), 2**31 - 1), int(clamp_negative),
+          _lib.ptr(out), current_stream_ptr(x.device))
   return out
 
 
@@ -1239,13 +1229,10 @@ def regrid_geometry(dtype: torch.dtype, lat_rows: bool, wide: bool) -> dict:
   `band` band entries a thread requests before it combines any, `max_contig`
   the longest contiguous axis the workgroup kernels hold (longer ones take the
   one-thread-per-cell kernel), `grid_slabs` slabs per grid row."""
-  import ctypes
-  vals = [ctypes.c_int32() for _ in range(5)]
-  _lib.check(_lib.load().wb2_regrid_geometry(
-      _DTYPES[dtype], int(lat_rows), int(wide),
-      *[ctypes.byref(v) for v in vals]), 'wb2_regrid_geometry')
-  return dict(zip(('tile', 'run', 'band', 'max_contig', 'grid_slabs'),
-                  (v.value for v in vals)))
+  return _geometry('wb2_regrid_geometry',
+                   (_DTYPES[dtype], int(lat_rows), int(wide)),
+                   [(name, _I32) for name in
+                    ('tile', 'run', 'band', 'max_contig', 'grid_slabs')])
 
 
 def regrid_separable(mode: str, x: torch.Tensor,
@@ -1257,28 +1244,20 @@ def regrid_separable(mode: str, x: torch.Tensor,
   Shapes are (n_lon, n_lat); `tables` = (ptr, idx, w, nan) of the longitude
   axis, then of the latitude axis, on the device of `x`; `slab` the int64
   device table of the slabs (None: contiguous)."""
-  lib = _lib.load()
-  if x.dtype not in _DTYPES:
-    raise TypeError('the input must be float32 or float64')
-  if slab is not None and (slab.dtype != torch.int64
-                           or slab.numel() != n_slab):
-    raise ValueError('the slab table must hold n_slab int64')
+  _require_float(x)
+  _check_slab(slab, n_slab, 'n_slab')
   (s_lon, s_lat), (t_lon, t_lat) = source_shape, target_shape
   ptr_lon, idx_lon, w_lon, nan_lon, ptr_lat, idx_lat, w_lat, nan_lat = tables
   for ptr, n in ((ptr_lon, t_lon), (ptr_lat, t_lat)):
     if ptr.dtype != torch.int32 or ptr.numel() != n + 1:
       raise ValueError('an axis table must hold n_target + 1 int32 offsets')
   out = torch.empty((n_slab, t_lat * t_lon), dtype=x.dtype, device=x.device)
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('begin', 'regrid_separable')
-  _lib.check(lib.wb2_regrid_separable(
-      REGRID_MODES[mode], _DTYPES[x.dtype], int(lat_rows), _lib.ptr(x),
-      _lib.ptr(slab), n_slab, s_lon, s_lat, t_lon, t_lat, _lib.ptr(ptr_lon),
-      _lib.ptr(idx_lon), _lib.ptr(w_lon), _lib.ptr(nan_lon), _lib.ptr(ptr_lat),
-      _lib.ptr(idx_lat), _lib.ptr(w_lat), _lib.ptr(nan_lat), _lib.ptr(out),
-      current_stream_ptr(x.device)), 'wb2_regrid_separable')
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('end', 'regrid_separable')
+  _launch('regrid_separable', 'wb2_regrid_separable', REGRID_MODES[mode],
+          _DTYPES[x.dtype], int(lat_rows), _lib.ptr(x), _lib.ptr(slab), n_slab,
+          s_lon, s_lat, t_lon, t_lat, _lib.ptr(ptr_lon), _lib.ptr(idx_lon),
+          _lib.ptr(w_lon), _lib.ptr(nan_lon), _lib.ptr(ptr_lat),
+          _lib.ptr(idx_lat), _lib.ptr(w_lat), _lib.ptr(nan_lat), _lib.ptr(out),
+          current_stream_ptr(x.device))
   return out
 
 
@@ -1287,21 +1266,13 @@ def regrid_gather(x: torch.Tensor, slab: t.Optional[torch.Tensor],
   """K11 gather: out[o][j] = slab o of `x` at index[j] (int32 device table),
   for elements of 1, 2, 4 or 8 bytes, [n_slab, len(index)] of the dtype of
   `x`."""
-  lib = _lib.load()
   if index.dtype != torch.int32:
     raise ValueError('the index table must be int32')
-  if slab is not None and (slab.dtype != torch.int64
-                           or slab.numel() != n_slab):
-    raise ValueError('the slab table must hold n_slab int64')
+  _check_slab(slab, n_slab, 'n_slab')
   out = torch.empty((n_slab, index.numel()), dtype=x.dtype, device=x.device)
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('begin', 'regrid_gather')
-  _lib.check(lib.wb2_regrid_gather(
-      x.element_size(), _lib.ptr(x), _lib.ptr(slab), n_slab, n_src,
-      _lib.ptr(index), index.numel(), _lib.ptr(out),
-      current_stream_ptr(x.device)), 'wb2_regrid_gather')
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('end', 'regrid_gather')
+  _launch('regrid_gather', 'wb2_regrid_gather', x.element_size(), _lib.ptr(x),
+          _lib.ptr(slab), n_slab, n_src, _lib.ptr(index), index.numel(),
+          _lib.ptr(out), current_stream_ptr(x.device))
   return out
 
 
@@ -1310,14 +1281,10 @@ def quantile_geometry(dtype: torch.dtype, wide: bool = False) -> dict:
   workgroup, `max_resident` the longest series selected out of LDS (longer
   ones stream), `targets_per_pass` quantiles that share a streaming pass,
   `key_bits_per_pass` key bits settled per counting pass."""
-  import ctypes
-  tile, targets, bits = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-  resident = ctypes.c_int64()
-  _lib.check(_lib.load().wb2_quantile_geometry(
-      _DTYPES[dtype], int(wide), ctypes.byref(tile), ctypes.byref(resident),
-      ctypes.byref(targets), ctypes.byref(bits)), 'wb2_quantile_geometry')
-  return {'tile_points': tile.value, 'max_resident': resident.value,
-          'targets_per_pass': targets.value, 'key_bits_per_pass': bits.value}
+  return _geometry('wb2_quantile_geometry', (_DTYPES[dtype], int(wide)),
+                   [('tile_points', _I32), ('max_resident', ctypes.c_int64),
+                    ('targets_per_pass', _I32),
+                    ('key_bits_per_pass', _I32)])
 
 
 def quantile_select(x: torch.Tensor, slab: t.Optional[torch.Tensor],
@@ -1328,25 +1295,16 @@ def quantile_select(x: torch.Tensor, slab: t.Optional[torch.Tensor],
   `slab` is the int64 device table [n_outer, n_red] (sample r of outer index o
   starts `table * n_inner` elements after the first element of `x`), None for
   a contiguous `x`; `q` a sequence of numbers in [0, 1]."""
-  import ctypes
-  lib = _lib.load()
-  if x.dtype not in _DTYPES:
-    raise TypeError('the input must be float32 or float64')
-  if slab is not None and (slab.dtype != torch.int64
-                           or slab.numel() != n_outer * n_red):
-    raise ValueError('the slab table must hold n_outer * n_red int64')
+  _require_float(x)
+  _check_slab(slab, n_outer * n_red, 'n_outer * n_red')
   qs = [float(v) for v in q]
   q_host = (ctypes.c_double * len(qs))(*qs)
   out = torch.empty((len(qs), n_outer, n_inner), dtype=torch.float64,
                     device=x.device)
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('begin', 'quantile_select')
-  _lib.check(lib.wb2_quantile_select(
-      _DTYPES[x.dtype], int(bool(skipna)), _lib.ptr(x), _lib.ptr(slab), n_outer,
-      n_red, n_inner, q_host, len(qs), _lib.ptr(out),
-      current_stream_ptr(x.device)), 'wb2_quantile_select')
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('end', 'quantile_select')
+  _launch('quantile_select', 'wb2_quantile_select', _DTYPES[x.dtype],
+          int(bool(skipna)), _lib.ptr(x), _lib.ptr(slab), n_outer, n_red,
+          n_inner, q_host, len(qs), _lib.ptr(out),
+          current_stream_ptr(x.device))
   return out
 
 
@@ -1357,13 +1315,9 @@ def time_window_geometry(dtype: torch.dtype, wide: bool = False) -> dict:
   """Extents of the K13 kernel: `tile_points` adjacent points per workgroup,
   `steps_ahead` time steps a thread requests before it combines any,
   `max_grid_outer` outer indices per grid row."""
-  import ctypes
-  tile, ahead, outer = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-  _lib.check(_lib.load().wb2_time_window_geometry(
-      _DTYPES[dtype], int(wide), ctypes.byref(tile), ctypes.byref(ahead),
-      ctypes.byref(outer)), 'wb2_time_window_geometry')
-  return {'tile_points': tile.value, 'steps_ahead': ahead.value,
-          'max_grid_outer': outer.value}
+  return _geometry('wb2_time_window_geometry', (_DTYPES[dtype], int(wide)),
+                   [('tile_points', _I32), ('steps_ahead', _I32),
+                    ('max_grid_outer', _I32)])
 
 
 def time_bin_stats(x: torch.Tensor, slab: t.Optional[torch.Tensor],
@@ -1378,12 +1332,8 @@ def time_bin_stats(x: torch.Tensor, slab: t.Optional[torch.Tensor],
   int64 device table [n_outer, n_time] (time step t of outer index o starts
   `table * n_point` elements after the first element of `x`), None for a
   contiguous `x`."""
-  lib = _lib.load()
-  if x.dtype not in _DTYPES:
-    raise TypeError('the input must be float32 or float64')
-  if slab is not None and (slab.dtype != torch.int64
-                           or slab.numel() != n_outer * n_time):
-    raise ValueError('the slab table must hold n_outer * n_time int64')
+  _require_float(x)
+  _check_slab(slab, n_outer * n_time, 'n_outer * n_time')
   if (bin_range.dtype != torch.int32 or bin_range.dim() != 2
       or bin_range.shape[1] != 2 or not bin_range.is_contiguous()
       or bin_range.device != x.device):
@@ -1398,15 +1348,10 @@ def time_bin_stats(x: torch.Tensor, slab: t.Optional[torch.Tensor],
                          device=x.device) for s in names}
   mask = sum(1 << TIME_STATS.index(s) for s in names)
   out_ptrs = _lib.ptr_array([outs.get(s) for s in TIME_STATS])
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('begin', 'time_bin_stats')
-  _lib.check(lib.wb2_time_bin_stats(
-      mask, _DTYPES[x.dtype], int(bool(skipna)), _lib.ptr(x), _lib.ptr(slab),
-      n_outer, n_time, n_point, _lib.ptr(bin_range), n_bin,
-      int(bins_per_group), out_ptrs, current_stream_ptr(x.device)),
-             'wb2_time_bin_stats')
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('end', 'time_bin_stats')
+  _launch('time_bin_stats', 'wb2_time_bin_stats', mask, _DTYPES[x.dtype],
+          int(bool(skipna)), _lib.ptr(x), _lib.ptr(slab), n_outer, n_time,
+          n_point, _lib.ptr(bin_range), n_bin, int(bins_per_group), out_ptrs,
+          current_stream_ptr(x.device))
   return outs
 
 
@@ -1417,21 +1362,14 @@ def climatology_geometry(dtype: torch.dtype, wide: bool = False) -> dict:
   """Extents of the K14 moments kernel: `tile_points` adjacent points per
   workgroup, `members_ahead` members a thread requests before it combines
   any, `max_grid_outer` outer indices per grid row."""
-  import ctypes
-  tile, ahead, outer = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-  _lib.check(_lib.load().wb2_climatology_geometry(
-      _DTYPES[dtype], int(wide), ctypes.byref(tile), ctypes.byref(ahead),
-      ctypes.byref(outer)), 'wb2_climatology_geometry')
-  return {'tile_points': tile.value, 'members_ahead': ahead.value,
-          'max_grid_outer': outer.value}
+  return _geometry('wb2_climatology_geometry', (_DTYPES[dtype], int(wide)),
+                   [('tile_points', _I32), ('members_ahead', _I32),
+                    ('max_grid_outer', _I32)])
 
 
 def _check_series(x, slab, n_outer, n_time, lists):
-  if x.dtype not in _DTYPES:
-    raise TypeError('the input must be float32 or float64')
-  if slab is not None and (slab.dtype != torch.int64
-                           or slab.numel() != n_outer * n_time):
-    raise ValueError('the slab table must hold n_outer * n_time int64')
+  _require_float(x)
+  _check_slab(slab, n_outer * n_time, 'n_outer * n_time')
   for name, a in lists.items():
     if a is not None and (a.dtype != torch.int32 or a.dim() != 1
                           or not a.is_contiguous() or a.device != x.device):
@@ -1451,8 +1389,6 @@ def group_moments(x: torch.Tensor, slab: t.Optional[torch.Tensor],
   [0, n_time) is an absent sample); `fill` (int32 device tensor like `member`,
   or None) names the step read in the place of a NaN, negative for none.
   `slab` as for `time_bin_stats`."""
-  import numpy as np
-  lib = _lib.load()
   _check_series(x, slab, n_outer, n_time, {'member': member, 'fill': fill})
   begin = np.ascontiguousarray(group_begin, dtype=np.int32)
   if begin.ndim != 1 or begin.size < 1:
@@ -1469,17 +1405,12 @@ def group_moments(x: torch.Tensor, slab: t.Optional[torch.Tensor],
   begin_dev = torch.from_numpy(begin).to(x.device)
   outs = tuple(torch.empty((n_outer, n_group, n_point), dtype=torch.float64,
                            device=x.device) for _ in range(3))
-  import ctypes
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('begin', 'group_moments')
-  _lib.check(lib.wb2_group_moments(
-      _DTYPES[x.dtype], _lib.ptr(x), _lib.ptr(slab), n_outer, n_time, n_point,
-      _lib.ptr(begin_dev), begin.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-      n_group, _lib.ptr(member), _lib.ptr(fill), n_member, _lib.ptr(pivot),
-      _lib.ptr(outs[0]), _lib.ptr(outs[1]), _lib.ptr(outs[2]),
-      current_stream_ptr(x.device)), 'wb2_group_moments')
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('end', 'group_moments')
+  _launch('group_moments', 'wb2_group_moments', _DTYPES[x.dtype], _lib.ptr(x),
+          _lib.ptr(slab), n_outer, n_time, n_point, _lib.ptr(begin_dev),
+          begin.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n_group,
+          _lib.ptr(member), _lib.ptr(fill), n_member, _lib.ptr(pivot),
+          _lib.ptr(outs[0]), _lib.ptr(outs[1]), _lib.ptr(outs[2]),
+          current_stream_ptr(x.device))
   return outs
 
 
@@ -1489,17 +1420,11 @@ def first_finite(x: torch.Tensor, slab: t.Optional[torch.Tensor],
   """K14 pivot plane: float64 [n_outer, n_point], the first sample of every
   point, in the order of `member`, that is neither NaN nor +-inf; 0.0 if there
   is none."""
-  lib = _lib.load()
   _check_series(x, slab, n_outer, n_time, {'member': member})
   pivot = torch.empty((n_outer, n_point), dtype=torch.float64, device=x.device)
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('begin', 'first_finite')
-  _lib.check(lib.wb2_first_finite(
-      _DTYPES[x.dtype], _lib.ptr(x), _lib.ptr(slab), n_outer, n_time, n_point,
-      _lib.ptr(member), int(member.numel()), _lib.ptr(pivot),
-      current_stream_ptr(x.device)), 'wb2_first_finite')
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('end', 'first_finite')
+  _launch('first_finite', 'wb2_first_finite', _DTYPES[x.dtype], _lib.ptr(x),
+          _lib.ptr(slab), n_outer, n_time, n_point, _lib.ptr(member),
+          int(member.numel()), _lib.ptr(pivot), current_stream_ptr(x.device))
   return pivot
 
 
@@ -1511,7 +1436,6 @@ def cycle_smooth(mode: str, moments, pivot: t.Optional[torch.Tensor],
   groups are n_cycle cycles of n_pos positions, with the float64 device
   `weights` of an odd window; `mode` is 'explicit' or 'fast' (see
   include/wb2hip.h)."""
-  lib = _lib.load()
   if mode not in SMOOTH_MODES:
     raise ValueError(f'mode must be one of {SMOOTH_MODES}: {mode!r}')
   names = list(dict.fromkeys(want))
@@ -1535,16 +1459,11 @@ def cycle_smooth(mode: str, moments, pivot: t.Optional[torch.Tensor],
                             or not pivot.is_contiguous()):
     raise ValueError('pivot must be a contiguous float64 [n_outer, n_point]')
   outs = {s: torch.empty_like(count) for s in names}
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('begin', 'cycle_smooth')
-  _lib.check(lib.wb2_cycle_smooth(
-      SMOOTH_MODES.index(mode), _lib.ptr(count), _lib.ptr(total),
-      _lib.ptr(sumsq), _lib.ptr(pivot), n_outer, n_cycle, n_pos, n_point,
-      _lib.ptr(weights), int(weights.numel()), _lib.ptr(outs.get('mean')),
-      _lib.ptr(outs.get('std')), current_stream_ptr(count.device)),
-             'wb2_cycle_smooth')
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('end', 'cycle_smooth')
+  _launch('cycle_smooth', 'wb2_cycle_smooth', SMOOTH_MODES.index(mode),
+          _lib.ptr(count), _lib.ptr(total), _lib.ptr(sumsq), _lib.ptr(pivot),
+          n_outer, n_cycle, n_pos, n_point, _lib.ptr(weights),
+          int(weights.numel()), _lib.ptr(outs.get('mean')),
+          _lib.ptr(outs.get('std')), current_stream_ptr(count.device))
   return outs
 
 
@@ -1615,7 +1534,6 @@ def rank_histogram(ens: torch.Tensor, member_stride: int, n_member: int,
     if x.device != dev or not x.is_contiguous():
       raise ValueError('inputs must be contiguous on one device')
   if mean_over is not None:
-    import ctypes
     n_lead, n_time, n_tail = (int(v) for v in mean_over)
     if n_lead * n_time * n_tail != n_outer or n_time < 1:
       raise ValueError(f'mean_over={mean_over} does not factor {n_outer}')
@@ -1645,7 +1563,6 @@ def rank_histogram(ens: torch.Tensor, member_stride: int, n_member: int,
     out = torch.zeros((n_acc, n_point, n_bins), dtype=torch.float64,
                       device=dev)
   if numpy_stream is not None and break_ties:
-    import ctypes
     state, inc, ref_off, strides, n_col = numpy_stream
     mask = (1 << 64) - 1
     pcg = (ctypes.c_uint64 * 4)(state >> 64, state & mask, inc >> 64, inc & mask)
@@ -1752,7 +1669,6 @@ def axis_moments(x: torch.Tensor, n_lead: int, n_red: int, n_tail: int,
 # ---------------------------------------------------------------------------
 def comm_unique_id() -> bytes:
   """128-byte RCCL id made by rank 0, to be handed to every rank."""
-  import ctypes
   buf = ctypes.create_string_buffer(128)
   _lib.check(_lib.load().wb2_comm_unique_id(buf), 'wb2_comm_unique_id')
   return buf.raw
@@ -1760,7 +1676,6 @@ def comm_unique_id() -> bytes:
 
 def comm_init_rank(unique_id: bytes, n_ranks: int, rank: int):
   """ncclComm_t (opaque handle) of this rank on the current device."""
-  import ctypes
   if len(unique_id) != 128:
     raise ValueError('unique_id must be the 128 bytes of comm_unique_id()')
   handle = ctypes.c_void_p()

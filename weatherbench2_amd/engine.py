@@ -6,6 +6,7 @@ every FLOP of the hot path runs in libwb2hip.so.
 from __future__ import annotations
 
 import ctypes
+import operator
 import os
 import threading
 import typing as t
@@ -33,15 +34,31 @@ def set_launch_hook(hook):
   return old
 
 
+def hooked_call(kernel: str, fn, what: str, *args) -> None:
+  """THE hook bracket: the bound library function `fn` called between the
+  hook's 'begin' and 'end' of `kernel`; a nonzero return raises in the name of
+  `what` and sends no 'end' (a failed launch leaves the bracket open)."""
+  hook = _LAUNCH_HOOK
+  if hook is not None:
+    hook('begin', kernel)
+  status = fn(*args)
+  if status != 0:
+    _lib.check(status, what)
+  if hook is not None:
+    hook('end', kernel)
+
+
 def _launch(kernel: str, c_name: str, *args) -> None:
-  """One entry point of the library between the hook's 'begin' and 'end' of
-  `kernel`; a nonzero return raises (and leaves the bracket open, as a failed
-  launch always did)."""
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('begin', kernel)
-  _lib.check(getattr(_lib.load(), c_name)(*args), c_name)
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('end', kernel)
+  """`hooked_call` of the entry point named `c_name`."""
+  hooked_call(kernel, getattr(_lib.load(), c_name), c_name, *args)
+
+
+def dtype_code(dtype: torch.dtype) -> int:
+  """The C ABI's code (WB2_F32 / WB2_F64) of one of the kernels' dtypes."""
+  try:
+    return _DTYPES[dtype]
+  except KeyError:
+    raise TypeError(f'unsupported dtype {dtype}') from None
 
 
 def _require_float(*tensors) -> None:
@@ -57,6 +74,17 @@ def _check_slab(slab, n: int, what: str) -> None:
   """A slab table is None or `n` int64; `what` spells n in the message."""
   if slab is not None and (slab.dtype != torch.int64 or slab.numel() != n):
     raise ValueError(f'the slab table must hold {what} int64')
+
+
+def _check_contiguous(device, where: str, *tensors, view=None) -> None:
+  """The tensors are contiguous on `device` (`where` names it in the message);
+  `view` only has to live there: a strided tensor whose intact slabs the
+  caller addresses one by one."""
+  ok = view is None or view.device == device
+  for x in tensors:
+    ok = ok and x.device == device and x.is_contiguous()
+  if not ok:
+    raise ValueError(f'inputs must be contiguous on {where}')
 
 
 _I32 = ctypes.c_int32
@@ -302,8 +330,7 @@ def stream_reduce(plan: ReductionPlan, mode: int,
   """
   dev = plan.device
   dtype = inputs[0].dtype
-  if dtype not in _DTYPES:
-    raise TypeError(f'unsupported dtype {dtype}')
+  dtype_code(dtype)  # (TypeError: not one of the kernels' dtypes)
   for x in inputs:
     if x.dtype != dtype or x.device != dev or not _slabs_intact(x):
       raise ValueError('inputs must share dtype/device and keep every '
@@ -316,8 +343,7 @@ def stream_reduce(plan: ReductionPlan, mode: int,
                       x.numel() != n_outer * plan.n_row * plan.n_col):
       raise ValueError('an input without a slab table must be n_outer '
                        'contiguous slabs')
-    if s is not None and (s.dtype != torch.int64 or s.numel() != n_outer):
-      raise ValueError('slab tables are int64[n_outer]')
+    _check_slab(s, n_outer, 'n_outer')
   aligned = all(x.data_ptr() % 16 == 0 for x in inputs)
   return _stream_launch(plan, mode, dtype, n_outer, skipna, want_sums, aux,
                         scalar, aligned, inputs=inputs, slabs=slabs)
@@ -331,15 +357,6 @@ def _check_address_tables(plan, addr, n_outer):
                        'plan device')
 
 
-def _fold_args(plan, seg_eoff, n_ts):
-  """The plan's arguments of wb2_det_combine / wb2_ens_combine, between
-  `n_outer` and `sums`."""
-  return (plan.n_chunk, plan.nwf, plan.n_seg, _lib.ptr(seg_eoff), n_ts,
-          _lib.ptr(plan.band_chunk0), plan.n_band, _lib.ptr(plan.coef_band),
-          _lib.ptr(plan.coef_seg), _lib.ptr(plan.region_wf),
-          _lib.ptr(plan.region_wsum), plan.n_region)
-
-
 def stream_reduce_addr(plan: ReductionPlan, mode: int, dtype: torch.dtype,
                        addr: t.Sequence[torch.Tensor], aligned16: bool,
                        n_outer: int, skipna: bool, want_sums: bool = False,
@@ -351,69 +368,148 @@ def stream_reduce_addr(plan: ReductionPlan, mode: int, dtype: torch.dtype,
   (wb2_stream_partials_addr).  The caller keeps the memory behind the
   addresses alive until the launch has been enqueued on the current stream
   (torch's allocator is stream-ordered).  Same return value as stream_reduce."""
-  if dtype not in _DTYPES:
-    raise TypeError(f'unsupported dtype {dtype}')
+  dtype_code(dtype)  # (TypeError: not one of the kernels' dtypes)
   _check_address_tables(plan, addr, n_outer)
   return _stream_launch(plan, mode, dtype, n_outer, skipna, want_sums, aux,
                         scalar, bool(aligned16), addr=addr)
 
 
-def _stream_launch(plan, mode, dtype, n_outer, skipna, want_sums, aux, scalar,
-                   aligned, inputs=None, slabs=None, addr=None):
-  lib = _lib.load()
-  dev = plan.device
-  code = _DTYPES[dtype]
-  k = lib.wb2_num_slots(mode, int(skipna))
-  field, field_code = _suite_field(plan, dtype, mode)
-  aligned = aligned and (field is None or field.data_ptr() % 16 == 0)
-  tile = lib.wb2_tile_cols_ex(mode, code, int(skipna),
-                              int(plan.wfield is not None), plan.n_col,
-                              int(aligned))
-  n_ctile = -(-plan.n_col // tile)
-  stream = current_stream_ptr(dev)
-  seg_eoff, n_ts = plan.seg_entries(tile)
-  partials = torch.empty((n_outer, plan.n_chunk, plan.nwf, n_ts, k),
-                         dtype=torch.float64, device=dev)
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('begin', 'stream_partials')
-  tail = (n_outer, plan.n_row, plan.n_col, _lib.ptr(plan.w_row),
-          _lib.ptr(plan.w_col), _lib.ptr(field), field_code, _lib.ptr(aux),
-          float(scalar), _lib.ptr(plan.chunk_row0),
-          _lib.ptr(plan.chunk_nrow), plan.n_chunk, n_ctile,
-          _lib.ptr(plan.seg_col0), _lib.ptr(seg_eoff), plan.n_seg, n_ts,
-          _lib.ptr(partials), stream)
-  if addr is not None:
-    _lib.check(lib.wb2_stream_partials_addr(
-        mode, code, int(skipna), _lib.ptr_array(addr), int(aligned), *tail),
-               'wb2_stream_partials_addr')
-  else:
-    _lib.check(lib.wb2_stream_partials_ex(
-        mode, code, int(skipna), _lib.ptr_array(inputs), _lib.ptr_array(slabs),
-        *tail), 'wb2_stream_partials')
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('end', 'stream_partials')
-  metrics = torch.empty((_lib.GENERIC_KQ.get(mode, _lib.NMETRIC),
-                         plan.n_region, n_outer),
-                        dtype=torch.float64, device=dev)
-  sums = (torch.empty((n_outer, plan.n_region, k), dtype=torch.float64,
-                      device=dev) if want_sums else None)
-  _lib.check(lib.wb2_det_combine(
-      mode, int(skipna), _lib.ptr(partials), n_outer,
-      *_fold_args(plan, seg_eoff, n_ts), _lib.ptr(sums), _lib.ptr(metrics),
-      stream), 'wb2_det_combine')
-  return metrics, sums
+class PreparedLaunch:
+  """What every launch of a reduction over `plan` at the column-tile width
+  `tile` is made of, worked out ONCE: the segment-entry table (`seg_eoff`,
+  `n_ts`), `n_ctile` and, with a slot count `k`, the `partials` tensor
+  [n_outer, n_chunk, nwf, n_ts, k].  `values` holds every field of
+  `wb2_plan_tables` by name (and `nwf`, which C reads off `wfield`).  The
+  struct (`tables`: what `plan_tables` returns) and the plan's part of the
+  long argument lists are both read from it, so the two forms of one launch
+  cannot drift.  It keeps alive what they point at."""
+
+  _REST = ('chunk_row0', 'chunk_nrow', 'n_chunk', 'n_ctile', 'seg_col0',
+           'seg_eoff', 'n_seg', 'n_ts')
+  _STREAM = operator.itemgetter('n_row', 'n_col', 'w_row', 'w_col', 'wfield',
+                                'wfield_dtype', 'aux', 'scalar', *_REST)
+  _ENS = operator.itemgetter('n_row', 'n_col', 'w_row', 'w_col', 'wfield',
+                             *_REST)
+  _FOLD = operator.itemgetter('n_chunk', 'nwf', 'n_seg', 'seg_eoff', 'n_ts',
+                              'band_chunk0', 'n_band', 'coef_band', 'coef_seg',
+                              'region_wf', 'region_wsum', 'n_region')
+
+  def __init__(self, plan: ReductionPlan, tile: int, k: int = 0,
+               n_outer: int = 0, field=None, field_code: int = _lib.WB2_F64,
+               aux=None, scalar: float = 0.0):
+    self.plan, self.k, self.n_outer = plan, k, n_outer
+    self.seg_eoff, self.n_ts = plan.seg_entries(tile)
+    self.n_ctile = -(-plan.n_col // tile)
+    self.keep = (field, aux)
+    ptr = _lib.ptr
+    self.values = {
+        'n_row': plan.n_row, 'n_col': plan.n_col, 'n_chunk': plan.n_chunk,
+        'n_ctile': self.n_ctile, 'n_seg': plan.n_seg, 'n_ts': self.n_ts,
+        'n_band': plan.n_band, 'n_region': plan.n_region, 'nwf': plan.nwf,
+        'w_row': ptr(plan.w_row), 'w_col': ptr(plan.w_col),
+        'wfield': ptr(field), 'wfield_dtype': field_code, 'reserved': 0,
+        'aux': ptr(aux), 'scalar': float(scalar),
+        # (tables every plan has: no None to map to NULL)
+        'chunk_row0': plan.chunk_row0.data_ptr(),
+        'chunk_nrow': plan.chunk_nrow.data_ptr(),
+        'seg_col0': plan.seg_col0.data_ptr(),
+        'seg_eoff': self.seg_eoff.data_ptr(),
+        'band_chunk0': plan.band_chunk0.data_ptr(),
+        'coef_band': plan.coef_band.data_ptr(),
+        'coef_seg': plan.coef_seg.data_ptr(),
+        'region_wf': plan.region_wf.data_ptr(),
+        'region_wsum': plan.region_wsum.data_ptr()}
+    self._tables = None
+    self.partials = self.new_partials(n_outer, k) if k else None
+
+  @property
+  def tables(self) -> _lib.PlanTables:
+    if self._tables is None:
+      self._tables = _lib.PlanTables(
+          **{name: self.values[name] for name, _ in _lib.PlanTables._fields_})
+    return self._tables
+
+  def new_partials(self, n_outer: int, k: int) -> torch.Tensor:
+    v = self.values
+    return torch.empty((n_outer, v['n_chunk'], v['nwf'], self.n_ts, k),
+                       dtype=torch.float64, device=self.plan.device)
+
+  def stream_args(self) -> tuple:
+    """The plan's arguments of wb2_stream_partials_ex / _addr, between
+    `n_outer` and `partials`."""
+    return self._STREAM(self.values)
+
+  def ens_args(self) -> tuple:
+    """The plan's arguments of the ensemble partials entry points, between
+    `n_outer` and `partials`."""
+    return self._ENS(self.values)
+
+  def fold_args(self) -> tuple:
+    """The plan's arguments of wb2_det_combine / wb2_ens_combine, between
+    `n_outer` and `sums`."""
+    return self._FOLD(self.values)
+
+  def fold(self, c_name: str, head: tuple, n_metric: int, want_sums: bool,
+           stream: int):
+    """The region fold `c_name` (whose arguments begin with `head`) of the
+    partials: (metrics[n_metric, n_region, n_outer], sums[n_outer, n_region,
+    k] or None)."""
+    n_region, dev = self.values['n_region'], self.plan.device
+    metrics = torch.empty((n_metric, n_region, self.n_outer),
+                          dtype=torch.float64, device=dev)
+    sums = (torch.empty((self.n_outer, n_region, self.k), dtype=torch.float64,
+                        device=dev) if want_sums else None)
+    _lib.check(getattr(_lib.load(), c_name)(
+        *head, _lib.ptr(self.partials), self.n_outer, *self.fold_args(),
+        _lib.ptr(sums), _lib.ptr(metrics), stream), c_name)
+    return metrics, sums
 
 
-def _suite_field(plan, dtype, mode):
-  """(weight field, its dtype code) of a deterministic launch: float32 where
-  the field's values are float32 numbers and the launch has the instantiation
-  (same bits, half the field bytes per point)."""
+def plan_tables(plan: ReductionPlan, tile_cols: int, field=None,
+                field_code: int = _lib.WB2_F64, aux=None, scalar: float = 0.0):
+  """(`wb2_plan_tables` struct of `plan` for a column-tile width, what it
+  points at -- keep both alive until the call has been enqueued)."""
+  prep = PreparedLaunch(plan, tile_cols, 0, 0, field, field_code, aux, scalar)
+  return prep.tables, (field, aux, prep.seg_eoff, prep.n_ts)
+
+
+def _field_and_tile(plan, dtype, mode, skipna, aligned=True):
+  """(weight field, its dtype code, column-tile width) of a deterministic
+  launch.  The field is float32 where its values are float32 numbers and the
+  launch has the instantiation (same bits, half the field bytes per point).
+  `aligned` is the caller's flag, passed on as it is: the width does not
+  depend on it (vec_width in csrc/stream_reduce.hip), and the launch tests the
+  field's address itself."""
   field, field_code = plan.wfield, _lib.WB2_F64
   if (dtype == torch.float32 and mode in _FIELD_F32_MODES and
       getattr(plan, 'wfield32', None) is not None and
       os.environ.get('WB2HIP_FIELD_F32', '1') != '0'):
     field, field_code = plan.wfield32, _lib.WB2_F32
-  return field, field_code
+  tile = _lib.load().wb2_tile_cols_ex(
+      mode, _DTYPES[dtype], int(skipna), int(plan.wfield is not None),
+      plan.n_col, int(aligned))
+  return field, field_code, tile
+
+
+def _stream_launch(plan, mode, dtype, n_outer, skipna, want_sums, aux, scalar,
+                   aligned, inputs=None, slabs=None, addr=None):
+  lib = _lib.load()
+  code = _DTYPES[dtype]
+  field, field_code, tile = _field_and_tile(plan, dtype, mode, skipna, aligned)
+  prep = PreparedLaunch(plan, tile, lib.wb2_num_slots(mode, int(skipna)),
+                        n_outer, field, field_code, aux, scalar)
+  stream = current_stream_ptr(plan.device)
+  tail = (n_outer, *prep.stream_args(), _lib.ptr(prep.partials), stream)
+  if addr is not None:
+    hooked_call('stream_partials', lib.wb2_stream_partials_addr,
+                'wb2_stream_partials_addr', mode, code, int(skipna),
+                _lib.ptr_array(addr), int(aligned), *tail)
+  else:
+    hooked_call('stream_partials', lib.wb2_stream_partials_ex,
+                'wb2_stream_partials', mode, code, int(skipna),
+                _lib.ptr_array(inputs), _lib.ptr_array(slabs), *tail)
+  return prep.fold('wb2_det_combine', (mode, int(skipna)),
+                   _lib.GENERIC_KQ.get(mode, _lib.NMETRIC), want_sums, stream)
 
 
 def pairs_supported(plan: ReductionPlan, mode: int, dtype: torch.dtype,
@@ -423,8 +519,6 @@ def pairs_supported(plan: ReductionPlan, mode: int, dtype: torch.dtype,
   kernel off for A/B runs: the pairs then take a WB2_MODE_WIND launch)."""
   if os.environ.get('WB2HIP_WIND_PAIRS', '1') == '0' or dtype not in _DTYPES:
     return False
-  field, _ = _suite_field(plan, dtype, mode)
-  aligned = aligned and (field is None or field.data_ptr() % 16 == 0)
   return bool(_lib.load().wb2_pairs_supported(
       mode, _DTYPES[dtype], int(skipna), int(plan.wfield is not None),
       plan.n_col, int(aligned)))
@@ -459,31 +553,22 @@ class PairSuiteStep:
   def __init__(self, plan: ReductionPlan, mode: int, dtype: torch.dtype,
                skipna: bool, n_outer: int, n_pair: int, aligned: bool = True):
     lib = _lib.load()
-    if dtype not in _DTYPES:
-      raise TypeError(f'unsupported dtype {dtype}')
+    code = dtype_code(dtype)
     if mode not in (_lib.MODE_DET, _lib.MODE_DET_ACC):
       raise ValueError('wind-vector pairs ride on MODE_DET / MODE_DET_ACC')
     if not 0 <= 2 * n_pair <= n_outer:
       raise ValueError(f'{n_pair=} does not fit {n_outer=}')
     self.lib, self.plan, self.mode, self.skipna = lib, plan, mode, bool(skipna)
-    self.code, self.n_outer, self.n_pair = _DTYPES[dtype], int(n_outer), int(
-        n_pair)
+    self.code, self.n_outer, self.n_pair = code, int(n_outer), int(n_pair)
     self.aligned = bool(aligned)
-    dev = plan.device
-    field, field_code = _suite_field(plan, dtype, mode)
-    aligned = aligned and (field is None or field.data_ptr() % 16 == 0)
-    tile = lib.wb2_tile_cols_ex(mode, self.code, int(skipna),
-                                int(plan.wfield is not None), plan.n_col,
-                                int(aligned))
-    self.tables, self._keep = plan_tables(plan, tile, field, field_code)
-    n_ts = self._keep[3]
-    k = lib.wb2_num_slots(mode, int(skipna))
-    kw = lib.wb2_num_slots(_lib.MODE_WIND, int(skipna))
-    self.partials = torch.empty((n_outer, plan.n_chunk, plan.nwf, n_ts, k),
-                                dtype=torch.float64, device=dev)
-    self.wind_partials = torch.empty(
-        (max(n_pair, 1), plan.n_chunk, plan.nwf, n_ts, kw),
-        dtype=torch.float64, device=dev)
+    field, field_code, tile = _field_and_tile(plan, dtype, mode, skipna,
+                                              aligned)
+    self._prep = prep = PreparedLaunch(
+        plan, tile, lib.wb2_num_slots(mode, int(skipna)), n_outer, field,
+        field_code)
+    self.tables, self.partials = prep.tables, prep.partials
+    self.wind_partials = prep.new_partials(
+        max(n_pair, 1), lib.wb2_num_slots(_lib.MODE_WIND, int(skipna)))
     self._tables_ref = ctypes.byref(self.tables)
     self._fn = lib.wb2_det_wind_suite_step
     self.n_metric = _lib.NMETRIC
@@ -497,20 +582,14 @@ class PairSuiteStep:
     if out is None:
       out = torch.empty((self.n_values,), dtype=torch.float64, device=dev)
     n_det = _lib.NMETRIC * self.plan.n_region * self.n_outer
-    hook = _LAUNCH_HOOK
-    if hook is not None:
-      hook('begin', 'stream_partials')
-    status = self._fn(
+    hooked_call(
+        'stream_partials', self._fn, 'wb2_det_wind_suite_step',
         self._tables_ref, self.mode, self.code, int(self.skipna),
         None if inputs is None else _lib.ptr_array(inputs),
         _lib.ptr_array(tables), int(self.aligned), self.n_outer, self.n_pair,
         self.partials.data_ptr(), self.wind_partials.data_ptr(),
         out.data_ptr(), out.data_ptr() + 8 * n_det,
         current_stream_ptr(dev) if stream_ptr is None else stream_ptr)
-    if hook is not None:
-      hook('end', 'stream_partials')
-    if status != 0:
-      _lib.check(status, 'wb2_det_wind_suite_step')
     flat = out.view(-1)
     return (flat[:n_det].view(_lib.NMETRIC, self.plan.n_region, self.n_outer),
             flat[n_det:n_det + _lib.NMETRIC * self.plan.n_region * self.n_pair]
@@ -538,30 +617,18 @@ class SuiteStep:
                aux: t.Optional[torch.Tensor] = None, scalar: float = 0.0,
                by_address: bool = False):
     lib = _lib.load()
-    if dtype not in _DTYPES:
-      raise TypeError(f'unsupported dtype {dtype}')
+    self.code, self.n_outer = dtype_code(dtype), int(n_outer)
     self.lib, self.plan, self.mode, self.skipna = lib, plan, mode, bool(skipna)
-    self.code, self.n_outer = _DTYPES[dtype], int(n_outer)
     self.by_address, self.aligned = bool(by_address), bool(aligned)
-    dev = plan.device
-    k = lib.wb2_num_slots(mode, int(skipna))
-    field, field_code = plan.wfield, _lib.WB2_F64
-    if (dtype == torch.float32 and mode in _FIELD_F32_MODES and
-        getattr(plan, 'wfield32', None) is not None and
-        os.environ.get('WB2HIP_FIELD_F32', '1') != '0'):
-      field, field_code = plan.wfield32, _lib.WB2_F32
-    aligned = aligned and (field is None or field.data_ptr() % 16 == 0)
-    tile = lib.wb2_tile_cols_ex(mode, self.code, int(skipna),
-                                int(plan.wfield is not None), plan.n_col,
-                                int(aligned))
-    self.tables, self._keep = plan_tables(plan, tile, field, field_code, aux,
-                                          scalar)
-    n_ts = self._keep[3]
+    field, field_code, tile = _field_and_tile(plan, dtype, mode, skipna,
+                                              aligned)
+    self._prep = prep = PreparedLaunch(
+        plan, tile, lib.wb2_num_slots(mode, int(skipna)), n_outer, field,
+        field_code, aux, scalar)
+    self.tables, self.partials = prep.tables, prep.partials
     self.n_metric = _lib.GENERIC_KQ.get(mode, _lib.NMETRIC)
-    self.partials = torch.empty((n_outer, plan.n_chunk, plan.nwf, n_ts, k),
-                                dtype=torch.float64, device=dev)
     self.metrics = torch.empty((self.n_metric, plan.n_region, n_outer),
-                               dtype=torch.float64, device=dev)
+                               dtype=torch.float64, device=plan.device)
     self._tables_ref = ctypes.byref(self.tables)
     self._acc = (0, 0, 0, 0, None, None, None)
     self._acc_keep = None
@@ -604,20 +671,14 @@ class SuiteStep:
     out = self.metrics if metrics is None else metrics
     if self.by_address != (inputs is None):
       raise ValueError('by_address steps take inputs=None and address tables')
-    hook = _LAUNCH_HOOK
-    if hook is not None:  # (brackets K1 + K2 [+ the accumulation] here)
-      hook('begin', 'stream_partials')
-    status = self._fn(
+    hooked_call(  # (brackets K1 + K2 [+ the accumulation] here)
+        'stream_partials', self._fn, 'wb2_det_suite_step',
         self._tables_ref, self.mode, self.code, int(self.skipna),
         None if inputs is None else _lib.ptr_array(inputs),
         _lib.ptr_array(tables), int(self.aligned), self.n_outer,
         self.partials.data_ptr(), out.data_ptr(), *self._acc,
         current_stream_ptr(self.plan.device) if stream_ptr is None
         else stream_ptr)
-    if hook is not None:
-      hook('end', 'stream_partials')
-    if status != 0:
-      _lib.check(status, 'wb2_det_suite_step')
     return out
 
   def bind(self, inputs, tables, stream_ptr: t.Optional[int] = None):
@@ -679,15 +740,6 @@ def gather_pointers(base: torch.Tensor, index: np.ndarray, slab_elems: int):
   return ptrs
 
 
-def _ens_plan_args(plan, seg_eoff, n_ts, n_ctile):
-  """The plan's arguments of the ensemble partials entry points, between
-  `n_outer` and `partials`."""
-  return (plan.n_row, plan.n_col, _lib.ptr(plan.w_row), _lib.ptr(plan.w_col),
-          _lib.ptr(plan.wfield), _lib.ptr(plan.chunk_row0),
-          _lib.ptr(plan.chunk_nrow), plan.n_chunk, n_ctile,
-          _lib.ptr(plan.seg_col0), _lib.ptr(seg_eoff), plan.n_seg, n_ts)
-
-
 def ensemble_reduce(plan: ReductionPlan, ens: torch.Tensor,
                     member_stride: int, n_member: int,
                     ens_slab: t.Optional[torch.Tensor], truth: torch.Tensor,
@@ -712,90 +764,53 @@ def ensemble_reduce(plan: ReductionPlan, ens: torch.Tensor,
   """
   lib = _lib.load()
   dev = plan.device
-  dtype = ens.dtype
-  if dtype not in _DTYPES or truth.dtype != dtype:
-    raise TypeError(f'unsupported / mismatched dtypes {ens.dtype} {truth.dtype}')
-  # (a non-contiguous `ens` is a view with intact slabs that the caller
-  # addresses through member_stride + ens_slab: metrics._ens_layout)
+  _require_float(ens, truth)
+  code = _DTYPES[ens.dtype]
   if addresses is not None:
     if (addresses.dtype != torch.int64 or addresses.device != dev or
         not addresses.is_contiguous() or addresses.numel() != 2 * n_outer or
         maps is not None or member_ptrs is not None):
       raise ValueError('addresses is a contiguous int64[2, n_outer] on the '
                        'plan device (no maps, no member_ptrs)')
-  elif ens.device != dev or truth.device != dev or not truth.is_contiguous() or (
-      not ens.is_contiguous() and ens_slab is None and member_ptrs is None):
-    raise ValueError('inputs must be contiguous on the plan device')
+  else:
+    # (a non-contiguous `ens` is a view with intact slabs that the caller
+    # addresses through member_stride + ens_slab: metrics._ens_layout)
+    addressed = ens_slab is not None or member_ptrs is not None
+    _check_contiguous(dev, 'the plan device', truth,
+                      *([] if addressed else [ens]), view=ens)
   for s in (ens_slab, truth_slab):
-    if s is not None and (s.dtype != torch.int64 or s.numel() != n_outer):
-      raise ValueError('slab tables are int64[n_outer]')
+    _check_slab(s, n_outer, 'n_outer')
   if member_ptrs is not None and (
       member_ptrs.dtype != torch.int64 or member_ptrs.device != dev or
       not member_ptrs.is_contiguous() or
       member_ptrs.numel() != n_outer * n_member):
     raise ValueError('member_ptrs is a contiguous int64[n_outer, n_member] '
                      'on the plan device')
-  k = lib.wb2_ens_num_slots(int(skipna))
-  tile = lib.wb2_ens_tile_cols(plan.n_col)
-  n_ctile = -(-plan.n_col // tile)
-  seg_eoff, n_ts = plan.seg_entries(tile)
-  stream = current_stream_ptr(dev)
-  partials = torch.empty((n_outer, plan.n_chunk, plan.nwf, n_ts, k),
-                         dtype=torch.float64, device=dev)
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('begin', 'ens_partials')
   if maps is not None and (maps.dtype != torch.float64 or maps.numel() !=
                            6 * n_outer * plan.n_row * plan.n_col):
     raise ValueError('maps must be float64[6, n_outer, n_row * n_col]')
-  tail = (n_outer, *_ens_plan_args(plan, seg_eoff, n_ts, n_ctile),
-          _lib.ptr(partials))
+  prep = PreparedLaunch(plan, lib.wb2_ens_tile_cols(plan.n_col),
+                        lib.wb2_ens_num_slots(int(skipna)), n_outer,
+                        plan.wfield)
+  stream = current_stream_ptr(dev)
+  tail = (n_outer, *prep.ens_args(), _lib.ptr(prep.partials))
   if addresses is not None:
     base = addresses.data_ptr()
-    _lib.check(lib.wb2_ens_partials_addr(
-        _DTYPES[dtype], int(skipna), base, base + 8 * n_outer, n_member,
-        member_stride, *tail, stream), 'wb2_ens_partials_addr')
+    hooked_call('ens_partials', lib.wb2_ens_partials_addr,
+                'wb2_ens_partials_addr', code, int(skipna), base,
+                base + 8 * n_outer, n_member, member_stride, *tail, stream)
   elif member_ptrs is not None:
-    _lib.check(lib.wb2_ens_partials_gather(
-        _DTYPES[dtype], int(skipna), _lib.ptr(member_ptrs), _lib.ptr(truth),
-        _lib.ptr(truth_slab), n_member, *tail, _lib.ptr(maps), stream),
-               'wb2_ens_partials_gather')
+    hooked_call('ens_partials', lib.wb2_ens_partials_gather,
+                'wb2_ens_partials_gather', code, int(skipna),
+                _lib.ptr(member_ptrs), _lib.ptr(truth), _lib.ptr(truth_slab),
+                n_member, *tail, _lib.ptr(maps), stream)
   else:
-    _lib.check(lib.wb2_ens_partials_maps(
-        _DTYPES[dtype], int(skipna), _lib.ptr(ens), _lib.ptr(ens_slab),
-        _lib.ptr(truth), _lib.ptr(truth_slab), n_member, member_stride, *tail,
-        _lib.ptr(maps), stream), 'wb2_ens_partials_maps')
-  if _LAUNCH_HOOK is not None:
-    _LAUNCH_HOOK('end', 'ens_partials')
-  metrics = torch.empty((_lib.NMETRIC_ENS, plan.n_region, n_outer),
-                        dtype=torch.float64, device=dev)
-  sums = (torch.empty((n_outer, plan.n_region, k), dtype=torch.float64,
-                      device=dev) if want_sums else None)
-  _lib.check(lib.wb2_ens_combine(
-      int(skipna), _lib.ptr(partials), n_outer,
-      *_fold_args(plan, seg_eoff, n_ts), _lib.ptr(sums), _lib.ptr(metrics),
-      stream), 'wb2_ens_combine')
-  return metrics, sums
-
-
-def plan_tables(plan: ReductionPlan, tile_cols: int, field=None,
-                field_code: int = _lib.WB2_F64, aux=None, scalar: float = 0.0):
-  """(`wb2_plan_tables` struct of `plan` for a column-tile width, what it
-  points at -- keep both alive until the call has been enqueued)."""
-  seg_eoff, n_ts = plan.seg_entries(tile_cols)
-  tables = _lib.PlanTables(
-      n_row=plan.n_row, n_col=plan.n_col, n_chunk=plan.n_chunk,
-      n_ctile=-(-plan.n_col // tile_cols), n_seg=plan.n_seg, n_ts=n_ts,
-      n_band=plan.n_band, n_region=plan.n_region,
-      w_row=_lib.ptr(plan.w_row) or None, w_col=_lib.ptr(plan.w_col) or None,
-      wfield=_lib.ptr(field) or None, wfield_dtype=field_code, reserved=0,
-      aux=_lib.ptr(aux) or None, scalar=float(scalar),
-      chunk_row0=_lib.ptr(plan.chunk_row0), chunk_nrow=_lib.ptr(plan.chunk_nrow),
-      seg_col0=_lib.ptr(plan.seg_col0), seg_eoff=_lib.ptr(seg_eoff),
-      band_chunk0=_lib.ptr(plan.band_chunk0),
-      coef_band=_lib.ptr(plan.coef_band), coef_seg=_lib.ptr(plan.coef_seg),
-      region_wf=_lib.ptr(plan.region_wf),
-      region_wsum=_lib.ptr(plan.region_wsum))
-  return tables, (field, aux, seg_eoff, n_ts)
+    hooked_call('ens_partials', lib.wb2_ens_partials_maps,
+                'wb2_ens_partials_maps', code, int(skipna), _lib.ptr(ens),
+                _lib.ptr(ens_slab), _lib.ptr(truth), _lib.ptr(truth_slab),
+                n_member, member_stride, *tail, _lib.ptr(maps), stream)
+  return prep.fold('wb2_ens_combine', (int(skipna),), _lib.NMETRIC_ENS,
+                   want_sums, stream)
 
 
 def energy_score(plan: ReductionPlan, ens: torch.Tensor, member_stride: int,
@@ -805,39 +820,29 @@ def energy_score(plan: ReductionPlan, ens: torch.Tensor, member_stride: int,
   """wb2_energy_score: (score, spread, skill)[3, n_region, n_outer] float64 of
   a member-major ensemble (`member_stride` elements between members) in one
   read of the members.  Asynchronous on the current stream."""
-  lib = _lib.load()
   dev = plan.device
-  dtype = ens.dtype
-  if dtype not in _DTYPES or truth.dtype != dtype:
-    raise TypeError(f'unsupported / mismatched dtypes {ens.dtype} {truth.dtype}')
+  _require_float(ens, truth)
   # (a non-contiguous `ens` is a view with intact slabs that the caller
   # addresses through member_stride + ens_slab: metrics._ens_layout)
-  if ens.device != dev or truth.device != dev or not truth.is_contiguous() or (
-      not ens.is_contiguous() and ens_slab is None):
-    raise ValueError('inputs must be contiguous on the plan device')
+  _check_contiguous(dev, 'the plan device', truth,
+                    *([ens] if ens_slab is None else []), view=ens)
   for s in (ens_slab, truth_slab):
-    if s is not None and (s.dtype != torch.int64 or s.numel() != n_outer):
-      raise ValueError('slab tables are int64[n_outer]')
-  block, n_block, k = (ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32())
-  _lib.check(lib.wb2_energy_layout(
-      n_member, int(skipna), int(plan.wfield is not None), ctypes.byref(block),
-      ctypes.byref(n_block), ctypes.byref(k)), 'wb2_energy_layout')
-  tables, keep = plan_tables(plan, lib.wb2_ens_tile_cols(plan.n_col),
-                             plan.wfield)
-  n_ts = keep[3]
-  n_virtual = n_outer * n_block.value
-  partials = torch.empty((n_virtual, plan.n_chunk, plan.nwf, n_ts, k.value),
-                         dtype=torch.float64, device=dev)
-  means = torch.empty((2 * block.value, plan.n_region, n_virtual),
+    _check_slab(s, n_outer, 'n_outer')
+  g = _geometry('wb2_energy_layout',
+                (n_member, int(skipna), int(plan.wfield is not None)),
+                [('block', _I32), ('n_block', _I32), ('k', _I32)])
+  n_virtual = n_outer * g['n_block']
+  prep = PreparedLaunch(plan, _lib.load().wb2_ens_tile_cols(plan.n_col),
+                        g['k'], n_virtual, plan.wfield)
+  means = torch.empty((2 * g['block'], plan.n_region, n_virtual),
                       dtype=torch.float64, device=dev)
   out = torch.empty((3, plan.n_region, n_outer), dtype=torch.float64,
                     device=dev)
-  _launch('energy_score', 'wb2_energy_score', _DTYPES[dtype], int(skipna),
+  _launch('energy_score', 'wb2_energy_score', _DTYPES[ens.dtype], int(skipna),
           _lib.ptr(ens), _lib.ptr(ens_slab), _lib.ptr(truth),
           _lib.ptr(truth_slab), n_member, member_stride, n_outer,
-          ctypes.byref(tables), _lib.ptr(partials), _lib.ptr(means),
+          ctypes.byref(prep.tables), _lib.ptr(prep.partials), _lib.ptr(means),
           _lib.ptr(out), current_stream_ptr(dev))
-  del keep
   return out
 
 
@@ -1002,8 +1007,7 @@ def spatial_maps(forecast: torch.Tensor, f_slab, truth: torch.Tensor, t_slab,
   """K5 per-time maps: returns {name: tensor[n_outer, n_point]} (input dtype)."""
   lib = _lib.load()
   dev = forecast.device
-  if forecast.dtype not in _DTYPES or truth.dtype != forecast.dtype:
-    raise TypeError('forecast/truth must share a float32/float64 dtype')
+  _require_float(forecast, truth)
   outs = {k: torch.empty((n_outer, n_point), dtype=forecast.dtype, device=dev)
           for k in want}
   _lib.check(lib.wb2_spatial_maps(
@@ -1020,8 +1024,7 @@ def spatial_accumulate(forecast: torch.Tensor, f_slab, truth: torch.Tensor,
                        count: t.Optional[torch.Tensor]):
   """K5 temporal accumulation into total/count [3, n_rest, n_point] (fp64)."""
   lib = _lib.load()
-  if forecast.dtype not in _DTYPES or truth.dtype != forecast.dtype:
-    raise TypeError('forecast/truth must share a float32/float64 dtype')
+  _require_float(forecast, truth)
   _lib.check(lib.wb2_spatial_accumulate(
       _DTYPES[forecast.dtype], int(skipna), _lib.ptr(forecast),
       _lib.ptr(f_slab), _lib.ptr(truth), _lib.ptr(t_slab), n_time, n_rest,
@@ -1476,35 +1479,20 @@ def ensemble_threshold_reduce(plan: ReductionPlan, ens: torch.Tensor,
   (Brier, debiased Brier, ignorance, RPS part).  With `want_sums`: (metrics,
   the raw region sums [n_outer, n_region, K])."""
   lib = _lib.load()
-  dev = plan.device
-  dtype = ens.dtype
-  if dtype not in _DTYPES or truth.dtype != dtype or thr.dtype != dtype:
-    raise TypeError('members, truth and threshold must share one dtype')
-  for x in (ens, truth, thr):
-    if x.device != dev or not x.is_contiguous():
-      raise ValueError('inputs must be contiguous on the plan device')
+  _require_float(ens, truth, thr)
+  _check_contiguous(plan.device, 'the plan device', ens, truth, thr)
   mode = _lib.MODE_ENS_THR
-  k = lib.wb2_num_slots(mode, int(skipna))
-  tile = lib.wb2_ens_tile_cols(plan.n_col)
-  n_ctile = -(-plan.n_col // tile)
-  seg_eoff, n_ts = plan.seg_entries(tile)
-  stream = current_stream_ptr(dev)
-  partials = torch.empty((n_outer, plan.n_chunk, plan.nwf, n_ts, k),
-                         dtype=torch.float64, device=dev)
+  prep = PreparedLaunch(plan, lib.wb2_ens_tile_cols(plan.n_col),
+                        lib.wb2_num_slots(mode, int(skipna)), n_outer,
+                        plan.wfield)
+  stream = current_stream_ptr(plan.device)
   _lib.check(lib.wb2_ens_threshold_partials(
-      _DTYPES[dtype], int(skipna), _lib.ptr(ens), _lib.ptr(ens_slab),
+      _DTYPES[ens.dtype], int(skipna), _lib.ptr(ens), _lib.ptr(ens_slab),
       _lib.ptr(truth), _lib.ptr(truth_slab), _lib.ptr(thr), _lib.ptr(thr_slab),
-      n_member, member_stride, n_outer,
-      *_ens_plan_args(plan, seg_eoff, n_ts, n_ctile), _lib.ptr(partials),
-      stream), 'wb2_ens_threshold_partials')
-  metrics = torch.empty((_lib.GENERIC_KQ[mode], plan.n_region, n_outer),
-                        dtype=torch.float64, device=dev)
-  sums = (torch.empty((n_outer, plan.n_region, k), dtype=torch.float64,
-                      device=dev) if want_sums else None)
-  _lib.check(lib.wb2_det_combine(
-      mode, int(skipna), _lib.ptr(partials), n_outer,
-      *_fold_args(plan, seg_eoff, n_ts), _lib.ptr(sums), _lib.ptr(metrics),
-      stream), 'wb2_det_combine')
+      n_member, member_stride, n_outer, *prep.ens_args(),
+      _lib.ptr(prep.partials), stream), 'wb2_ens_threshold_partials')
+  metrics, sums = prep.fold('wb2_det_combine', (mode, int(skipna)),
+                            _lib.GENERIC_KQ[mode], want_sums, stream)
   return (metrics, sums) if want_sums else metrics
 
 
@@ -1528,27 +1516,24 @@ def rank_histogram(ens: torch.Tensor, member_stride: int, n_member: int,
   np.random.default_rng(seed).uniform hands the reference."""
   lib = _lib.load()
   dev = ens.device
-  if ens.dtype not in _DTYPES or truth.dtype != ens.dtype:
-    raise TypeError('members and truth must share a float32/float64 dtype')
-  for x in (ens, truth):
-    if x.device != dev or not x.is_contiguous():
-      raise ValueError('inputs must be contiguous on one device')
+  _require_float(ens, truth)
+  _check_contiguous(dev, 'one device', ens, truth)
   if mean_over is not None:
     n_lead, n_time, n_tail = (int(v) for v in mean_over)
     if n_lead * n_time * n_tail != n_outer or n_time < 1:
       raise ValueError(f'mean_over={mean_over} does not factor {n_outer}')
+  pcg = st = ref_off = None
+  n_col = 1
+  if numpy_stream is not None and break_ties:
+    state, inc, ref_off, strides, n_col = numpy_stream
+    mask = (1 << 64) - 1
+    pcg = (ctypes.c_uint64 * 4)(state >> 64, state & mask, inc >> 64, inc & mask)
+    st = (ctypes.c_int64 * 3)(*[int(v) for v in strides])
+    if ref_off.dtype != torch.int64 or ref_off.numel() != n_outer:
+      raise ValueError('ref_outer_off must be int64[n_outer]')
+  if mean_over is not None:
     out = torch.empty((n_lead * n_tail, n_point, n_bins), dtype=torch.float64,
                       device=dev)
-    pcg = st = ref_off = None
-    n_col = 1
-    if numpy_stream is not None and break_ties:
-      state, inc, ref_off, strides, n_col = numpy_stream
-      mask = (1 << 64) - 1
-      pcg = (ctypes.c_uint64 * 4)(state >> 64, state & mask, inc >> 64,
-                                  inc & mask)
-      st = (ctypes.c_int64 * 3)(*[int(v) for v in strides])
-      if ref_off.dtype != torch.int64 or ref_off.numel() != n_outer:
-        raise ValueError('ref_outer_off must be int64[n_outer]')
     _lib.check(lib.wb2_rank_histogram_mean(
         _DTYPES[ens.dtype], _lib.ptr(ens), _lib.ptr(ens_slab), _lib.ptr(truth),
         _lib.ptr(truth_slab), n_member, member_stride, n_lead, n_time, n_tail,
@@ -1562,13 +1547,7 @@ def rank_histogram(ens: torch.Tensor, member_stride: int, n_member: int,
   else:
     out = torch.zeros((n_acc, n_point, n_bins), dtype=torch.float64,
                       device=dev)
-  if numpy_stream is not None and break_ties:
-    state, inc, ref_off, strides, n_col = numpy_stream
-    mask = (1 << 64) - 1
-    pcg = (ctypes.c_uint64 * 4)(state >> 64, state & mask, inc >> 64, inc & mask)
-    st = (ctypes.c_int64 * 3)(*[int(v) for v in strides])
-    if ref_off.dtype != torch.int64 or ref_off.numel() != n_outer:
-      raise ValueError('ref_outer_off must be int64[n_outer]')
+  if pcg is not None:
     _lib.check(lib.wb2_rank_histogram_seeded(
         _DTYPES[ens.dtype], _lib.ptr(ens), _lib.ptr(ens_slab), _lib.ptr(truth),
         _lib.ptr(truth_slab), n_member, member_stride, n_outer, n_point,
@@ -1592,12 +1571,8 @@ def ensemble_threshold_maps(ens: torch.Tensor, member_stride: int,
   Brier, ignorance, RPS part), unreduced."""
   lib = _lib.load()
   dev = ens.device
-  if ens.dtype not in _DTYPES or truth.dtype != ens.dtype or (
-      thr.dtype != ens.dtype):
-    raise TypeError('members, truth and threshold must share one dtype')
-  for x in (ens, truth, thr):
-    if x.device != dev or not x.is_contiguous():
-      raise ValueError('inputs must be contiguous on one device')
+  _require_float(ens, truth, thr)
+  _check_contiguous(dev, 'one device', ens, truth, thr)
   maps = torch.empty((4, n_outer, n_point), dtype=torch.float64, device=dev)
   _lib.check(lib.wb2_ens_threshold_maps(
       _DTYPES[ens.dtype], int(skipna), _lib.ptr(ens), _lib.ptr(ens_slab),
@@ -1614,11 +1589,10 @@ def seeps_map(inputs: t.Sequence[torch.Tensor],
   lib = _lib.load()
   dev = inputs[0].device
   dtype = inputs[0].dtype
-  if dtype not in _DTYPES:
-    raise TypeError(f'unsupported dtype {dtype}')
-  for x in inputs:
-    if x.dtype != dtype or x.device != dev or not x.is_contiguous():
-      raise ValueError('inputs must share dtype/device and be contiguous')
+  dtype_code(dtype)  # (TypeError: not one of the kernels' dtypes)
+  if any(x.dtype != dtype for x in inputs):
+    raise ValueError('inputs must share dtype/device and be contiguous')
+  _check_contiguous(dev, 'one device', *inputs)
   if aux.dtype != torch.float64 or aux.numel() != n_point:
     raise ValueError('aux must be float64[n_point]')
   out = torch.empty((n_outer, n_point), dtype=torch.float64, device=dev)

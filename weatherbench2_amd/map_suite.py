@@ -272,17 +272,12 @@ class MapSuite:
           device, cache=False)
       n = n_time * n_dst
       base = table.data_ptr()
-      hook = engine._LAUNCH_HOOK
-      if hook is not None:
-        hook('begin', 'spatial_accumulate')
-      status = self._lib.wb2_spatial_accumulate_addr(
-          engine._DTYPES[dtype], int(self.skipna), int(aligned), base,
-          base + 8 * n, n_time, n_dst, n_point, base + 16 * n,
+      engine.hooked_call(
+          'spatial_accumulate', self._lib.wb2_spatial_accumulate_addr,
+          'wb2_spatial_accumulate_addr', engine.dtype_code(dtype),
+          int(self.skipna), int(aligned), base, base + 8 * n, n_time, n_dst,
+          n_point, base + 16 * n,
           (base + 16 * n + 24 * n_dst) if self.skipna else None, stream)
-      if status != 0:
-        _lib.check(status, 'wb2_spatial_accumulate_addr')
-      if hook is not None:
-        hook('end', 'spatial_accumulate')
     self._keep = None  # the launches are enqueued: the allocator orders reuse
 
 
@@ -313,9 +308,9 @@ class _FastSeeps:
     for x in (fdata, tdata, wdata):
       if not (isinstance(x, torch.Tensor) and x.is_cuda and x.is_contiguous()):
         raise ValueError('an input is not a contiguous device tensor')
-    if not (fdata.dtype == tdata.dtype == wdata.dtype) or (
-        fdata.dtype not in engine._DTYPES):
+    if not (fdata.dtype == tdata.dtype == wdata.dtype):
       raise ValueError('inputs differ in dtype')
+    self.code = engine.dtype_code(fdata.dtype)  # (TypeError: no such kernel)
     if fdata is not f[name].data or tdata is not t_[name].data:
       raise ValueError('the pass read a copy of the chunk')
     climatology = xl.as_dataset(metric.climatology)
@@ -324,7 +319,6 @@ class _FastSeeps:
     self.gather = gm._climatology_gather(climatology, wvar, f, geo, wrest)
     self.suite, self.name, self.m = suite, name, m
     self.layouts = (_layout(fdata), _layout(tdata))
-    self.code = engine._DTYPES[fdata.dtype]
     self.n_outer = geo.n_outer
     self.n_point = int(fdata.shape[-2]) * int(fdata.shape[-1])
     self.slab_bytes = self.n_point * fdata.element_size()

@@ -355,34 +355,24 @@ class _EnsPass:
   index are `slot` / `rel` [2][n_total] -- pointer source and byte offset, as
   for `_Launch`.  Subclasses fill them."""
 
-  def _setup(self, pl, skipna, dtype, n_member, member_stride, n_total,
-             device):
+  def _setup(self, pl, skipna, dtype, n_member, member_stride, n_total):
     self.plan, self.skipna, self.dtype = pl, bool(skipna), dtype
     self.n_member, self.member_stride = int(n_member), int(member_stride)
     self.n_total = int(n_total)
     self.n_metric = _lib.NMETRIC_ENS
     self.n_values = self.n_metric * pl.n_region * self.n_total
     lib = self._lib = _lib.load()
-    k = lib.wb2_ens_num_slots(int(self.skipna))
-    tile = lib.wb2_ens_tile_cols(pl.n_col)
-    n_ctile = -(-pl.n_col // tile)
-    seg_eoff, n_ts = pl.seg_entries(tile)
-    self.partials = torch.empty((self.n_total, pl.n_chunk, pl.nwf, n_ts, k),
-                                dtype=torch.float64, device=device)
-    self.keep = (seg_eoff, pl)
-    ptr = _lib.ptr
+    prep = self.prepared = engine.PreparedLaunch(
+        pl, lib.wb2_ens_tile_cols(pl.n_col),
+        lib.wb2_ens_num_slots(int(self.skipna)), self.n_total, pl.wfield)
+    self.partials = prep.partials
     # (dtype, skipna, ens addresses, truth addresses, ...)
     self.partials_args = [
-        engine._DTYPES[dtype], int(self.skipna), None, None, self.n_member,
-        self.member_stride, self.n_total, pl.n_row, pl.n_col, ptr(pl.w_row),
-        ptr(pl.w_col), ptr(pl.wfield), ptr(pl.chunk_row0), ptr(pl.chunk_nrow),
-        pl.n_chunk, n_ctile, ptr(pl.seg_col0), ptr(seg_eoff), pl.n_seg, n_ts,
-        ptr(self.partials)]
-    self.combine_args = [
-        int(self.skipna), ptr(self.partials), self.n_total, pl.n_chunk, pl.nwf,
-        pl.n_seg, ptr(seg_eoff), n_ts, ptr(pl.band_chunk0), pl.n_band,
-        ptr(pl.coef_band), ptr(pl.coef_seg), ptr(pl.region_wf),
-        ptr(pl.region_wsum), pl.n_region, None]
+        engine.dtype_code(dtype), int(self.skipna), None, None, self.n_member,
+        self.member_stride, self.n_total, *prep.ens_args(),
+        _lib.ptr(self.partials)]
+    self.combine_args = [int(self.skipna), _lib.ptr(self.partials),
+                         self.n_total, *prep.fold_args(), None]
 
   def fuse_key(self):
     return (id(self.plan), self.skipna, self.n_member, self.member_stride,
@@ -398,14 +388,8 @@ class _EnsPass:
     args[2] = base
     args[3] = base + 8 * self.n_total
     lib = self._lib
-    hook = engine._LAUNCH_HOOK
-    if hook is not None:
-      hook('begin', 'ens_partials')
-    status = lib.wb2_ens_partials_addr(*args, stream)
-    if status != 0:
-      _lib.check(status, 'wb2_ens_partials_addr')
-    if hook is not None:
-      hook('end', 'ens_partials')
+    engine.hooked_call('ens_partials', lib.wb2_ens_partials_addr,
+                       'wb2_ens_partials_addr', *args, stream)
     status = lib.wb2_ens_combine(*self.combine_args, out.data_ptr(), stream)
     if status != 0:
       _lib.check(status, 'wb2_ens_combine')
@@ -478,7 +462,7 @@ class _EnsLaunch(_EnsPass):
         self.rel[1] = addr - tdata.data_ptr()
         self.slot[1] = whole(*role_t)
     self._setup(pl, rec['skipna'], dtype, rec['n_member'],
-                rec['member_stride'], n, device)
+                rec['member_stride'], n)
 
 
 class _EnsFused(_EnsPass):
@@ -507,7 +491,7 @@ class _EnsFused(_EnsPass):
     self.slot = np.concatenate(slots, axis=1)
     self.rel = np.concatenate([la.rel for la in singles], axis=1)
     self._setup(first.plan, first.skipna, first.dtype, first.n_member,
-                first.member_stride, sum(self.counts), device)
+                first.member_stride, sum(self.counts))
 
   def perm(self) -> np.ndarray:
     """Element of the separate passes' output blocks (one after the other) ->
@@ -792,15 +776,12 @@ class _Native:
                          dtype=np.int32)
         slot = np.ascontiguousarray(remap[la.slot], dtype=np.int32)
         rel = np.ascontiguousarray(la.rel, dtype=np.int64)
-        pl = la.plan
-        tables, held = engine.plan_tables(
-            pl, lib.wb2_ens_tile_cols(pl.n_col), field=pl.wfield)
         _lib.check(lib.wb2_program_add_ens_launch(
-            handle, ctypes.byref(tables), engine._DTYPES[la.dtype],
-            int(la.skipna), la.n_member, la.member_stride, la.n_total,
-            slot.ctypes.data, rel.ctypes.data, la.partials.data_ptr(), off),
-                   'wb2_program_add_ens_launch')
-        keep.append((la, tables, held))
+            handle, ctypes.byref(la.prepared.tables),
+            engine.dtype_code(la.dtype), int(la.skipna), la.n_member,
+            la.member_stride, la.n_total, slot.ctypes.data, rel.ctypes.data,
+            la.partials.data_ptr(), off), 'wb2_program_add_ens_launch')
+        keep.append(la)
         off += la.n_values
         continue
       remap = np.array([source(k, g) for k, g in zip(la.source_keys,
@@ -932,18 +913,12 @@ class _Native:
         d_sum, d_cnt = group._accumulator_tables(mean, labels)
         # (the program was built for this sink's NaN rule)
       args[k, 0], args[k, 1] = d_sum.data_ptr(), d_cnt.data_ptr()
-    hook = engine._LAUNCH_HOOK
-    if hook is not None:   # (brackets every launch of the chunk + the sinks)
-      hook('begin', 'stream_partials')
-    status = self._replay(
+    engine.hooked_call(  # (brackets every launch of the chunk + the sinks)
+        'stream_partials', self._replay, 'wb2_program_replay',
         self._handle, self._ptrs_at, self.n_ptrs, values.ctypes.data,
         self.n_values, self._sink_at,
         None if rows is None else rows.ctypes.data,
         0 if rows is None else rows.size, stream)
-    if hook is not None:
-      hook('end', 'stream_partials')
-    if status != 0:
-      _lib.check(status, 'wb2_program_replay')
 
 
 class ChunkProgram:

@@ -1385,6 +1385,78 @@ int wb2_cycle_smooth(int mode, const double* count, const double* sum,
 int wb2_climatology_geometry(int dtype, int wide, int32_t* tile_points,
                              int32_t* members_ahead, int32_t* max_grid_outer);
 
+/*
+ * K15: weighted quantiles and SEEPS thresholds over the rolling day-of-year
+ * window (scripts/compute_climatology.py:130-216: the `quantile` and `seeps`
+ * statistics, through weatherbench2/utils.py:88-124 with a callable stat_fn).
+ *
+ * Semantics, per (outer, cycle c, position a, point), groups g = c * n_pos + a
+ * as in K14 (member, fill, absent samples and the slab table alike): the
+ * samples of a are X[y, (a + k) mod n_pos], k = -H .. H, H = n_w / 2, sample
+ * (k, y) with the integer weight m[k + H] (the reference's window weights are
+ * proportional to H - |k|; xarray's weighted quantile normalises them, so the
+ * scale is free).  H >= n_pos is legal: the window wraps, a position then
+ * enters once per k.
+ *   dry       with use_dry != 0, t = T(dry_threshold): a sample x < t, compared
+ *             in T, is dry.  dry_fraction = (dry samples of the window, weight
+ *             zero included) / denominator; a NaN sample is not dry.
+ *   kept      samples that are not NaN, not dry and have m > 0.  M = S m and
+ *             Q = S m^2 over them (exact integers); M == 0 gives NaN.
+ *   quantile  xarray's _weighted_quantile_1d, method 'linear', skipna: with
+ *             n = M M / Q, h = (n - 1) q + 1, A = (h - 1) / n M and
+ *             B = h / n M, clamped to [0, M], all float64 in this order,
+ *               result = n / M * S_v v |[C<(v), C<=(v)] ^ [A, B]|
+ *             over the distinct kept values v, C<(v) and C<=(v) the weight
+ *             below and up to v.  Evaluated as: kA the smallest v with C<=(v) >
+ *             A, kB the smallest v with C<=(v) >= B, mid = S x m over the kept
+ *             samples with kA < x < kB (float64, fixed order);
+ *               kA == kB:  s = kA (B - A)
+ *               else       s = (kA (C<=(kA) - A) + mid) + kB (B - C<(kB))
+ *             result = n / M * s, no FMA contraction.  A window that holds
+ *             +-inf is not pinned.
+ * wb2_window_quantile: `weights` = HOST int32[n_w], n_w odd, each >= 0; q =
+ * HOST double[n_q], each in [0, 1], taken as given; quantile = DEV double
+ * [n_q][n_outer][n_cycle * n_pos][n_point]; dry_fraction = DEV double
+ * [n_outer][n_cycle * n_pos][n_point] or NULL (it needs use_dry and
+ * denominator > 0).  Checked before anything is enqueued: K14's conditions on
+ * group_begin_host, the weights, and that (largest group) * S m and * S m^2
+ * fit the kernel's 32-bit counters; the kernel cuts a device list that
+ * disagrees to the members.  One launch per 64 quantiles.  A workgroup owns
+ * (outer, cycle, tile of tile_points adjacent points, block of `positions`
+ * consecutive positions): it stages the positions + n_w - 1 cyclic positions'
+ * member rows into LDS once, as K12's order-preserving keys (NaN / absent and
+ * dry samples as two keys above every value), so the input of a block is read
+ * from memory once whatever n_q is; a wave then serves one (position,
+ * quantile) at a time, its lanes being (slice of the window's samples, point)
+ * pairs that add integer weight counters up by lane exchange: one pass for M,
+ * Q and the dry count, counting passes of key_bits_per_pass bits for kA and
+ * kB together, one pass for the sums.  No atomics; every trip count comes from
+ * the arguments.  Zero sizes of n_outer, n_cycle, n_pos, n_point or n_q are a
+ * no-op.
+ * wb2_window_quantile_geometry: for groups of at most n_year members and n_w
+ * weights, the tile is the widest of 64 bytes, 32, ... , one point whose
+ * staging leaves room for 4 positions (one point: 1) in 160 KiB of LDS;
+ * `positions` is what fits, at most 32 (a launch uses min(positions, n_pos));
+ * lds_bytes = (positions + n_w - 1) * n_year * tile_points * sizeof(T) + 4 *
+ * n_w * n_year.  Both calls fail where not even one position of one point
+ * fits (n_w * n_year above about 20 000 samples for float32): there is no
+ * streaming regime.
+ */
+int wb2_window_quantile(int dtype, const void* in, const int64_t* slab,
+                        int64_t n_outer, int32_t n_time, int64_t n_point,
+                        const int32_t* group_begin,
+                        const int32_t* group_begin_host, int32_t n_cycle,
+                        int32_t n_pos, const int32_t* member,
+                        const int32_t* fill, int32_t n_member,
+                        const int32_t* weights, int32_t n_w, int use_dry,
+                        double dry_threshold, int32_t denominator,
+                        const double* q, int32_t n_q, double* quantile,
+                        double* dry_fraction, void* stream);
+int wb2_window_quantile_geometry(int dtype, int64_t n_year, int32_t n_w,
+                                 int32_t* tile_points, int32_t* positions,
+                                 int64_t* lds_bytes,
+                                 int32_t* key_bits_per_pass);
+
 #ifdef __cplusplus
 }
 #endif

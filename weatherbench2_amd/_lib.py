@@ -223,6 +223,13 @@ _SIGNATURES = {
                                 _i64, _vp, _i32, _vp, _vp, _vp]),
     'wb2_climatology_geometry': (_int, [_int, _int, _c.POINTER(_i32),
                                         _c.POINTER(_i32), _c.POINTER(_i32)]),
+    'wb2_window_quantile': (_int, [
+        _int, _vp, _vp, _i64, _i32, _i64, _vp, _c.POINTER(_i32), _i32, _i32,
+        _vp, _vp, _i32, _c.POINTER(_i32), _i32, _int, _c.c_double, _i32,
+        _c.POINTER(_c.c_double), _i32, _vp, _vp, _vp]),
+    'wb2_window_quantile_geometry': (_int, [
+        _int, _i64, _i32, _c.POINTER(_i32), _c.POINTER(_i32),
+        _c.POINTER(_i64), _c.POINTER(_i32)]),
 }
 
 _lib = None

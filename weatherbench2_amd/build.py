@@ -13,7 +13,8 @@ SOURCES = ('common.cpp', 'comm.cpp', 'staging.cpp', 'program.cpp', 'stream_reduc
            'spectrum.hip', 'spectrum_fused.hip', 'spatial_maps.hip',
            'rank_histogram.hip', 'axis_reduce.hip', 'derived_fields.hip',
            'derived_column.hip', 'derived_lead.hip', 'regrid.hip', 'quantile.hip',
-           'time_window.hip', 'climatology.hip')
+           'time_window.hip', 'climatology.hip',
+           'climatology_quantile.hip')
 # compiled once per member count listed in sort3_networks.inc (WB2_SORT3_SIZES)
 EXACT_SOURCE = 'ensemble_exact.hip'
 

@@ -1,8 +1,9 @@
 """Climatology by day of year (scripts/compute_climatology.py and
-weatherbench2/utils.py:73-287): the weighted rolling-window mean and std over
-the years, per day of year and, for `frequency='hourly'`, per hour of day.  No
-Beam, no zarr, no flags: what the script reads from flags is a keyword
-argument here (`method` replaces --method).
+weatherbench2/utils.py:73-287): the weighted rolling-window mean, std,
+quantiles and SEEPS thresholds over the years, per day of year and, for
+`frequency='hourly'`, per hour of day.  No Beam, no zarr, no flags: what the
+script reads from flags is a keyword argument here (`method` replaces
+--method, `seeps_dry_threshold_mm` and `quantiles` their flags).
 
 The reference stacks the years, pads the day-of-year axis cyclically, builds a
 W-wide window and takes a weighted mean or std over (window, year).  The
@@ -42,6 +43,30 @@ Semantics
     alignment.  m[a] and s[a] are the NaN-skipping mean and ddof=0 std of the
     group; the result at a is the NaN-skipping plain mean over i = -H..H of
     v[(a - i) mod n] * w[i+H] (roll, times the weight, then mean('stack')).
+  Window statistics (`stat_fn` the bound `compute` of a `Quantile` or a
+    `SEEPSThreshold`, the script's classes; statistics 'quantile' and 'seeps'
+    of the script's functions; method `explicit` only).  The samples of
+    position a are the X[y, (a + k) mod n], k = -H .. H, of `explicit`, with
+    the weights w[k + H].  `Quantile(qs)` is xarray's weighted quantile
+    (`_weighted_quantile_1d`, method 'linear', NaNs dropped: xarray is not at
+    hand, this is this build's reading of it): drop NaN samples and samples of
+    weight 0 (none left: NaN); sort by value, normalise the weights to sum 1,
+    cum = [0, cumsum(w)]; n = 1 / S w^2; h = (n - 1) q + 1; u = max((h - 1) /
+    n, min(h / n, cum)); v = u n - h + 1; result = S data diff(v).  That is n
+    times the integral of the step function "sorted value over cumulative
+    weight" over [(h - 1) / n, h / n]; the weights are proportional to the
+    integers m = H - |k|, so with M = S m, Q = S m^2: n = M M / Q, A = (h - 1)
+    / n M, B = h / n M and result = n / M * S_i x_(i) |[c_{i-1}, c_i] ^ [A,
+    B]| with exact integer cumulative weights c_i (include/wb2hip.h, K15, has
+    the order of the operations).  The result gets a `quantile` dim in front
+    of `dayofyear` (after `hour`); a scalar q gives a scalar coordinate.
+    `SEEPSThreshold(dry_mm, var)`: is_dry = x < dry_mm / 1000, compared in the
+    data's dtype; `<var>_seeps_dry_fraction` = (dry entries of the window) /
+    (W * number of years present), unweighted, a NaN entry not dry;
+    `<var>_seeps_threshold` = the weighted quantile at 2 / 3 of the entries
+    that are neither NaN nor dry (none: NaN).  Without weights both `compute`
+    are the plain statistics over `dim` (the `quantiles` module; a mean of the
+    comparison).
   Output.  float64 for float32, float64 and integer input (the window weights
     are float64, so xarray promotes).  The dims are the input's with `time`
     replaced by `dayofyear` (labels A), and `hour` in front for hourly; this is
@@ -50,20 +75,32 @@ Semantics
 Differences from the reference:
   * an even window size raises ValueError (the reference asserts);
   * a window of one has the reference's single weight 0 / 0 = NaN and gives
-    NaN everywhere (the reference's `weighted` refuses NaN weights);
+    NaN everywhere for mean and std; the window statistics raise ValueError
+    (the reference's `weighted` refuses NaN weights);
   * where a window holds an inf, mean and std are not finite, as in the
-    reference, but which of NaN and inf is not pinned (inf - inf);
-  * `stat_fn` is 'mean' or 'std'; a callable (the quantile and SEEPS
-    statistics) raises NotImplementedError: they are not ported;
+    reference, but which of NaN and inf is not pinned (inf - inf); a quantile
+    or SEEPS threshold of such a window is not pinned either (the reference's
+    inf * 0 makes NaN);
+  * `stat_fn` is 'mean', 'std' or the bound `compute` of this module's
+    `Quantile` / `SEEPSThreshold`; any other callable raises
+    NotImplementedError, and so do 'quantile' without `quantiles` and 'seeps'
+    without `seeps_dry_threshold_mm`;
+  * the window statistics take the module's own weights only: weights given
+    to compute_rolling_stat must be proportional to H - |k| (to 1e-12 of the
+    largest), else ValueError; a window of more than 511 days, or more than
+    about 20 000 samples (float32; years x days), is refused by the kernel;
   * for hourly frequency every hour must have the same days of year (the
-    reference's concat would outer-join them);
+    reference's concat would outer-join them) and, for SEEPS, the same years;
   * float32 input is accumulated in float64 everywhere (the reference's `fast`
     method and daily resample keep float32 for their first stage).
 
 Device-backed variables (torch tensors on the GPU, `SlabGather` /
-`SlabConcat`, time-sliced views) go through csrc/climatology.hip, are read in
-place and give float64 device tensors; time as the innermost dim costs one
-transposing copy.  Host variables take a NumPy path with the same bits.  Inputs
+`SlabConcat`, time-sliced views) go through csrc/climatology.hip (mean, std)
+and csrc/climatology_quantile.hip (the window statistics: one launch per
+statistic and variable, all hours and quantiles in it), are read in place and
+give float64 device tensors; time as the innermost dim costs one transposing
+copy.  Host variables take a NumPy path: the same bits for mean, std and the
+dry fraction, the same formula (equal to rounding) for the quantiles.  Inputs
 are never modified.
 """
 from __future__ import annotations
@@ -80,9 +117,11 @@ from weatherbench2_amd import resampling
 from weatherbench2_amd import xarray_lite as xl
 
 METHODS = ('explicit', 'fast')
-_NOT_PORTED = ('only the statistics "mean" and "std" are computed here: the '
-               'quantile and SEEPS statistics (a callable stat_fn) are not '
-               'ported')
+_NOT_PORTED = ('a statistic is "mean", "std" or the bound `compute` of a '
+               '`Quantile` or `SEEPSThreshold` of this module: the quantile and '
+               'SEEPS statistics need their parameters (`quantiles`, '
+               '`seeps_dry_threshold_mm`), and no other callable stat_fn is '
+               'computed here')
 
 
 # ---------------------------------------------------------------------------
@@ -165,6 +204,7 @@ class Plan:
   n_pos: int
   axis: np.ndarray         # int64 [n_pos]: the day-of-year labels A
   hours: t.Optional[np.ndarray]
+  n_year: tuple = ()       # explicit: the years present, per cycle
 
 
 def hours_of(hour_interval: int) -> np.ndarray:
@@ -197,7 +237,7 @@ def plan_groups(times, steps, method: str, hours=None) -> Plan:
   if any(not np.array_equal(a, axis) for a in axes[1:]):
     raise ValueError('the hours of day do not have the same days of year')
   n_pos = int(axis.size)
-  begin, member, fill = [0], [], []
+  begin, member, fill, n_year = [0], [], [], []
   for s in series:
     pos = np.searchsorted(axis, doy[s])
     if method == 'fast':
@@ -209,6 +249,7 @@ def plan_groups(times, steps, method: str, hours=None) -> Plan:
     if 365 not in axis:
       raise KeyError('dayofyear 365 is not among the days present')
     years = np.unique(year[s])
+    n_year.append(int(years.size))
     row = np.searchsorted(years, year[s])
     table = np.full((years.size, n_pos), -1, dtype=np.int64)
     if np.unique(row * n_pos + pos).size != s.size:
@@ -227,7 +268,8 @@ def plan_groups(times, steps, method: str, hours=None) -> Plan:
     raise ValueError('too many time steps for one launch')
   return Plan(np.asarray(begin, dtype=np.int32), cat(member),
               cat(fill) if method == 'explicit' else None, len(series), n_pos,
-              axis, None if hours is None else np.asarray(hours, np.int64))
+              axis, None if hours is None else np.asarray(hours, np.int64),
+              tuple(n_year))
 
 
 # ---------------------------------------------------------------------------
@@ -386,6 +428,11 @@ def _smooth(state: dict, mode: str, plan: Plan, w: np.ndarray,
   else:
     outs = _host_smooth(mode, moments, pivot, plan.n_cycle, plan.n_pos, w,
                         want)
+  return {s: _plane(state, plan, a, dims) for s, a in outs.items()}
+
+
+def _plane(state: dict, plan: Plan, a, dims: tuple):
+  """A plane [n_outer, n_group, n_point] as data with `_result_dims(dims)`."""
   order, first, shape = state['order'], state['first'], state['shape']
   full = shape[:first] + (plan.n_cycle, plan.n_pos) + shape[first + 1:]
   # [outer.., cycle, position, inner..] -> [cycle, dims with time -> position]
@@ -393,21 +440,253 @@ def _smooth(state: dict, mode: str, plan: Plan, w: np.ndarray,
   names = ('hour',) + tuple(order)
   target = ('hour',) + tuple(dims)
   perm = [names.index(d) for d in target]
-  result = {}
-  for s, a in outs.items():
-    a = a.reshape(full)
-    if state['device'] is not None:
-      a = a.permute(*lead).permute(*perm)
-      result[s] = a if plan.hours is not None else a[0]
+  a = a.reshape(full)
+  if state['device'] is not None:
+    a = a.permute(*lead).permute(*perm)
+  else:
+    a = np.transpose(np.transpose(a, lead), perm)
+  return a if plan.hours is not None else a[0]
+
+
+# ---------------------------------------------------------------------------
+# the window statistics: weighted quantiles and SEEPS thresholds (K15)
+# ---------------------------------------------------------------------------
+class Quantile:
+  """Compute quantiles (compute_climatology.py:130-144)."""
+
+  def __init__(self, quantiles: t.Sequence[float]):
+    self.quantiles = quantiles
+
+  def compute(self, ds, dim, weights=None):
+    """The quantiles of `ds` over `dim`.  With weights this is the statistic
+    of the rolling window: pass the bound method as `stat_fn`."""
+    if weights is not None:
+      raise NotImplementedError(_WINDOW_ONLY)
+    return quantiles_module().quantile(ds, self.quantiles,
+                                       _plain_dims(dim))
+
+
+class SEEPSThreshold:
+  """Compute SEEPS thresholds (heavy / light) and the fraction of dry grid
+  points (compute_climatology.py:147-178)."""
+
+  def __init__(self, dry_threshold_mm: float, var: str):
+    self.dry_threshold_m = dry_threshold_mm / 1000.0
+    self.var = var
+
+  def compute(self, ds, dim, weights=None):
+    if weights is not None:
+      raise NotImplementedError(_WINDOW_ONLY)
+    da = ds[self.var]
+    dims = _plain_dims(dim) or list(da.dims)
+    data = da.data
+    if dv._on_device(data):
+      if not isinstance(data, torch.Tensor):
+        data = data.materialize(engine.require_gpu())
+      if not data.dtype.is_floating_point:
+        data = data.to(torch.float64)
+      is_dry = data < self.dry_threshold_m  # (compared in the data's dtype)
+      axes = tuple(da.dims.index(d) for d in dims)
+      fraction = is_dry.to(torch.float64).mean(dim=axes)
+      wet = torch.where(is_dry, torch.full_like(data, float('nan')), data)
     else:
-      a = np.transpose(np.transpose(a, lead), perm)
-      result[s] = a if plan.hours is not None else a[0]
-  return result
+      data = np.asarray(da.values)
+      if data.dtype not in (np.float32, np.float64):
+        data = data.astype(np.float64)
+      is_dry = data < data.dtype.type(self.dry_threshold_m)
+      fraction = is_dry.mean(axis=tuple(da.dims.index(d) for d in dims))
+      wet = np.where(is_dry, np.nan, data)
+    heavy = quantiles_module().quantile(
+        xl.DataArray(wet, da.dims, da.coords, da.name), 2 / 3, dims)
+    coords = {k: c for k, c in heavy.coords.items() if k != 'quantile'}
+    out = xl.Dataset(coords=coords)
+    for name, values in ((f'{self.var}_seeps_threshold', heavy.data),
+                         (f'{self.var}_seeps_dry_fraction', fraction)):
+      out.data_vars[name] = xl.DataArray(values, heavy.dims, out.coords, name)
+    return out
 
 
-def _check_stat(stat_fn) -> str:
+_WINDOW_ONLY = ('a weighted quantile is computed over the rolling window only: '
+                'pass this bound method as `stat_fn` of compute_rolling_stat, '
+                'compute_daily_stat or compute_hourly_stat')
+
+
+def quantiles_module():
+  from weatherbench2_amd import quantiles
+  return quantiles
+
+
+def _plain_dims(dim):
+  if dim is None or dim is Ellipsis:
+    return None
+  return [dim] if isinstance(dim, str) else list(dim)
+
+
+def _owner(stat_fn):
+  """The Quantile / SEEPSThreshold whose bound `compute` `stat_fn` is, else
+  None."""
+  owner = getattr(stat_fn, '__self__', None)
+  if isinstance(owner, (Quantile, SEEPSThreshold)) and getattr(
+      stat_fn, '__func__', None) is type(owner).compute:
+    return owner
+  return None
+
+
+def _integer_weights(w: np.ndarray) -> np.ndarray:
+  """The integers H - |k| the window weights `w` are proportional to."""
+  half = w.size // 2
+  if w.size == 1 or np.isnan(w).any():
+    raise ValueError('a window of one has the single weight 0 / 0 = NaN: a '
+                     'weighted quantile refuses NaN weights')
+  base = half - np.abs(np.arange(-half, half + 1))
+  top = w.max()
+  if not top > 0 or np.abs(w / top - base / half).max() > 1e-12:
+    raise ValueError('the quantile and SEEPS statistics take the weights of '
+                     'create_window_weights only (proportional to H - |k|)')
+  return np.ascontiguousarray(base, dtype=np.int32)
+
+
+def _owner_quantiles(owner) -> tuple:
+  """(quantiles float64 [n_q], dry threshold in metres or None)."""
+  if isinstance(owner, SEEPSThreshold):
+    return np.asarray([2 / 3], dtype=np.float64), float(owner.dry_threshold_m)
+  qs = np.atleast_1d(np.asarray(owner.quantiles, dtype=np.float64))
+  if qs.ndim != 1 or qs.size == 0:
+    raise ValueError('quantiles must be a number or a non-empty sequence')
+  if not np.all((qs >= 0) & (qs <= 1)):
+    raise ValueError('Quantiles must be in the range [0, 1]')
+  return qs, None
+
+
+def _host_window(x: np.ndarray, plan: Plan, m: np.ndarray, qs: np.ndarray,
+                 threshold: t.Optional[float],
+                 denominator: t.Optional[int]) -> tuple:
+  """The K15 launch in NumPy: x [n_outer, n_time, n_point] -> (quantile [n_q,
+  n_outer, n_group, n_point], dry fraction [n_outer, n_group, n_point] or
+  None), the kernel's formula (include/wb2hip.h)."""
+  n_outer, n_time, n_point = x.shape
+  n_pos, n_group = plan.n_pos, plan.n_cycle * plan.n_pos
+  begin = plan.group_begin.tolist()
+  member = plan.member.tolist()
+  fill = plan.fill.tolist() if plan.fill is not None else None
+  n_year = max([b - a for a, b in zip(begin[:-1], begin[1:])] + [1])
+  half = m.size // 2
+  cols = n_outer * n_point
+  quant = np.full((qs.size, n_outer, n_group, n_point), np.nan)
+  dry = None if denominator is None else np.zeros((n_outer, n_group, n_point))
+  weight = np.repeat(m.astype(np.int64), n_year)[:, None]
+  absent = np.full((n_outer, n_point), np.nan, dtype=x.dtype)
+  with np.errstate(all='ignore'):
+    for c in range(plan.n_cycle):
+      stack = np.full((n_pos, n_year, n_outer, n_point), np.nan, dtype=x.dtype)
+      for a in range(n_pos):
+        g = c * n_pos + a
+        for y, j in enumerate(range(begin[g], begin[g + 1])):
+          v = x[:, member[j]] if 0 <= member[j] < n_time else absent
+          if fill is not None and 0 <= fill[j] < n_time:
+            v = np.where(np.isnan(v), x[:, fill[j]], v)
+          stack[a, y] = v
+      is_dry = (stack < x.dtype.type(threshold) if threshold is not None
+                else np.zeros(stack.shape, dtype=bool))
+      for a in range(n_pos):
+        at = (a + np.arange(-half, half + 1)) % n_pos
+        sample = stack[at].reshape(-1, cols)
+        dflag = is_dry[at].reshape(-1, cols)
+        kept = ~np.isnan(sample) & ~dflag & (weight > 0)
+        value = np.where(kept, sample, np.inf).astype(np.float64)
+        order = np.argsort(value, axis=0, kind='stable')
+        vs = np.take_along_axis(value, order, 0)
+        ws = np.take_along_axis(np.where(kept, weight, 0), order, 0)
+        cum = np.cumsum(ws, axis=0)
+        big = cum[-1].astype(np.float64)
+        sq = (ws * ws).sum(axis=0).astype(np.float64)
+        n = big * big / sq
+        g = c * n_pos + a
+        for iq, q in enumerate(qs.tolist()):
+          h = (n - 1.0) * q + 1.0
+          lo = (h - 1.0) / n * big
+          hi = h / n * big
+          lo = np.where(lo < 0.0, 0.0, lo)
+          hi = np.where(hi > big, big, hi)
+          xa = np.take_along_axis(vs, (cum > lo).argmax(0)[None], 0)[0]
+          xb = np.take_along_axis(vs, (cum >= hi).argmax(0)[None], 0)[0]
+          le_a = (ws * (vs <= xa)).sum(axis=0).astype(np.float64)
+          lt_b = (ws * (vs < xb)).sum(axis=0).astype(np.float64)
+          inner = (vs > xa) & (vs < xb) & (ws > 0)
+          mid = np.where(inner, vs * ws, 0.0).sum(axis=0)
+          s = np.where(xa == xb, xa * (hi - lo),
+                       (xa * (le_a - lo) + mid) + xb * (hi - lt_b))
+          res = np.where(cum[-1] == 0, np.nan, n / big * s)
+          quant[iq, :, g, :] = res.reshape(n_outer, n_point)
+        if dry is not None:
+          dry[:, g, :] = (dflag.sum(axis=0).astype(np.float64)
+                          / np.float64(denominator)).reshape(n_outer, n_point)
+  return quant, dry
+
+
+def _window(da: xl.DataArray, time_dim: str, plan: Plan, w: np.ndarray,
+            owner) -> dict:
+  """{output suffix: (data, dims)} of one window statistic of one variable."""
+  m = _integer_weights(w)
+  qs, threshold = _owner_quantiles(owner)
+  seeps = isinstance(owner, SEEPSThreshold)
+  denominator = None
+  if seeps:
+    if len(set(plan.n_year)) != 1:
+      raise ValueError('the hours of day do not have the same years')
+    denominator = int(m.size) * plan.n_year[0]
+  order, first = _layout(da, time_dim)
+  sizes = da.sizes
+  shape = tuple(sizes[d] for d in order)
+  n_outer = int(np.prod(shape[:first], dtype=np.int64))
+  n_time = shape[first]
+  n_point = int(np.prod(shape[first + 1:], dtype=np.int64))
+  n_group = plan.n_cycle * plan.n_pos
+  state = {'order': order, 'first': first, 'shape': shape, 'device': None}
+  if dv._on_device(da.data):
+    device = engine.require_gpu()
+    state['device'] = device
+    dtype = dv._float_dtype(da.dtype)
+    if n_outer * n_point * n_group == 0:
+      quant = torch.zeros((qs.size, n_outer, n_group, n_point),
+                          dtype=torch.float64, device=device)
+      dry = quant[0].clone() if seeps else None
+    else:
+      ten, table = dv._operand(da, order, device, dtype,
+                               len(order) - first - 1)
+      table = dv._table_tensor(table, device)
+      member = torch.from_numpy(plan.member).to(device, non_blocking=True)
+      fill = torch.from_numpy(plan.fill).to(device, non_blocking=True)
+      quant, dry = engine.window_quantile(
+          ten, table, n_outer, n_time, n_point, plan.group_begin, plan.n_cycle,
+          plan.n_pos, member, fill, m, qs, threshold, denominator)
+  else:
+    data = np.asarray(da.values)
+    if data.dtype not in (np.float32, np.float64):
+      data = data.astype(np.float64)
+    x = np.transpose(data, [da.dims.index(d) for d in order]).reshape(
+        n_outer, n_time, n_point)
+    quant, dry = _host_window(x, plan, m, qs, threshold, denominator)
+  dims = _result_dims(da.dims, plan, time_dim)
+  if seeps:
+    return {'seeps_threshold': (_plane(state, plan, quant[0], da.dims), dims),
+            'seeps_dry_fraction': (_plane(state, plan, dry, da.dims), dims)}
+  planes = [_plane(state, plan, quant[i], da.dims) for i in range(qs.size)]
+  at = 1 if plan.hours is not None else 0
+  if np.ndim(owner.quantiles) == 0:
+    return {'quantile': (planes[0], dims)}
+  stack = torch.stack if state['device'] is not None else np.stack
+  return {'quantile': (stack(planes, at),
+                       dims[:at] + ('quantile',) + dims[at:])}
+
+
+def _check_stat(stat_fn):
+  """'mean', 'std' or the owner of a window statistic."""
   if callable(stat_fn):
-    raise NotImplementedError(_NOT_PORTED)
+    owner = _owner(stat_fn)
+    if owner is None:
+      raise NotImplementedError(_NOT_PORTED)
+    return owner
   if stat_fn not in ('mean', 'std'):
     raise NotImplementedError(f'stat {stat_fn} not implemented.')
   return stat_fn
@@ -476,17 +755,28 @@ def _variable(da: xl.DataArray, times: np.ndarray, *, frequency: str,
     raise NotImplementedError(
         f'method {method} for climatological frequency {frequency} not '
         'implemented.')
-  for s in statistics:
+  moment = [s for s in statistics if isinstance(s, str)]
+  window = [s for s in statistics if not isinstance(s, str)]
+  for s in moment:
     _check_stat(s)
+  if window and method != 'explicit':
+    raise NotImplementedError(
+        'the quantile and SEEPS statistics are computed by method "explicit" '
+        f'only, not {method!r}')
   w = create_window_weights(window_size).values
+  if window:
+    _integer_weights(w)
   steps = select_years(times, clim_years)
   if steps.size == 0:
     raise ValueError('clim_years selects no time step')
   out = {}
   if frequency == 'hourly':
     plan = plan_groups(times, steps, method, hours_of(hour_interval))
-    state = _moments(da, 'time', plan)
-    out = _smooth(state, method, plan, w, statistics, da.dims, 'time')
+    if moment:
+      state = _moments(da, 'time', plan)
+      out = _smooth(state, method, plan, w, moment, da.dims, 'time')
+    for owner in window:
+      out[owner] = _window(da, 'time', plan, w, owner)
     return out, plan
   plan = None
   if method == 'fast' and 'mean' in statistics:
@@ -498,8 +788,13 @@ def _variable(da: xl.DataArray, times: np.ndarray, *, frequency: str,
     daily = _daily_mean(da, steps, times)
     days = np.asarray(daily.coords['time'])
     plan = plan_groups(days, np.arange(days.size), method)
-    state = _moments(daily, 'time', plan)
-    out.update(_smooth(state, method, plan, w, rest, da.dims, 'time'))
+    if [s for s in rest if isinstance(s, str)]:
+      state = _moments(daily, 'time', plan)
+      out.update(_smooth(state, method, plan, w,
+                         [s for s in rest if isinstance(s, str)], da.dims,
+                         'time'))
+    for owner in window:
+      out[owner] = _window(daily, 'time', plan, w, owner)
   return {s: out[s] for s in statistics}, plan
 
 
@@ -509,28 +804,59 @@ def _dataset_stat(obs, names: t.Callable[[str, str], str],
   statistic)`, statistic-major; a DataArray gives a DataArray of the first
   statistic."""
   if isinstance(obs, xl.DataArray):
+    first = statistics[0]
+    if isinstance(first, SEEPSThreshold):
+      raise ValueError('SEEPSThreshold selects its variable from a Dataset')
     out, plan = _variable(obs, _time_values(obs), statistics=statistics,
                           **kwargs)
-    return xl.DataArray(out[statistics[0]], _result_dims(obs.dims, plan),
-                        _result_coords(obs.coords, plan), obs.name)
+    coords = _result_coords(obs.coords, plan)
+    if isinstance(first, str):
+      return xl.DataArray(out[first], _result_dims(obs.dims, plan), coords,
+                          obs.name)
+    data, dims = out[first]['quantile']
+    coords['quantile'] = _quantile_coord(first)
+    return xl.DataArray(data, dims, coords, obs.name)
   dataset = xl.as_dataset(obs)
   times = _time_values(dataset)
+  for s in statistics:
+    if isinstance(s, SEEPSThreshold) and s.var not in dataset.data_vars:
+      raise KeyError(s.var)
   results, plan = {}, None
   for name, da in dataset.data_vars.items():
     if 'time' not in da.dims:
       raise ValueError(f'variable {name!r} has no time dim: drop static '
                        'variables first')
-    results[name], plan = _variable(da, times, statistics=statistics, **kwargs)
+    mine = [s for s in statistics
+            if not isinstance(s, SEEPSThreshold) or s.var == name]
+    if mine:
+      results[name], plan = _variable(da, times, statistics=mine, **kwargs)
   if plan is None:
     return xl.Dataset(attrs=dataset.attrs)
   out = xl.Dataset(coords=_result_coords(dataset.coords, plan),
                    attrs=dataset.attrs)
   for s in statistics:
+    if isinstance(s, Quantile):
+      out.coords['quantile'] = _quantile_coord(s)
     for name, da in dataset.data_vars.items():
-      new = names(name, s)
-      out.data_vars[new] = xl.DataArray(
-          results[name][s], _result_dims(da.dims, plan), out.coords, new)
+      if isinstance(s, str):
+        new = names(name, s)
+        out.data_vars[new] = xl.DataArray(
+            results[name][s], _result_dims(da.dims, plan), out.coords, new)
+      elif isinstance(s, Quantile):
+        new = names(name, 'quantile')
+        data, dims = results[name][s]['quantile']
+        out.data_vars[new] = xl.DataArray(data, dims, out.coords, new)
+      elif s.var == name:
+        for suffix, (data, dims) in results[name][s].items():
+          new = f'{name}_{suffix}'
+          out.data_vars[new] = xl.DataArray(data, dims, out.coords, new)
   return out
+
+
+def _quantile_coord(owner: Quantile):
+  qs, _ = _owner_quantiles(owner)
+  return xl.DataArray(np.asarray(qs[0]), ()) if np.ndim(
+      owner.quantiles) == 0 else qs
 
 
 def _same_name(name: str, statistic: str) -> str:
@@ -544,29 +870,47 @@ def compute_rolling_stat(ds, window_weights, stat_fn='mean'):
   """Rolling climatology of a series labelled by day (utils.py:88-124)."""
   stat = _check_stat(stat_fn)
   w = _weights(window_weights)
+  if not isinstance(stat, str):
+    _integer_weights(w)
 
   def one(da, times):
     plan = plan_groups(times, np.arange(times.size), 'explicit')
+    if not isinstance(stat, str):
+      return _window(da, 'time', plan, w, stat), plan
     state = _moments(da, 'time', plan)
     return _smooth(state, 'explicit', plan, w, [stat], da.dims,
                    'time')[stat], plan
 
   if isinstance(ds, xl.DataArray):
+    if isinstance(stat, SEEPSThreshold):
+      raise ValueError('SEEPSThreshold selects its variable from a Dataset')
     data, plan = one(ds, _time_values(ds))
-    return xl.DataArray(data, _result_dims(ds.dims, plan),
-                        _result_coords(ds.coords, plan), ds.name)
+    coords = _result_coords(ds.coords, plan)
+    dims = _result_dims(ds.dims, plan)
+    if isinstance(stat, Quantile):
+      data, dims = data['quantile']
+      coords['quantile'] = _quantile_coord(stat)
+    return xl.DataArray(data, dims, coords, ds.name)
   dataset = xl.as_dataset(ds)
   times = _time_values(dataset)
   plan = plan_groups(times, np.arange(times.size), 'explicit')
   out = xl.Dataset(coords=_result_coords(dataset.coords, plan),
                    attrs=dataset.attrs)
+  if isinstance(stat, SEEPSThreshold):
+    for suffix, (data, dims) in one(dataset[stat.var], times)[0].items():
+      new = f'{stat.var}_{suffix}'
+      out.data_vars[new] = xl.DataArray(data, dims, out.coords, new)
+    return out
+  if isinstance(stat, Quantile):
+    out.coords['quantile'] = _quantile_coord(stat)
   for name, da in dataset.data_vars.items():
     if 'time' not in da.dims:
       out.data_vars[name] = xl.DataArray(da.data, da.dims, out.coords, name)
       continue
-    out.data_vars[name] = xl.DataArray(one(da, times)[0],
-                                       _result_dims(da.dims, plan), out.coords,
-                                       name)
+    data, dims = one(da, times)[0], _result_dims(da.dims, plan)
+    if isinstance(stat, Quantile):
+      data, dims = data['quantile']
+    out.data_vars[name] = xl.DataArray(data, dims, out.coords, name)
   return out
 
 
@@ -683,25 +1027,47 @@ def compute_daily_stat_fast(obs, window_size: int, clim_years: slice,
 # ---------------------------------------------------------------------------
 # the script
 # ---------------------------------------------------------------------------
+def compute_seeps_chunk(obs_chunk, *, frequency: str, window_size: int,
+                        clim_years: slice, hour_interval: t.Optional[int],
+                        seeps_threshold_mm: dict, method: str = 'explicit'):
+  """The script's `compute_seeps_chunk` (:181-216) without the key: the chunk
+  holds exactly one variable, a key of `seeps_threshold_mm`; the result holds
+  `<variable>_seeps_threshold` and `<variable>_seeps_dry_fraction`."""
+  if method != 'explicit':
+    raise NotImplementedError('SEEPS only tested for explicit.')
+  (var,) = list(xl.as_dataset(obs_chunk).data_vars)
+  stat_fn = SEEPSThreshold(seeps_threshold_mm[var], var=var).compute
+  if frequency == 'hourly':
+    return compute_hourly_stat(obs_chunk, window_size, clim_years,
+                               hour_interval, stat_fn)
+  if frequency == 'daily':
+    return compute_daily_stat(obs_chunk, window_size, clim_years, stat_fn)
+  raise NotImplementedError(f'Frequency {frequency} not implemented.')
+
+
 def compute_stat_chunk(obs_chunk, *, frequency: str, window_size: int,
                        clim_years: slice, statistic='mean',
                        hour_interval: t.Optional[int] = None,
+                       quantiles: t.Optional[t.Sequence[float]] = None,
                        method: str = 'explicit'):
   """The script's `compute_stat_chunk` (:219-269) without the key: the
   climatology of every variable of the chunk, named `<variable>_<statistic>`
-  for a statistic other than 'mean'."""
+  for a statistic other than 'mean'; 'quantile' takes `quantiles` and gives a
+  `quantile` dim in front of `dayofyear`."""
   if callable(statistic):
     raise NotImplementedError(_NOT_PORTED)
   if statistic not in ['mean', 'std', 'quantile']:
     raise NotImplementedError(f'stat {statistic} not implemented.')
-  if statistic == 'quantile':
-    raise NotImplementedError(_NOT_PORTED)
   if method not in METHODS or frequency not in ('hourly', 'daily'):
     raise NotImplementedError(
         f'method {method} for climatological frequency {frequency} not '
         'implemented.')
   names = _same_name if statistic == 'mean' else (
       lambda name, s: f'{name}_{s}')
+  if statistic == 'quantile':
+    if quantiles is None:
+      raise NotImplementedError(_NOT_PORTED)
+    statistic = Quantile([float(q) for q in quantiles])
   return _dataset_stat(obs_chunk, names, [statistic], frequency=frequency,
                        window_size=window_size, clim_years=clim_years,
                        hour_interval=hour_interval, method=method)
@@ -711,19 +1077,25 @@ def compute_climatology(obs, *, frequency: str = 'hourly',
                         hour_interval: int = 1, window_size: int = 61,
                         start_year: int = 1990, end_year: int = 2020,
                         statistics: t.Sequence[str] = ('mean',),
-                        method: str = 'explicit'):
-  """The script's `main` for the statistics 'mean' and 'std': variables
-  without `time` are dropped; per statistic, in the order of `statistics`,
-  every variable's mean under its own name and its std under `<name>_std`.
-  With method='explicit' one moments launch serves all statistics and all
-  hours of a variable."""
+                        method: str = 'explicit',
+                        seeps_dry_threshold_mm: t.Optional[dict] = None,
+                        quantiles: t.Optional[t.Sequence[float]] = None):
+  """The script's `main`: variables without `time` are dropped; per
+  statistic, in the order of `statistics`, every variable's mean under its own
+  name, its std under `<name>_std`, its quantiles (`quantiles`) under
+  `<name>_quantile`, and for 'seeps', for every variable that is a key of
+  `seeps_dry_threshold_mm`, `<name>_seeps_threshold` then
+  `<name>_seeps_dry_fraction`.  With method='explicit' one moments launch
+  serves mean and std and all hours of a variable; every quantile or SEEPS
+  statistic is one further launch."""
   if isinstance(statistics, str):
     statistics = [statistics]
   statistics = list(dict.fromkeys(statistics))
   for s in statistics:
-    if callable(s) or s in ('quantile', 'seeps'):
+    if callable(s) or (s == 'quantile' and quantiles is None) or (
+        s == 'seeps' and seeps_dry_threshold_mm is None):
       raise NotImplementedError(_NOT_PORTED)
-    if s not in ('mean', 'std'):
+    if s not in ('mean', 'std', 'quantile', 'seeps'):
       raise NotImplementedError(f'stat {s} not implemented.')
   if frequency not in ('hourly', 'daily'):
     raise NotImplementedError(f'frequency {frequency} not implemented.')
@@ -732,6 +1104,17 @@ def compute_climatology(obs, *, frequency: str = 'hourly',
   for name, da in dataset.data_vars.items():
     if 'time' in da.dims:
       kept.data_vars[name] = da
+  expanded = []
+  for s in statistics:
+    if s == 'quantile':
+      expanded.append(Quantile([float(q) for q in quantiles]))
+    elif s == 'seeps':
+      expanded.extend(SEEPSThreshold(seeps_dry_threshold_mm[name], var=name)
+                      for name in kept.data_vars
+                      if name in seeps_dry_threshold_mm)
+    else:
+      expanded.append(s)
+  statistics = expanded
   return _dataset_stat(
       kept, lambda name, s: name if s == 'mean' else f'{name}_{s}',
       statistics, frequency=frequency, window_size=window_size,

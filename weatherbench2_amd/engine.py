@@ -1470,6 +1470,68 @@ def cycle_smooth(mode: str, moments, pivot: t.Optional[torch.Tensor],
   return outs
 
 
+def window_quantile_geometry(dtype: torch.dtype, n_year: int,
+                             n_w: int) -> dict:
+  """What the K15 launch chooses for groups of at most `n_year` members and a
+  window of `n_w` weights: `tile_points` adjacent points and `positions`
+  consecutive positions per workgroup, its `lds_bytes`, and the key bits
+  settled per counting pass.  Raises where no tile fits the LDS."""
+  return _geometry('wb2_window_quantile_geometry',
+                   (_DTYPES[dtype], int(n_year), int(n_w)),
+                   [('tile_points', _I32), ('positions', _I32),
+                    ('lds_bytes', ctypes.c_int64),
+                    ('key_bits_per_pass', _I32)])
+
+
+def window_quantile(x: torch.Tensor, slab: t.Optional[torch.Tensor],
+                    n_outer: int, n_time: int, n_point: int, group_begin,
+                    n_cycle: int, n_pos: int, member: torch.Tensor,
+                    fill: t.Optional[torch.Tensor], weights, quantiles,
+                    dry_threshold: t.Optional[float] = None,
+                    denominator: t.Optional[int] = None) -> tuple:
+  """K15: (quantile, dry_fraction) of the rolling window over K14's groups g =
+  c * n_pos + a, from ONE launch.  `weights` is a HOST sequence of an odd
+  number of non-negative integers (the window, proportional to H - |k|),
+  `quantiles` a HOST sequence in [0, 1].  quantile is float64 [n_q, n_outer,
+  n_cycle * n_pos, n_point]: the weighted quantiles (include/wb2hip.h) of the
+  samples X[y, (a + k) mod n_pos] that are not NaN and, with `dry_threshold`,
+  not below it.  With `denominator` as well, dry_fraction is float64 [n_outer,
+  n_cycle * n_pos, n_point]: the samples below the threshold / denominator;
+  otherwise None.  `group_begin`, `member`, `fill`, `slab` as for
+  `group_moments`."""
+  _check_series(x, slab, n_outer, n_time, {'member': member, 'fill': fill})
+  begin = np.ascontiguousarray(group_begin, dtype=np.int32)
+  n_group = int(n_cycle) * int(n_pos)
+  if begin.ndim != 1 or begin.size != n_group + 1:
+    raise ValueError('group_begin must hold n_cycle * n_pos + 1 offsets')
+  n_member = int(member.numel())
+  if fill is not None and fill.numel() != n_member:
+    raise ValueError('fill must have one entry per member')
+  w = np.ascontiguousarray(weights, dtype=np.int32)
+  q = np.ascontiguousarray(quantiles, dtype=np.float64)
+  if w.ndim != 1 or q.ndim != 1:
+    raise ValueError('weights and quantiles must be vectors')
+  if denominator is not None and dry_threshold is None:
+    raise ValueError('the dry fraction needs a dry threshold')
+  begin_dev = torch.from_numpy(begin).to(x.device)
+  quant = torch.empty((q.size, n_outer, n_group, n_point),
+                      dtype=torch.float64, device=x.device)
+  dry = None if denominator is None else torch.empty(
+      (n_outer, n_group, n_point), dtype=torch.float64, device=x.device)
+  _launch('window_quantile', 'wb2_window_quantile', _DTYPES[x.dtype],
+          _lib.ptr(x), _lib.ptr(slab), n_outer, n_time, n_point,
+          _lib.ptr(begin_dev),
+          begin.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(n_cycle),
+          int(n_pos), _lib.ptr(member), _lib.ptr(fill), n_member,
+          w.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(w.size),
+          int(dry_threshold is not None),
+          0.0 if dry_threshold is None else float(dry_threshold),
+          int(denominator or 0),
+          q.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(q.size),
+          _lib.ptr(quant), _lib.ptr(dry), current_stream_ptr(x.device))
+  return quant, dry
+
+
 def ensemble_threshold_reduce(plan: ReductionPlan, ens: torch.Tensor,
                               member_stride: int, n_member: int, ens_slab,
                               truth: torch.Tensor, truth_slab,

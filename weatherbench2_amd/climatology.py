@@ -111,8 +111,8 @@ import typing as t
 import numpy as np
 import torch
 
-from weatherbench2_amd import derived_variables as dv
 from weatherbench2_amd import engine
+from weatherbench2_amd import operands
 from weatherbench2_amd import resampling
 from weatherbench2_amd import xarray_lite as xl
 
@@ -360,91 +360,58 @@ def _host_smooth(mode: str, moments, pivot, n_cycle: int, n_pos: int,
 # ---------------------------------------------------------------------------
 # one variable: moments, then the smoothing
 # ---------------------------------------------------------------------------
-def _layout(da: xl.DataArray, time_dim: str) -> tuple:
-  """(order of the dims the kernel reads, index of the time dim in it)."""
-  dims = tuple(da.dims)
-  axis = dims.index(time_dim)
-  if axis < len(dims) - 1 or len(dims) == 1:
-    order = dims  # read where it lies
-  else:
-    order = (time_dim,) + dims[:-1]  # one transposing copy
-  return order, order.index(time_dim)
-
-
-def _moments(da: xl.DataArray, time_dim: str, plan: Plan) -> dict:
+class _Moments(t.NamedTuple):
   """The three moment planes [n_outer, n_group, n_point] and the pivot of one
-  variable, on the device for a device-backed variable, else in NumPy."""
-  order, first = _layout(da, time_dim)
-  sizes = da.sizes
-  shape = tuple(sizes[d] for d in order)
-  n_outer = int(np.prod(shape[:first], dtype=np.int64))
-  n_time = shape[first]
-  n_point = int(np.prod(shape[first + 1:], dtype=np.int64))
+  variable: device tensors for a device-backed variable, else NumPy arrays."""
+  layout: operands.SeriesLayout
+  moments: tuple
+  pivot: t.Any
+
+
+def _moments(da: xl.DataArray, time_dim: str, plan: Plan) -> _Moments:
+  lay = operands.SeriesLayout.of(da.dims, da.sizes, time_dim)
+  n_outer, n_time, n_point = lay.n_outer, lay.n_series, lay.n_point
   n_group = plan.n_cycle * plan.n_pos
-  state = {'order': order, 'first': first, 'shape': shape, 'device': None}
-  if dv._on_device(da.data):
+  if operands.on_device(da.data):
     device = engine.require_gpu()
-    state['device'] = device
-    dtype = dv._float_dtype(da.dtype)
     if n_outer * n_point * n_group == 0:
-      state['moments'] = tuple(torch.zeros(
-          (n_outer, n_group, n_point), dtype=torch.float64, device=device)
-                               for _ in range(3))
-      state['pivot'] = torch.zeros((n_outer, n_point), dtype=torch.float64,
-                                   device=device)
-      return state
-    ten, table = dv._operand(da, order, device, dtype, len(order) - first - 1)
-    table = dv._table_tensor(table, device)
+      zeros = lambda *n: torch.zeros(n, dtype=torch.float64, device=device)
+      return _Moments(lay, tuple(zeros(n_outer, n_group, n_point)
+                                 for _ in range(3)), zeros(n_outer, n_point))
+    ten, table = lay.operand(da, device, operands.float_dtype(da.dtype))
     member = torch.from_numpy(plan.member).to(device, non_blocking=True)
     fill = None if plan.fill is None else torch.from_numpy(plan.fill).to(
         device, non_blocking=True)
     pivot = engine.first_finite(ten, table, n_outer, n_time, n_point, member)
-    state['moments'] = engine.group_moments(
+    return _Moments(lay, engine.group_moments(
         ten, table, n_outer, n_time, n_point, plan.group_begin, member, fill,
-        pivot)
-    state['pivot'] = pivot
-    return state
-  data = np.asarray(da.values)
-  if data.dtype not in (np.float32, np.float64):
-    data = data.astype(np.float64)
-  x = np.transpose(data, [da.dims.index(d) for d in order]).reshape(
-      n_outer, n_time, n_point)
-  state['pivot'] = _host_first_finite(x, plan.member)
-  state['moments'] = _host_moments(x, plan, state['pivot'])
-  return state
+        pivot), pivot)
+  x = lay.host(da)
+  pivot = _host_first_finite(x, plan.member)
+  return _Moments(lay, _host_moments(x, plan, pivot), pivot)
 
 
-def _smooth(state: dict, mode: str, plan: Plan, w: np.ndarray,
-            want: t.Sequence[str], dims: tuple, time_dim: str) -> dict:
+def _smooth(state: _Moments, mode: str, plan: Plan, w: np.ndarray,
+            want: t.Sequence[str]) -> dict:
   """{statistic: data with the dims `_result_dims(dims)`}."""
-  moments, pivot = state['moments'], state['pivot']
-  if state['device'] is not None:
+  moments, pivot = state.moments, state.pivot
+  if isinstance(moments[0], torch.Tensor):
     if moments[0].numel() == 0:
       outs = {s: torch.empty_like(moments[0]) for s in want}
     else:
-      weights = torch.from_numpy(w).to(state['device'])
+      weights = torch.from_numpy(w).to(moments[0].device)
       outs = engine.cycle_smooth(mode, moments, pivot, plan.n_cycle,
                                  plan.n_pos, weights, want)
   else:
     outs = _host_smooth(mode, moments, pivot, plan.n_cycle, plan.n_pos, w,
                         want)
-  return {s: _plane(state, plan, a, dims) for s, a in outs.items()}
+  return {s: _plane(state.layout, plan, a) for s, a in outs.items()}
 
 
-def _plane(state: dict, plan: Plan, a, dims: tuple):
-  """A plane [n_outer, n_group, n_point] as data with `_result_dims(dims)`."""
-  order, first, shape = state['order'], state['first'], state['shape']
-  full = shape[:first] + (plan.n_cycle, plan.n_pos) + shape[first + 1:]
-  # [outer.., cycle, position, inner..] -> [cycle, dims with time -> position]
-  lead = [first] + [i for i in range(len(full)) if i != first]
-  names = ('hour',) + tuple(order)
-  target = ('hour',) + tuple(dims)
-  perm = [names.index(d) for d in target]
-  a = a.reshape(full)
-  if state['device'] is not None:
-    a = a.permute(*lead).permute(*perm)
-  else:
-    a = np.transpose(np.transpose(a, lead), perm)
+def _plane(lay: operands.SeriesLayout, plan: Plan, a):
+  """A plane [n_outer, n_group, n_point] as data with `_result_dims(dims)`:
+  [hour,] the variable's dims with the position where the time stood."""
+  a = lay.restore(a, (plan.n_cycle, plan.n_pos))
   return a if plan.hours is not None else a[0]
 
 
@@ -480,7 +447,7 @@ class SEEPSThreshold:
     da = ds[self.var]
     dims = _plain_dims(dim) or list(da.dims)
     data = da.data
-    if dv._on_device(data):
+    if operands.on_device(data):
       if not isinstance(data, torch.Tensor):
         data = data.materialize(engine.require_gpu())
       if not data.dtype.is_floating_point:
@@ -635,47 +602,35 @@ def _window(da: xl.DataArray, time_dim: str, plan: Plan, w: np.ndarray,
     if len(set(plan.n_year)) != 1:
       raise ValueError('the hours of day do not have the same years')
     denominator = int(m.size) * plan.n_year[0]
-  order, first = _layout(da, time_dim)
-  sizes = da.sizes
-  shape = tuple(sizes[d] for d in order)
-  n_outer = int(np.prod(shape[:first], dtype=np.int64))
-  n_time = shape[first]
-  n_point = int(np.prod(shape[first + 1:], dtype=np.int64))
+  lay = operands.SeriesLayout.of(da.dims, da.sizes, time_dim)
+  n_outer, n_time, n_point = lay.n_outer, lay.n_series, lay.n_point
   n_group = plan.n_cycle * plan.n_pos
-  state = {'order': order, 'first': first, 'shape': shape, 'device': None}
-  if dv._on_device(da.data):
+  device = None
+  if operands.on_device(da.data):
     device = engine.require_gpu()
-    state['device'] = device
-    dtype = dv._float_dtype(da.dtype)
     if n_outer * n_point * n_group == 0:
       quant = torch.zeros((qs.size, n_outer, n_group, n_point),
                           dtype=torch.float64, device=device)
       dry = quant[0].clone() if seeps else None
     else:
-      ten, table = dv._operand(da, order, device, dtype,
-                               len(order) - first - 1)
-      table = dv._table_tensor(table, device)
+      ten, table = lay.operand(da, device, operands.float_dtype(da.dtype))
       member = torch.from_numpy(plan.member).to(device, non_blocking=True)
       fill = torch.from_numpy(plan.fill).to(device, non_blocking=True)
       quant, dry = engine.window_quantile(
           ten, table, n_outer, n_time, n_point, plan.group_begin, plan.n_cycle,
           plan.n_pos, member, fill, m, qs, threshold, denominator)
   else:
-    data = np.asarray(da.values)
-    if data.dtype not in (np.float32, np.float64):
-      data = data.astype(np.float64)
-    x = np.transpose(data, [da.dims.index(d) for d in order]).reshape(
-        n_outer, n_time, n_point)
-    quant, dry = _host_window(x, plan, m, qs, threshold, denominator)
+    quant, dry = _host_window(lay.host(da), plan, m, qs, threshold,
+                              denominator)
   dims = _result_dims(da.dims, plan, time_dim)
   if seeps:
-    return {'seeps_threshold': (_plane(state, plan, quant[0], da.dims), dims),
-            'seeps_dry_fraction': (_plane(state, plan, dry, da.dims), dims)}
-  planes = [_plane(state, plan, quant[i], da.dims) for i in range(qs.size)]
+    return {'seeps_threshold': (_plane(lay, plan, quant[0]), dims),
+            'seeps_dry_fraction': (_plane(lay, plan, dry), dims)}
+  planes = [_plane(lay, plan, quant[i]) for i in range(qs.size)]
   at = 1 if plan.hours is not None else 0
   if np.ndim(owner.quantiles) == 0:
     return {'quantile': (planes[0], dims)}
-  stack = torch.stack if state['device'] is not None else np.stack
+  stack = torch.stack if device is not None else np.stack
   return {'quantile': (stack(planes, at),
                        dims[:at] + ('quantile',) + dims[at:])}
 
@@ -695,18 +650,12 @@ def _check_stat(stat_fn):
 def _time_values(obj, time_dim: str = 'time') -> np.ndarray:
   if time_dim not in obj.coords:
     raise ValueError(f'{time_dim!r} has no coordinate to group by')
-  c = obj.coords[time_dim]
-  return np.asarray(c.values if isinstance(c, xl.DataArray) else c)
+  return xl.coord_values(obj, time_dim)
 
 
 def _result_coords(coords: dict, plan: Plan, time_dim: str = 'time') -> dict:
-  out = {}
-  if plan.hours is not None:
-    out['hour'] = plan.hours
-  for k, c in coords.items():
-    if k == time_dim or (isinstance(c, xl.DataArray) and time_dim in c.dims):
-      continue
-    out[k] = c
+  out = {'hour': plan.hours} if plan.hours is not None else {}
+  out.update(xl.coords_without(coords, (time_dim,)))
   out['dayofyear'] = plan.axis
   return out
 
@@ -728,12 +677,11 @@ def _take_steps(da: xl.DataArray, steps: np.ndarray, times: np.ndarray,
   sl = [slice(None)] * len(da.dims)
   sl[ax] = index
   data = da.data
-  if dv._on_device(data) and not isinstance(data, torch.Tensor):
+  if operands.on_device(data) and not isinstance(data, torch.Tensor):
     data = data.materialize(engine.require_gpu())
   if isinstance(index, np.ndarray) and isinstance(data, torch.Tensor):
     sl[ax] = torch.from_numpy(index).to(data.device)
-  coords = {k: c for k, c in da.coords.items()
-            if not (isinstance(c, xl.DataArray) and time_dim in c.dims)}
+  coords = xl.coords_without(da.coords, (time_dim,))
   coords[time_dim] = times[steps]
   return xl.DataArray(data[tuple(sl)], da.dims, coords, da.name)
 
@@ -773,26 +721,22 @@ def _variable(da: xl.DataArray, times: np.ndarray, *, frequency: str,
   if frequency == 'hourly':
     plan = plan_groups(times, steps, method, hours_of(hour_interval))
     if moment:
-      state = _moments(da, 'time', plan)
-      out = _smooth(state, method, plan, w, moment, da.dims, 'time')
+      out = _smooth(_moments(da, 'time', plan), method, plan, w, moment)
     for owner in window:
       out[owner] = _window(da, 'time', plan, w, owner)
     return out, plan
   plan = None
   if method == 'fast' and 'mean' in statistics:
     plan = plan_groups(times, steps, 'fast')
-    state = _moments(da, 'time', plan)
-    out.update(_smooth(state, 'fast', plan, w, ['mean'], da.dims, 'time'))
+    out.update(_smooth(_moments(da, 'time', plan), 'fast', plan, w, ['mean']))
   rest = [s for s in statistics if s not in out]
   if rest:
     daily = _daily_mean(da, steps, times)
     days = np.asarray(daily.coords['time'])
     plan = plan_groups(days, np.arange(days.size), method)
     if [s for s in rest if isinstance(s, str)]:
-      state = _moments(daily, 'time', plan)
-      out.update(_smooth(state, method, plan, w,
-                         [s for s in rest if isinstance(s, str)], da.dims,
-                         'time'))
+      out.update(_smooth(_moments(daily, 'time', plan), method, plan, w,
+                         [s for s in rest if isinstance(s, str)]))
     for owner in window:
       out[owner] = _window(daily, 'time', plan, w, owner)
   return {s: out[s] for s in statistics}, plan
@@ -877,9 +821,8 @@ def compute_rolling_stat(ds, window_weights, stat_fn='mean'):
     plan = plan_groups(times, np.arange(times.size), 'explicit')
     if not isinstance(stat, str):
       return _window(da, 'time', plan, w, stat), plan
-    state = _moments(da, 'time', plan)
-    return _smooth(state, 'explicit', plan, w, [stat], da.dims,
-                   'time')[stat], plan
+    return _smooth(_moments(da, 'time', plan), 'explicit', plan, w,
+                   [stat])[stat], plan
 
   if isinstance(ds, xl.DataArray):
     if isinstance(stat, SEEPSThreshold):
@@ -942,31 +885,24 @@ def smooth_dayofyear_variable_with_rolling_window(obs_dayofyear,
     # the values as moments of one sample each: pivot + S / C is the value
     plan = Plan(np.zeros(1, np.int32), np.zeros(0, np.int32), None, 1,
                 da.sizes['dayofyear'], np.zeros(0, np.int64), None)
-    order, first = _layout(da, 'dayofyear')
-    shape = tuple(da.sizes[d] for d in order)
-    n_outer = int(np.prod(shape[:first], dtype=np.int64))
-    n_point = int(np.prod(shape[first + 1:], dtype=np.int64))
-    flat = (n_outer, shape[first], n_point)
-    state = {'order': order, 'first': first, 'shape': shape, 'device': None}
-    if dv._on_device(da.data):
+    lay = operands.SeriesLayout.of(da.dims, da.sizes, 'dayofyear')
+    flat = (lay.n_outer, lay.n_series, lay.n_point)
+    if operands.on_device(da.data):
       device = engine.require_gpu()
-      ten, _ = dv._operand(da, order, device, torch.float64, 0)
+      # the moments are new tensors, so the values are flattened, not tabled
+      ten, _ = operands.operand(da, lay.order, device, torch.float64, 0)
       ten = ten.contiguous().reshape(flat)
       nan = torch.isnan(ten)
-      state['device'] = device
-      state['moments'] = ((~nan).to(torch.float64),
-                          torch.where(nan, torch.zeros_like(ten), ten),
-                          torch.zeros_like(ten))
-      state['pivot'] = None
+      state = _Moments(lay, ((~nan).to(torch.float64),
+                             torch.where(nan, torch.zeros_like(ten), ten),
+                             torch.zeros_like(ten)), None)
     else:
-      v = np.transpose(np.asarray(da.values, dtype=np.float64),
-                       [da.dims.index(d) for d in order]).reshape(flat)
+      v = np.asarray(lay.host(da), dtype=np.float64)
       nan = np.isnan(v)
-      state['moments'] = ((~nan).astype(np.float64), np.where(nan, 0.0, v),
-                          np.zeros(flat))
-      state['pivot'] = np.zeros((n_outer, n_point))
-    return _smooth(state, 'fast', plan, w, ['mean'], da.dims,
-                   'dayofyear')['mean']
+      state = _Moments(lay, ((~nan).astype(np.float64), np.where(nan, 0.0, v),
+                             np.zeros(flat)),
+                       np.zeros((lay.n_outer, lay.n_point)))
+    return _smooth(state, 'fast', plan, w, ['mean'])['mean']
 
   if isinstance(obs_dayofyear, xl.DataArray):
     if 'dayofyear' not in obs_dayofyear.dims:

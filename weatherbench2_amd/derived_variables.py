@@ -47,6 +47,7 @@ import torch
 
 from weatherbench2_amd import engine
 from weatherbench2_amd import feeder
+from weatherbench2_amd import operands
 from weatherbench2_amd import plan as plan_lib
 from weatherbench2_amd import xarray_lite as xl
 
@@ -172,80 +173,6 @@ class ZonalEnergySpectrum(DerivedVariable):
 # ---------------------------------------------------------------------------
 # Materialising derived variables (csrc/derived_fields.hip)
 # ---------------------------------------------------------------------------
-def _on_device(data) -> bool:
-  if isinstance(data, xl.SlabGather):
-    data = data.base
-  elif isinstance(data, xl.SlabConcat):
-    data = data.bases[0]
-  return isinstance(data, torch.Tensor) and data.is_cuda
-
-
-def _float_dtype(*dtypes) -> torch.dtype:
-  """float32 if every input is float32, float64 otherwise (integers square
-  to integers and take their root in float64)."""
-  as_np = [np.dtype(str(d).replace('torch.', '')) if isinstance(d, torch.dtype)
-           else np.dtype(d) for d in dtypes]
-  return torch.float32 if all(d == np.float32 for d in as_np) else torch.float64
-
-
-def _coord_values(dataset: xl.Dataset, name: str) -> np.ndarray:
-  c = dataset.coords[name]
-  return np.asarray(c.values if isinstance(c, xl.DataArray) else c)
-
-
-def _stride_table(x: torch.Tensor, n_inner: int):
-  """Slab table of a strided view whose inner blocks (the last `n_inner` dims)
-  are contiguous and whose outer strides are whole blocks; None otherwise."""
-  n_outer = x.dim() - n_inner
-  inner, expect = 1, 1
-  for n, s in zip(reversed(x.shape[n_outer:]), reversed(x.stride()[n_outer:])):
-    if n != 1 and s != expect:
-      return None
-    expect *= n
-    inner *= n
-  if inner == 0 or any(s < 0 or s % inner for s in x.stride()[:n_outer]):
-    return None
-  table = np.zeros(tuple(x.shape[:n_outer]), dtype=np.int64)
-  for ax, (n, s) in enumerate(zip(x.shape[:n_outer], x.stride()[:n_outer])):
-    shape = [1] * n_outer
-    shape[ax] = n
-    table = table + (np.arange(n, dtype=np.int64) * (s // inner)).reshape(shape)
-  return table.ravel()
-
-
-def _operand(da: xl.DataArray, order: tuple, device, dtype: torch.dtype,
-             n_inner: int):
-  """(device tensor, slab table or None) of `da` with its dims in `order`:
-  read where it lies when its blocks of the last `n_inner` dims are intact (a
-  contiguous tensor, a strided view of whole blocks, a gather over a resident
-  base), copied otherwise."""
-  if da.dims != tuple(order):
-    da = da.transpose(*order)
-  data = da.data
-  if (isinstance(data, xl.SlabGather) and n_inner == 2
-      and isinstance(data.base, torch.Tensor) and data.base.is_cuda
-      and data.base.dtype == dtype and data.base.is_contiguous()
-      and not data.has_missing):
-    return data.base, data.index.ravel()
-  if isinstance(data, (xl.SlabGather, xl.SlabConcat)):
-    data = data.materialize(device)
-  if isinstance(data, torch.Tensor) and data.device == device:
-    ten = data if data.dtype == dtype else data.to(dtype)
-  else:
-    ten = engine.as_device_tensor(data, device)
-    ten = ten if ten.dtype == dtype else ten.to(dtype)
-  if ten.is_contiguous():
-    return ten, None
-  table = _stride_table(ten, n_inner)
-  if table is None:
-    return ten.contiguous(), None
-  return ten, table
-
-
-def _table_tensor(table, device):
-  return None if table is None else engine.upload_table(table, device)
-
-
 def _result_coords(dataset: xl.Dataset, dims: tuple) -> dict:
   return {k: v for k, v in dataset.coords.items()
           if (set(v.dims) <= set(dims) if isinstance(v, xl.DataArray)
@@ -266,8 +193,8 @@ class _MaterializedVariable(DerivedVariable):
       return xl.like_input(self.compute(xl.as_dataset(dataset)), dataset)
     dataset = xl.as_dataset(dataset)
     result = self.compute_on_device(dataset)
-    if any(_on_device(dataset[name].data) for name in self.base_variables
-           if name in dataset.data_vars):
+    if any(operands.on_device(dataset[name].data)
+           for name in self.base_variables if name in dataset.data_vars):
       return result
     engine.order_read(result.data)
     return xl.DataArray(feeder.download(result.data.contiguous()), result.dims,
@@ -292,7 +219,7 @@ def _pointwise(mode: str, dataset: xl.Dataset, a_name: str, b_name: str,
     raise ValueError(f'{a_name} {das[0].dims} and {b_name} {das[1].dims} must '
                      'have the same dims')
   sizes = das[order_of].sizes
-  dtype = _float_dtype(das[0].dtype, das[1].dtype)
+  dtype = operands.float_dtype(das[0].dtype, das[1].dtype)
   out_dtype, n_inner, pressure = dtype, min(2, len(order)), None
   if pressure_name is not None:
     p = dataset[pressure_name]  # the COORDINATE, broadcast by name (:464)
@@ -300,7 +227,7 @@ def _pointwise(mode: str, dataset: xl.Dataset, a_name: str, b_name: str,
     if missing:
       raise ValueError(f'{pressure_name} dims {missing} not in {order}')
     pvals = np.asarray(p.values)
-    out_dtype = _float_dtype(dtype, pvals.dtype)
+    out_dtype = operands.float_dtype(dtype, pvals.dtype)
     # a block = the trailing dims the pressure does not vary along
     last = max([order.index(d) for d in p.dims], default=-1)
     n_inner = len(order) - 1 - last
@@ -308,7 +235,7 @@ def _pointwise(mode: str, dataset: xl.Dataset, a_name: str, b_name: str,
     pvals = np.transpose(pvals, [p.dims.index(d) for d in outer if d in p.dims])
     pvals = pvals.reshape([sizes[d] if d in p.dims else 1 for d in outer])
     pressure = np.broadcast_to(pvals, [sizes[d] for d in outer]).ravel()
-  ops = [_operand(da, order, device, dtype, n_inner) for da in das]
+  ops = [operands.operand(da, order, device, dtype, n_inner) for da in das]
   shape = tuple(sizes[d] for d in order)
   n_point = int(np.prod(shape[len(order) - n_inner:], dtype=np.int64))
   n_slab = int(np.prod(shape[:len(order) - n_inner], dtype=np.int64))
@@ -326,8 +253,8 @@ def _pointwise(mode: str, dataset: xl.Dataset, a_name: str, b_name: str,
     scalar = engine.upload_table(host.view(np.int64), device).view(out_dtype)[
         :n_slab]
   out = engine.derived_pointwise(
-      mode, ops[0][0], _table_tensor(ops[0][1], device), ops[1][0],
-      _table_tensor(ops[1][1], device), n_slab, n_point, out_dtype,
+      mode, ops[0][0], operands.table_tensor(ops[0][1], device), ops[1][0],
+      operands.table_tensor(ops[1][1], device), n_slab, n_point, out_dtype,
       scalar).reshape(shape)
   return xl.DataArray(out, order, _result_coords(dataset, order))
 
@@ -427,19 +354,21 @@ def _stencil_launch(mode: str, dataset: xl.Dataset, names: t.Sequence[str],
     raise ValueError(f'{names[lead]}: needs latitude and longitude, has {dims}')
   order = tuple(d for d in dims if d not in spatial) + spatial
   (row_coef, row_uniform), (col_coef, col_uniform), lat_tables = _stencil_tables(
-      _coord_values(dataset, spatial[0]), _coord_values(dataset, spatial[1]),
-      _coord_values(dataset, 'latitude'))
-  dtype = _float_dtype(*[da.dtype for da in das])
+      xl.coord_values(dataset, spatial[0]),
+      xl.coord_values(dataset, spatial[1]),
+      xl.coord_values(dataset, 'latitude'))
+  dtype = operands.float_dtype(*[da.dtype for da in das])
   seen: dict = {}
   ops = []
   for n, da in zip(names, das):  # (the geostrophic modes name one field twice)
     if n not in seen:
-      seen[n] = _operand(da, order, device, dtype, 2)
+      seen[n] = operands.operand(da, order, device, dtype, 2)
     ops.append(seen[n])
   sizes = das[lead].sizes
   shape = tuple(sizes[d] for d in order)
   n_slab = int(np.prod(shape[:-2], dtype=np.int64))
-  tabs = {n: _table_tensor(tab, device) for n, (_, tab) in seen.items()}
+  tabs = {n: operands.table_tensor(tab, device)
+          for n, (_, tab) in seen.items()}
   out = engine.derived_stencil(
       mode, [x for x, _ in ops], [tabs[n] for n in names], n_slab, shape[-2],
       shape[-1], spatial[0] == 'latitude',
@@ -587,7 +516,7 @@ def _level_values(dataset: xl.Dataset, dims: tuple, name: str) -> np.ndarray:
     raise ValueError(f"{name}: needs a 'level' dim, has {dims}")
   if 'level' not in dataset.coords:
     raise ValueError(f"{name}: the dataset has no 'level' coordinate")
-  level = _coord_values(dataset, 'level')
+  level = xl.coord_values(dataset, 'level')
   if level.ndim != 1 or level.dtype.kind not in 'iuf':
     raise ValueError(f"{name}: 'level' must be a 1-D numeric coordinate")
   return level
@@ -661,14 +590,14 @@ def _columns(dataset: xl.Dataset, names: t.Sequence[str],
   sizes = das[0].sizes
   shape = tuple(sizes[d] for d in order)
   n_outer = len(order) - n_inner
-  dtype = _float_dtype(*[da.dtype for da in das])
+  dtype = operands.float_dtype(*[da.dtype for da in das])
   n_level = shape[at]
   n_point = int(np.prod(shape[n_outer:], dtype=np.int64))
   n_column = int(np.prod(shape[:n_outer], dtype=np.int64)) // max(n_level, 1)
   tensors, tables, seen = [], [], {}
   for n, da in zip(names, das):
     if n not in seen:
-      ten, table = (_operand(da, order, device, dtype, n_inner)
+      ten, table = (operands.operand(da, order, device, dtype, n_inner)
                     if n_column * n_level * n_point else (None, None))
       if table is None:
         table = np.arange(n_column * n_level, dtype=np.int64)
@@ -711,7 +640,7 @@ def _column_integral(mode: str, dataset: xl.Dataset, names: t.Sequence[str],
   if mode == 'eddy' and 'longitude' not in dims:
     raise ValueError(f"{label}: needs a 'longitude' dim, has {dims}")
   cols = _columns(dataset, names, spatial_last=mode == 'eddy')
-  out_dtype = _float_dtype(cols.dtype, level.dtype)
+  out_dtype = operands.float_dtype(cols.dtype, level.dtype)
   if cols.n_column * cols.n_point == 0:
     out = torch.empty((cols.n_column, cols.n_point), dtype=out_dtype,
                       device=cols.device)
@@ -887,33 +816,24 @@ def _lead_window(mode: str, dataset: xl.Dataset, name: str, lead_name: str,
   after `lead_name` form the block of points a lead is read in, the dims
   before it index the outer slabs, read where they lie through the slab table
   (a contiguous tensor needs none).  `lead_name` as the innermost of several
-  dims is moved to the front (a copy).  The result has the field's dims."""
+  dims is moved to the front (a copy): `operands.SeriesLayout`.  The result
+  has the field's dims."""
   da = dataset[name]
   dims = tuple(da.dims)
   if lead_name not in dims:
     raise ValueError(f'{name}: needs a {lead_name!r} dim, has {dims}')
   device = engine.require_gpu()
-  order = dims
-  if len(dims) > 1 and dims[-1] == lead_name:
-    order = (lead_name,) + dims[:-1]
-  at = order.index(lead_name)
-  n_inner = len(order) - 1 - at
-  sizes = da.sizes
-  shape = tuple(sizes[d] for d in order)
-  dtype = _float_dtype(da.dtype)
-  n_lead = shape[at]
-  n_outer = int(np.prod(shape[:at], dtype=np.int64))
-  n_point = int(np.prod(shape[at + 1:], dtype=np.int64))
+  lay = operands.SeriesLayout.of(dims, da.sizes, lead_name)
+  dtype = operands.float_dtype(da.dtype)
+  n_outer, n_lead, n_point = lay.n_outer, lay.n_series, lay.n_point
   if n_outer * n_lead * n_point == 0:
-    out = torch.empty(shape, dtype=dtype, device=device)
+    out = torch.empty(lay.shape, dtype=dtype, device=device)
   else:
-    ten, table = _operand(da, order, device, dtype, n_inner)
-    out = engine.derived_lead_window(
-        mode, ten, _table_tensor(table, device), n_outer, n_lead, n_point,
-        window, clamp_negative).reshape(shape)
-  if order != dims:
-    out = out.permute(*[order.index(d) for d in dims])
-  return xl.DataArray(out, dims, _result_coords(dataset, dims))
+    ten, table = lay.operand(da, device, dtype)
+    out = engine.derived_lead_window(mode, ten, table, n_outer, n_lead,
+                                     n_point, window, clamp_negative)
+  return xl.DataArray(lay.restore(out, (n_lead,)), dims,
+                      _result_coords(dataset, dims))
 
 
 def _whole_steps(numerator, denominator) -> int:
@@ -955,7 +875,7 @@ class PrecipitationAccumulation(_MaterializedVariable):
       raise ValueError(
           f'PrecipitationAccumulation: the dataset has no {lead_name!r} '
           'coordinate to take the time step from')
-    lead = _coord_values(dataset, lead_name)
+    lead = xl.coord_values(dataset, lead_name)
     if lead.ndim != 1 or lead.size < 2:
       raise ValueError(
           f'PrecipitationAccumulation: {lead_name!r} holds {lead.size} lead '

@@ -1736,9 +1736,7 @@ def _with_derived(dataset: xl.Dataset, derived: dict) -> xl.Dataset:
 # Baseline substitutions (evaluation.py:165-193, 452-472, 618-675;
 # utils.py:47-70): label work on the host, the data stays where it is
 # ---------------------------------------------------------------------------
-def _index_values(ds: xl.Dataset, name: str) -> np.ndarray:
-  c = ds.coords[name]
-  return np.asarray(c.values if isinstance(c, xl.DataArray) else c)
+_index_values = xl.coord_values
 
 
 def _positions(have: np.ndarray, want: np.ndarray, what: str) -> np.ndarray:

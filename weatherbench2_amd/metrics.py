@@ -500,9 +500,7 @@ def _slab_table(out_dims, out_shape, in_dims, in_shape, extra=None):
   return np.ascontiguousarray(table).ravel()
 
 
-def _coord_values(ds: xl.Dataset, name: str) -> np.ndarray:
-  c = ds.coords[name]
-  return np.asarray(c.values if isinstance(c, xl.DataArray) else c)
+_coord_values = xl.coord_values
 
 
 def _geometry(forecast: xl.Dataset, fvar: xl.DataArray, others) -> tuple:

@@ -34,8 +34,8 @@ import typing as t
 import numpy as np
 import torch
 
-from weatherbench2_amd import derived_variables as dv
 from weatherbench2_amd import engine
+from weatherbench2_amd import operands
 from weatherbench2_amd import xarray_lite as xl
 
 QUANTILE_DIM = 'quantile'
@@ -54,46 +54,31 @@ def _dims_list(dim, have) -> list:
 def _skip(skipna, dtype) -> bool:
   """xarray's default: skip NaN for floating data."""
   if skipna is None:
-    kind = (np.dtype(str(dtype).replace('torch.', ''))
-            if isinstance(dtype, torch.dtype) else np.dtype(dtype)).kind
-    return kind in 'fc'
+    return operands.numpy_dtype(dtype).kind in 'fc'
   return bool(skipna)
 
 
 def _device_quantile(da: xl.DataArray, qs: np.ndarray, reduced: list,
                      skipna: bool) -> tuple:
   """(device tensor [n_q, *preserved shape], preserved dims)."""
-  dims = tuple(da.dims)
-  keep = tuple(d for d in dims if d not in reduced)
-  at = [dims.index(d) for d in reduced]
-  adjacent = at == list(range(at[0], at[0] + len(at)))
-  if adjacent and at[-1] < len(dims) - 1:
-    order = dims  # read where it lies
-    first = at[0]
-  else:
-    order = tuple(d for d in dims if d in reduced) + keep
-    first = 0
-  n_inner_dims = len(order) - first - len(reduced)
-  sizes = da.sizes
-  shape = tuple(sizes[d] for d in order)
-  n_outer = int(np.prod(shape[:first], dtype=np.int64))
-  n_red = int(np.prod(shape[first:first + len(reduced)], dtype=np.int64))
-  n_inner = int(np.prod(shape[first + len(reduced):], dtype=np.int64))
+  keep = tuple(d for d in da.dims if d not in reduced)
+  lay = operands.SeriesLayout.of(da.dims, da.sizes, reduced)
+  n_outer, n_red, n_inner = lay.n_outer, lay.n_series, lay.n_point
   if n_red == 0:
     raise ValueError(f'cannot take a quantile over {reduced}: no samples')
   device = engine.require_gpu()
-  dtype = dv._float_dtype(da.dtype)
-  out_shape = (len(qs),) + tuple(sizes[d] for d in keep)
   if n_outer * n_inner == 0:
-    return torch.empty(out_shape, dtype=torch.float64, device=device), keep
-  if n_inner_dims == 0:  # every dim reduced
-    ten, table = dv._operand(da, order, device, dtype, 0)
+    out = torch.empty((len(qs), n_outer, n_inner), dtype=torch.float64,
+                      device=device)
+    return lay.restore(out, (), (len(qs),)), keep
+  dtype = operands.float_dtype(da.dtype)
+  if lay.n_inner_dims == 0:  # every dim reduced: flattened, no table
+    ten, _ = operands.operand(da, lay.order, device, dtype, 0)
     ten, table = ten.contiguous(), None
   else:
-    ten, table = dv._operand(da, order, device, dtype, n_inner_dims)
-  out = engine.quantile_select(ten, dv._table_tensor(table, device), n_outer,
-                               n_red, n_inner, qs, skipna)
-  return out.reshape(out_shape), keep
+    ten, table = lay.operand(da, device, dtype)
+  out =engine.quantile_select(ten, table, n_outer, n_red, n_inner, qs, skipna)
+  return lay.restore(out, (), (len(qs),)), keep
 
 
 def _host_quantile(da: xl.DataArray, qs: np.ndarray, reduced: list,
@@ -117,7 +102,7 @@ def _array_quantile(da: xl.DataArray, q, reduced: list, skipna,
   if not np.all((qs >= 0) & (qs <= 1)):
     raise ValueError('Quantiles must be in the range [0, 1]')
   skip = _skip(skipna, da.dtype)
-  if dv._on_device(da.data):
+  if operands.on_device(da.data):
     out, keep = _device_quantile(da, qs, reduced, skip)
   else:
     out, keep = _host_quantile(da, qs, reduced, skip)

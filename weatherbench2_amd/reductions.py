@@ -79,24 +79,14 @@ def _moments(da: xl.DataArray, dims: t.Sequence[str], skipna: bool,
   return rs(total), rs(sq), rs(count), keep, x.dtype
 
 
-def _coords_without(ds: xl.Dataset, dims) -> dict:
-  out = {}
-  for k, c in ds.coords.items():
-    if k in dims:
-      continue
-    if isinstance(c, xl.DataArray) and any(d in dims for d in c.dims):
-      continue
-    out[k] = c
-  return out
-
-
 @_like_input
 def mean(dataset, dims: t.Sequence[str], skipna: bool = False) -> xl.Dataset:
   """`dataset.mean(dims, skipna)`: variables lacking a dim are averaged over
   the ones they have; results keep the input dtype, like xarray."""
   ds = xl.as_dataset(dataset)
   dims = (dims,) if isinstance(dims, str) else tuple(dims)
-  out = xl.Dataset(coords=_coords_without(ds, dims), attrs=dict(ds.attrs))
+  out = xl.Dataset(coords=xl.coords_without(ds.coords, dims),
+                   attrs=dict(ds.attrs))
   for name, da in ds.data_vars.items():
     if not any(d in da.dims for d in dims):
       out.data_vars[name] = da
@@ -130,7 +120,7 @@ def averages(dataset, averaging_dims: t.Sequence[str],
   if 'latitude' in averaging_dims:
     weights = {'latitude': plan_lib.get_lat_weights(
         np.asarray(ds.coords['latitude']))}
-  out = xl.Dataset(coords=_coords_without(ds, averaging_dims),
+  out = xl.Dataset(coords=xl.coords_without(ds.coords, averaging_dims),
                    attrs=dict(ds.attrs))
   for name, da in ds.data_vars.items():
     if not any(d in da.dims for d in averaging_dims):
@@ -155,7 +145,7 @@ def statistical_moments(dataset,
   (compute_statistical_moments.py:52-80) -- from ONE read of each variable."""
   ds = xl.as_dataset(dataset)
   reduce_dims = tuple(reduce_dims)
-  out = xl.Dataset(coords=_coords_without(ds, reduce_dims),
+  out = xl.Dataset(coords=xl.coords_without(ds.coords, reduce_dims),
                    attrs=dict(ds.attrs))
   for name, da in ds.data_vars.items():
     total, sq, count, keep, dtype = _moments(da, reduce_dims, True,

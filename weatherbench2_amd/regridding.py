@@ -30,6 +30,9 @@ import typing as t
 import numpy as np
 import torch
 
+from weatherbench2_amd import engine
+from weatherbench2_amd import feeder
+from weatherbench2_amd import operands
 from weatherbench2_amd import xarray_lite as xl
 
 Array = t.Union[np.ndarray, torch.Tensor]
@@ -382,8 +385,6 @@ class Regridder:
     """`x`: (..., lat, lon) when lat_rows else (..., lon, lat), on the device,
     in its compute dtype; `table` its slab table and `outer` the leading
     shape where the slabs are picked from `x` (a view, a gather)."""
-    from weatherbench2_amd import derived_variables as dv
-    from weatherbench2_amd import engine
     n_lon, n_lat = self.source.shape
     want = (n_lat, n_lon) if lat_rows else (n_lon, n_lat)
     if tuple(x.shape[-2:]) != want:
@@ -391,11 +392,11 @@ class Regridder:
                        f'grid\'s {want}')
     outer = tuple(x.shape[:-2]) if outer is None else tuple(outer)
     if table is None and not x.is_contiguous():
-      table = dv._stride_table(x, 2)
+      table = operands.stride_table(x, 2)
       if table is None:
         x = x.contiguous()
     n_slab = int(np.prod(outer, dtype=np.int64))
-    slab = None if table is None else engine.upload_table(table, x.device)
+    slab = operands.table_tensor(table, x.device)
     out = self._device_regrid(x, slab, n_slab, lat_rows, lat_reversed)
     t_lon, t_lat = self.target.shape
     return out.reshape(outer + ((t_lat, t_lon) if lat_rows else (t_lon, t_lat)))
@@ -404,8 +405,6 @@ class Regridder:
     """Regrid an array with dimensions (..., lon, lat) from source to target:
     a device tensor stays on the device, a NumPy array (or a host tensor)
     comes back as NumPy (a host tensor)."""
-    from weatherbench2_amd import engine
-    from weatherbench2_amd import feeder
     shape = tuple(np.shape(field))
     if shape[-2:] != self.source.shape:
       raise ValueError(f'expected {shape=} to match {self.source.shape=}')
@@ -431,20 +430,14 @@ class Regridder:
     target's coordinates and every variable keeps its own dimension order;
     variables without both horizontal dims pass through unchanged.  Device
     data stays on the device, host data comes back on the host."""
-    from weatherbench2_amd import derived_variables as dv
-    from weatherbench2_amd import engine
-    from weatherbench2_amd import feeder
     if xl.is_xarray(dataset):
       return xl.like_input(self.regrid_dataset(xl.as_dataset(dataset)), dataset)
     ds = xl.as_dataset(dataset)
-    lat = np.asarray(dv._coord_values(ds, 'latitude'))
+    lat = xl.coord_values(ds, 'latitude')
     reverse = not (np.diff(lat) > 0).all()
     if reverse:
       _assert_increasing(lat[::-1])
-    coords = {k: v for k, v in ds.coords.items()
-              if k not in _HORIZONTAL
-              and not (isinstance(v, xl.DataArray)
-                       and set(_HORIZONTAL) & set(v.dims))}
+    coords = xl.coords_without(ds.coords, _HORIZONTAL)
     coords['latitude'] = np.asarray(self.target.latitudes)
     coords['longitude'] = np.asarray(self.target.longitudes)
     out = xl.Dataset(coords=coords, attrs=dict(ds.attrs))
@@ -458,26 +451,20 @@ class Regridder:
       device = device or engine.require_gpu()
       pair = tuple(d for d in da.dims if d in _HORIZONTAL)
       order = tuple(d for d in da.dims if d not in _HORIZONTAL) + pair
-      dtype = self._compute_dtype(_torch_dtype(da.dtype))
-      x, table = dv._operand(da, order, device, dtype, 2)
+      dtype = self._compute_dtype(operands.torch_dtype(da.dtype))
+      x, table = operands.operand(da, order, device, dtype, 2)
       res = self._run(x, lat_rows=pair[0] == 'latitude', lat_reversed=reverse,
                       table=table,
                       outer=tuple(da.sizes[d] for d in order[:-2]))
       res_da = xl.DataArray(res, order, coords, name)
       if order != da.dims:
         res_da = res_da.transpose(*da.dims)
-      if not dv._on_device(da.data):
+      if not operands.on_device(da.data):
         engine.order_read(res_da.data)
         res_da = xl.DataArray(feeder.download(res_da.data.contiguous()),
                               da.dims, coords, name)
       out.data_vars[name] = xl.DataArray(res_da.data, da.dims, coords, name)
     return out
-
-
-def _torch_dtype(dtype) -> torch.dtype:
-  if isinstance(dtype, torch.dtype):
-    return dtype
-  return torch.from_numpy(np.empty(0, dtype=np.dtype(dtype))).dtype
 
 
 class _SeparableRegridder(Regridder):
@@ -506,7 +493,6 @@ class _SeparableRegridder(Regridder):
     return cache[key]
 
   def _device_regrid(self, x, slab, n_slab, lat_rows, lat_reversed):
-    from weatherbench2_amd import engine
     tables = self._tables_on(x.device, lat_reversed)
     return engine.regrid_separable(self._MODE, x, slab, n_slab, lat_rows,
                                    self.source.shape, self.target.shape,
@@ -577,7 +563,6 @@ class NearestRegridder(Regridder):
     return cache[key]
 
   def _device_regrid(self, x, slab, n_slab, lat_rows, lat_reversed):
-    from weatherbench2_amd import engine
     n_lon, n_lat = self.source.shape
     return engine.regrid_gather(
         x, slab, n_slab, n_lon * n_lat,

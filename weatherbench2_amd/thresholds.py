@@ -20,9 +20,7 @@ from scipy import stats
 from weatherbench2_amd import xarray_lite as xl
 
 
-def _coord(ds: xl.Dataset, name: str) -> np.ndarray:
-  c = ds.coords[name]
-  return np.asarray(c.values if isinstance(c, xl.DataArray) else c)
+_coord = xl.coord_values
 
 
 def _positions(have: np.ndarray, want: np.ndarray, what: str) -> np.ndarray:

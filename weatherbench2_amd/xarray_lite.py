@@ -726,6 +726,20 @@ def merge(datasets: t.Sequence[Dataset]) -> Dataset:
   return out
 
 
+def coord_values(obj, name: str) -> np.ndarray:
+  """The coordinate `name` of a Dataset or DataArray as a NumPy array."""
+  c = obj.coords[name]
+  return np.asarray(c.values if isinstance(c, DataArray) else c)
+
+
+def coords_without(coords: dict, dims) -> dict:
+  """The coordinates that touch none of `dims`: neither named after one nor
+  (a DataArray) lying along one."""
+  return {k: c for k, c in coords.items()
+          if k not in dims and not (isinstance(c, DataArray)
+                                    and any(d in dims for d in c.dims))}
+
+
 def _index_or_slice(idx: np.ndarray):
   """A contiguous ascending run becomes a slice (a view, no copy)."""
   if len(idx) and np.array_equal(idx, np.arange(idx[0], idx[0] + len(idx))):

@@ -449,10 +449,32 @@ class _Geometry:
   out_shape: tuple
   latitude: np.ndarray
   longitude: np.ndarray
+  # {region key: total weight} of the pass that used this geometry (_ens_pass:
+  # a spatial average of zeros is 0/0 = NaN over a region without weight)
+  region_wsum: t.Optional[dict] = None
 
   @property
   def n_outer(self):
     return int(np.prod(self.out_shape, dtype=np.int64))
+
+  @property
+  def spatial_dims(self):
+    return _spatial_dims(self.layout)
+
+
+def _spatial_dims(layout: str) -> tuple:
+  """The two spatial dims in the order the slabs of `layout` hold them."""
+  return _SPATIAL if layout == plan_lib.LATLON else _SPATIAL[::-1]
+
+
+def _time_average_dim(forecast: xl.Dataset) -> str:
+  """The dim `Metric.compute` averages over (metrics.py:117-138)."""
+  if 'time' in forecast.dims:
+    return 'time'
+  if 'init_time' in forecast.dims:
+    return 'init_time'
+  raise ValueError(
+      f'Forecast has neither valid_time or init_time dimension {forecast}')
 
 
 def _spatial_last(da: xl.DataArray, layout: t.Optional[str]):
@@ -464,7 +486,7 @@ def _spatial_last(da: xl.DataArray, layout: t.Optional[str]):
   tail = tuple(d for d in da.dims if d in _SPATIAL)
   if layout is None:
     layout = plan_lib.LATLON if tail == _SPATIAL else plan_lib.LONLAT
-  want = _SPATIAL if layout == plan_lib.LATLON else _SPATIAL[::-1]
+  want = _spatial_dims(layout)
   if da.dims[-2:] == want:
     return da.data, rest, layout
   moved = da.transpose(*rest, *want)
@@ -524,12 +546,101 @@ def _geometry(forecast: xl.Dataset, fvar: xl.DataArray, others) -> tuple:
   return geo, prepared
 
 
+def _operand_tables(geo: _Geometry, prepared, out_dims=None, out_shape=None):
+  """The slab table of every `(data, dims)` operand of `_geometry`, for the
+  output dims of `geo` -- or for a reordering of them (`out_dims, out_shape`)."""
+  if out_dims is None:
+    out_dims, out_shape = geo.out_dims, geo.out_shape
+  return [_slab_table(out_dims, out_shape, rest, data.shape[:-2])
+          for data, rest in prepared]
+
+
 def _check_grid(geo: _Geometry, data) -> None:
   n_lat, n_lon = len(geo.latitude), len(geo.longitude)
   want = (n_lat, n_lon) if geo.layout == plan_lib.LATLON else (n_lon, n_lat)
   if tuple(data.shape[-2:]) != want:
     raise ValueError(f'spatial shape {tuple(data.shape[-2:])} does not match '
                      f'the coordinates {want}')
+
+
+def _common_float(geo: _Geometry, tensors) -> tuple:
+  """(the operands of a pass in ONE dtype, that dtype): torch's promotion over
+  all of them, float64 for whatever is not float32 / float64 (integers, half
+  floats); only what differs is cast, and every operand must fit the grid."""
+  dtype = tensors[0].dtype
+  for x in tensors[1:]:
+    dtype = torch.promote_types(dtype, x.dtype)
+  if dtype not in (torch.float32, torch.float64):
+    dtype = torch.float64
+
+  def cast(x):
+    if x.dtype == dtype:
+      return x
+    if isinstance(x, (xl.SlabGather, xl.SlabConcat)):
+      x = x.materialize()  # never convert a whole resident base
+    return x.to(dtype)
+  tensors = [cast(x) for x in tensors]
+  for x in tensors:
+    _check_grid(geo, x)
+  return tensors, dtype
+
+
+@dataclasses.dataclass
+class _EnsOuter:
+  """Host layout of one ensemble variable: member m of outer index o is slab
+  m * strides[ensemble dim] + ens_table()[o]  of the forecast array."""
+  geo: _Geometry
+  prepared: list     # [(data, non-spatial dims)]: the forecast, then the others
+  ensemble_dim: str
+  n_member: int
+  strides: dict      # forecast dim -> slabs per step, C order
+
+  def ens_table(self, strides: t.Optional[dict] = None) -> np.ndarray:
+    """int64[n_outer]: member 0's slab of every outer index (`strides`: those
+    of a strided view instead of the C-order ones)."""
+    strides = self.strides if strides is None else strides
+    out_dims, out_shape = self.geo.out_dims, self.geo.out_shape
+    frest = self.prepared[0][1]
+    table = np.zeros(out_shape, dtype=np.int64)
+    for d, n in zip(frest, self.prepared[0][0].shape[:-2]):
+      if d == self.ensemble_dim:
+        continue
+      shape = [1] * len(out_shape)
+      shape[out_dims.index(d)] = n
+      table = table + (np.arange(n, dtype=np.int64) * strides[d]).reshape(shape)
+    return np.ascontiguousarray(table).ravel()
+
+
+def _ens_outer_layout(forecast, fvar, others, ensemble_dim) -> _EnsOuter:
+  """What every ensemble layout starts from (label and shape work only, no
+  device): the output dims are the forecast's without the ensemble dim, then
+  the unseen dims of `others` = [truth, ...] in their order."""
+  if ensemble_dim not in fvar.dims:
+    raise ValueError(f'{ensemble_dim=} not found in {fvar.dims=}')
+  fdata, frest, layout = _spatial_last(fvar, None)
+  prepared = [(fdata, frest)]
+  for i, da in enumerate(others):
+    data, rest, _ = _spatial_last(da, layout)
+    if i == 0 and ensemble_dim in rest:
+      raise ValueError(f'truth must not have the ensemble dim {ensemble_dim!r}')
+    prepared.append((data, rest))
+  fsizes = dict(zip(frest, fdata.shape[:-2]))
+  out_dims = [d for d in frest if d != ensemble_dim]
+  sizes = {d: fsizes[d] for d in out_dims}
+  for data, rest in prepared[1:]:
+    for d, n in zip(rest, data.shape[:-2]):
+      if d not in out_dims:
+        out_dims.append(d)
+        sizes[d] = n
+  out_dims = tuple(out_dims)
+  geo = _Geometry(layout, out_dims, tuple(sizes[d] for d in out_dims),
+                  _coord_values(forecast, 'latitude'),
+                  _coord_values(forecast, 'longitude'))
+  stride, strides = 1, {}
+  for d in reversed(frest):
+    strides[d] = stride
+    stride *= fsizes[d]
+  return _EnsOuter(geo, prepared, ensemble_dim, fsizes[ensemble_dim], strides)
 
 
 # ---------------------------------------------------------------------------
@@ -845,22 +956,8 @@ def _prepare_inputs(geo, arrays, tables, device):
       n_slab = a.size // max(a.shape[-1] * a.shape[-2], 1)
       if len(np.unique(tb)) < n_slab:
         arrays[i], tables[i] = xl.SlabGather(a, tb), None
-  tensors = [_to_device(a, device, allow_gather=True) for a in arrays]
-  dtype = tensors[0].dtype
-  for x in tensors[1:]:
-    dtype = torch.promote_types(dtype, x.dtype)
-  if dtype not in (torch.float32, torch.float64):
-    dtype = torch.float64
-
-  def cast(x):
-    if x.dtype == dtype:
-      return x
-    if isinstance(x, (xl.SlabGather, xl.SlabConcat)):
-      x = x.materialize()  # never convert a whole resident base
-    return x.to(dtype)
-  tensors = [cast(x) for x in tensors]
-  for x in tensors:
-    _check_grid(geo, x)
+  tensors, dtype = _common_float(
+      geo, [_to_device(a, device, allow_gather=True) for a in arrays])
   return tensors, tables, dtype
 
 
@@ -1097,6 +1194,53 @@ def _result_key(kind, arrays, region_key_obj, skipna, datasets=()):
           bool(skipna))
 
 
+def _cached_pass(key, pins, compute):
+  """The result of a fused pass under `key`: a lookup, or `compute()` once --
+  kept together with `pins`, the objects whose identity the key names."""
+  hit = _RESULTS.get(key)
+  if hit is None:
+    hit = compute()
+    _RESULTS.put(key, pins, hit)
+  return hit
+
+
+def _regional_pass(geo, region, device, rows_per_chunk, n_metric, launch):
+  """One launch over the active regions: `launch(plan)` -> metrics[n_metric,
+  n_region * n_outer]; returns {region key: metrics[n_metric, ...]}."""
+  regions, _ = _region_set_for(region)
+  pl = plan_lib.cached_plan(geo.latitude, geo.longitude, geo.layout, regions,
+                            device, rows_per_chunk)
+  dev = launch(pl).reshape((n_metric, pl.n_region) + geo.out_shape)
+  # total weight of each region: a spatial average of zeros is 0/0 = NaN over
+  # an empty region (CRPSSpread with one member, metrics.py:689-693, 783-784)
+  geo.region_wsum = dict(zip(pl.region_names,
+                             (float(w) for w in pl.region_wsum_host)))
+  return {nm: dev[:, i] for i, nm in enumerate(pl.region_names)}
+
+
+def _climatology_operand(climatology, cvar, forecast, geo):
+  """(data, non-spatial dims, slab table) of a climatology variable read by
+  the valid times of `forecast` (ACC's climatology, SEEPS' wet threshold)."""
+  crest = tuple(d for d in cvar.dims if d not in _SPATIAL)
+  cdata, _, _ = _spatial_last(cvar, geo.layout)
+  ctable = _climatology_slabs(climatology, cvar, forecast, geo, crest)
+  rec = program.recorder()
+  if rec is not None and not rec.probe:
+    # how another chunk of this structure gets ITS table (program.py);
+    # variables with the same climatology dims share one table per chunk
+    sizes = tuple(cvar.sizes[d] for d in crest)
+
+    def recompute(other, memo):
+      key = (id(climatology), crest, sizes, geo.out_dims, geo.out_shape)
+      if key not in memo:
+        memo[key] = _climatology_slabs_by_content(climatology, cvar, other,
+                                                  geo, crest)
+      return memo[key]
+    rec.note_table(ctable, recompute, _climatology_gather(
+        climatology, cvar, forecast, geo, crest))
+  return cdata, crest, ctable
+
+
 def _fuse_variables() -> bool:
   """Inside a chunk scope the first variable asked for brings every variable
   of the chunk along (WB2HIP_FUSE_VARIABLES=0: one launch per variable, the
@@ -1123,29 +1267,12 @@ def _det_plan(forecast, truth, name, climatology):
       climatology, cvar = None, None
   pins = [fvar.data, tvar.data]
   geo, prepared = _geometry(forecast, fvar, [tvar])
-  tables = [_slab_table(geo.out_dims, geo.out_shape, p[1], p[0].shape[:-2])
-            for p in prepared]
+  tables = _operand_tables(geo, prepared)
   mode = _lib.MODE_DET
   if cvar is not None:
     try:
-      crest = tuple(d for d in cvar.dims if d not in _SPATIAL)
-      cdata, _, _ = _spatial_last(cvar, geo.layout)
-      ctable = _climatology_slabs(climatology, cvar, forecast, geo, crest)
-      rec = program.recorder()
-      if rec is not None and not rec.probe:
-        # how another chunk of this structure gets ITS table (program.py);
-        # variables with the same climatology dims share one table per chunk
-        sizes = tuple(cvar.sizes[d] for d in crest)
-
-        def recompute(other, memo, climatology=climatology, cvar=cvar,
-                      geo=geo, crest=crest, sizes=sizes):
-          key = (id(climatology), crest, sizes, geo.out_dims, geo.out_shape)
-          if key not in memo:
-            memo[key] = _climatology_slabs_by_content(climatology, cvar, other,
-                                                      geo, crest)
-          return memo[key]
-        rec.note_table(ctable, recompute, _climatology_gather(
-            climatology, cvar, forecast, geo, crest))
+      cdata, crest, ctable = _climatology_operand(climatology, cvar, forecast,
+                                                  geo)
     except (KeyError, ValueError):
       if not announced:
         raise
@@ -1449,8 +1576,24 @@ def _returns_like_input(fn):
 class Metric:
   """Base class for metrics (metrics.py:84-138)."""
 
+  # What a class declares about ITS OWN compute_chunk:
+  #   _fused_regions          it takes `regions=` and answers for all of them
+  #                           from one fused pass, with a leading `region` dim
+  #   _reads_slabs_in_place   it reads concatenated chunks (xarray_lite.
+  #                           SlabConcat) through address tables, without
+  #                           materialising them: evaluate_chunks may batch
+  #                           chunks for it
+  # A subclass that brings its own compute_chunk / compute without declaring
+  # them again (a user's metric, the map families) is taken to do neither.
+  _fused_regions = False
+  _reads_slabs_in_place = False
+
   def __init_subclass__(cls, **kwargs):
     super().__init_subclass__(**kwargs)
+    if 'compute_chunk' in cls.__dict__ or 'compute' in cls.__dict__:
+      for flag in ('_fused_regions', '_reads_slabs_in_place'):
+        if flag not in cls.__dict__:
+          setattr(cls, flag, False)
     for name in ('compute_chunk', 'compute', 'compute_chunk_regions',
                  'compute_regions'):
       fn = cls.__dict__.get(name)
@@ -1461,30 +1604,44 @@ class Metric:
                     skipna: bool = False) -> xl.Dataset:
     raise NotImplementedError
 
+  def _result_attrs(self, forecast: xl.Dataset) -> dict:
+    """Attributes `compute` puts on its result (`ensemble_size`)."""
+    return {}
+
+  def _time_mean(self, chunk_fn, forecast, truth, skipna):
+    """The temporal mean of `chunk_fn(forecast, truth)` (metrics.py:117-138)."""
+    forecast, truth = xl.as_dataset(forecast), xl.as_dataset(truth)
+    avg_dim = _time_average_dim(forecast)
+    result = chunk_fn(forecast, truth).mean(avg_dim, skipna=skipna)
+    attrs = self._result_attrs(forecast)
+    return result.assign_attrs(**attrs) if attrs else result
+
   def compute(self, forecast, truth, region: t.Optional[Region] = None,
               skipna: bool = False) -> xl.Dataset:
     """Evaluate this metric on datasets with full temporal coverages."""
-    forecast, truth = xl.as_dataset(forecast), xl.as_dataset(truth)
-    if 'time' in forecast.dims:
-      avg_dim = 'time'
-    elif 'init_time' in forecast.dims:
-      avg_dim = 'init_time'
-    else:
-      raise ValueError(
-          f'Forecast has neither valid_time or init_time dimension {forecast}')
-    return self.compute_chunk(forecast, truth, region=region,
-                              skipna=skipna).mean(avg_dim, skipna=skipna)
+    return self._time_mean(
+        lambda f, t_: self.compute_chunk(f, t_, region=region, skipna=skipna),
+        forecast, truth, skipna)
 
   # All regions of a loop at once, with a leading `region` dim: what
   # evaluation.py:416-430 builds with one call + expand_dims + concat per
-  # region.  The generic versions do exactly that; metrics whose fused pass
-  # already holds every region override them with a single stack.
+  # region.  That is what happens here too, unless the class declares that its
+  # fused pass already holds every region (`_fused_regions`): then it is one
+  # call of its compute_chunk with `regions=`.
   def compute_chunk_regions(self, forecast, truth, regions: dict,
                             skipna: bool = False) -> xl.Dataset:
+    if self._fused_regions:
+      # (the function itself: this entry point's own wrapper converts)
+      return type(self).compute_chunk.__wrapped__(self, forecast, truth, None,
+                                                  skipna, regions)
     return self._fan_out(self.compute_chunk, forecast, truth, regions, skipna)
 
   def compute_regions(self, forecast, truth, regions: dict,
                       skipna: bool = False) -> xl.Dataset:
+    if self._fused_regions:
+      return self._time_mean(
+          lambda f, t_: self.compute_chunk_regions(f, t_, regions, skipna),
+          forecast, truth, skipna)
     return self._fan_out(self.compute, forecast, truth, regions, skipna)
 
   def _fan_out(self, fn, forecast, truth, regions, skipna):
@@ -1495,19 +1652,6 @@ class Metric:
                for name, region in regions.items()]
     return xl.concat(parts, 'region')
 
-  def _mean_regions(self, forecast, truth, regions, skipna):
-    """Metric.compute on the stacked result (same checks, same mean)."""
-    forecast, truth = xl.as_dataset(forecast), xl.as_dataset(truth)
-    if 'time' in forecast.dims:
-      avg_dim = 'time'
-    elif 'init_time' in forecast.dims:
-      avg_dim = 'init_time'
-    else:
-      raise ValueError(
-          f'Forecast has neither valid_time or init_time dimension {forecast}')
-    return self.compute_chunk_regions(forecast, truth, regions,
-                                      skipna).mean(avg_dim, skipna=skipna)
-
 
 for _name in ('compute', 'compute_chunk_regions', 'compute_regions'):
   setattr(Metric, _name, _returns_like_input(Metric.__dict__[_name]))
@@ -1516,9 +1660,24 @@ del _name
 
 class _DetMetric(Metric):
   _index: int = -1
-  # reads concatenated chunks (xarray_lite.SlabConcat) through address tables,
-  # without materialising them: evaluate_chunks may batch chunks for it
+  _wind_vectors = ''  # name of the field with the wind-vector metrics, if any
   _reads_slabs_in_place = True
+  _fused_regions = True
+
+  def compute_chunk(self, forecast, truth, region=None, skipna=False,
+                    regions: t.Optional[dict] = None):
+    # converted once, here: the wind-vector metrics below are then called with
+    # lite Datasets and answer with lite Datasets (xarray callers get their
+    # xarray result from the wrapper around THIS method)
+    forecast, truth = xl.as_dataset(forecast), xl.as_dataset(truth)
+    results = self._scalar(forecast, truth, region, skipna, regions)
+    for wv in getattr(self, self._wind_vectors, None) or ():
+      if regions is None:
+        part = wv.compute_chunk(forecast, truth, region=region, skipna=skipna)
+      else:
+        part = wv.compute_chunk_regions(forecast, truth, regions, skipna)
+      results[wv.vector_name] = part[wv.vector_name]
+    return results
 
   def _scalar(self, forecast, truth, region, skipna,
               regions: t.Optional[dict] = None) -> xl.Dataset:
@@ -1536,21 +1695,13 @@ class _DetMetric(Metric):
         per_var[name] = (lead + geo.out_dims, values, dtype)
     return _assemble(forecast, per_var, regions)
 
-  def compute_chunk_regions(self, forecast, truth, regions, skipna=False):
-    return self._scalar(forecast, truth, None, skipna, regions)
-
-  def compute_regions(self, forecast, truth, regions, skipna=False):
-    return self._mean_regions(forecast, truth, regions, skipna)
-
 
 def _wind_plan(forecast, truth, u_name, v_name):
   fu, fv, tu, tv = (forecast[u_name], forecast[v_name], truth[u_name],
                     truth[v_name])
   pins = (fu.data, tu.data, fv.data, tv.data)
   geo, prepared = _geometry(forecast, fu, [tu, fv, tv])
-  tables = [_slab_table(geo.out_dims, geo.out_shape, p[1], p[0].shape[:-2])
-            for p in prepared]
-  return geo, [p[0] for p in prepared], tables, pins
+  return (geo, [p[0] for p in prepared], _operand_tables(geo, prepared), pins)
 
 
 def _wind_key(forecast, truth, u_name, v_name, region, skipna):
@@ -1607,6 +1758,7 @@ class WindVectorMSE(Metric):
   vector_name: str
   _index = _lib.METRIC_INDEX['mse']
   _reads_slabs_in_place = True
+  _fused_regions = True
 
   def compute_chunk(self, forecast, truth, region=None, skipna=False,
                     regions: t.Optional[dict] = None):
@@ -1622,12 +1774,6 @@ class WindVectorMSE(Metric):
     return _assemble(forecast, {self.vector_name: (lead + geo.out_dims,
                                                    values, dtype)}, regions)
 
-  def compute_chunk_regions(self, forecast, truth, regions, skipna=False):
-    return self.compute_chunk(forecast, truth, None, skipna, regions)
-
-  def compute_regions(self, forecast, truth, regions, skipna=False):
-    return self._mean_regions(forecast, truth, regions, skipna)
-
 
 @dataclasses.dataclass
 class WindVectorRMSESqrtBeforeTimeAvg(WindVectorMSE):
@@ -1642,27 +1788,7 @@ class RMSESqrtBeforeTimeAvg(_DetMetric):
 
   wind_vector_rmse: t.Optional[list] = None
   _index = _lib.METRIC_INDEX['rmse']
-
-  def compute_chunk(self, forecast, truth, region=None, skipna=False):
-    # converted once, here: the wind-vector metrics below are then called with
-    # lite Datasets and answer with lite Datasets (xarray callers get their
-    # xarray result from the wrapper around THIS method)
-    forecast, truth = xl.as_dataset(forecast), xl.as_dataset(truth)
-    results = self._scalar(forecast, truth, region, skipna)
-    if self.wind_vector_rmse is not None:
-      for wv in self.wind_vector_rmse:
-        results[wv.vector_name] = wv.compute_chunk(
-            forecast, truth, region=region, skipna=skipna)[wv.vector_name]
-    return results
-
-  def compute_chunk_regions(self, forecast, truth, regions, skipna=False):
-    forecast, truth = xl.as_dataset(forecast), xl.as_dataset(truth)
-    results = self._scalar(forecast, truth, None, skipna, regions)
-    if self.wind_vector_rmse is not None:
-      for wv in self.wind_vector_rmse:
-        results[wv.vector_name] = wv.compute_chunk_regions(
-            forecast, truth, regions, skipna)[wv.vector_name]
-    return results
+  _wind_vectors = 'wind_vector_rmse'
 
 
 @dataclasses.dataclass
@@ -1671,27 +1797,7 @@ class MSE(_DetMetric):
 
   wind_vector_mse: t.Optional[list] = None
   _index = _lib.METRIC_INDEX['mse']
-
-  def compute_chunk(self, forecast, truth, region=None, skipna=False):
-    # converted once, here: the wind-vector metrics below are then called with
-    # lite Datasets and answer with lite Datasets (xarray callers get their
-    # xarray result from the wrapper around THIS method)
-    forecast, truth = xl.as_dataset(forecast), xl.as_dataset(truth)
-    results = self._scalar(forecast, truth, region, skipna)
-    if self.wind_vector_mse is not None:
-      for wv in self.wind_vector_mse:
-        results[wv.vector_name] = wv.compute_chunk(
-            forecast, truth, region=region, skipna=skipna)[wv.vector_name]
-    return results
-
-  def compute_chunk_regions(self, forecast, truth, regions, skipna=False):
-    forecast, truth = xl.as_dataset(forecast), xl.as_dataset(truth)
-    results = self._scalar(forecast, truth, None, skipna, regions)
-    if self.wind_vector_mse is not None:
-      for wv in self.wind_vector_mse:
-        results[wv.vector_name] = wv.compute_chunk_regions(
-            forecast, truth, regions, skipna)[wv.vector_name]
-    return results
+  _wind_vectors = 'wind_vector_mse'
 
 
 @dataclasses.dataclass
@@ -1700,18 +1806,12 @@ class MAE(_DetMetric):
 
   _index = _lib.METRIC_INDEX['mae']
 
-  def compute_chunk(self, forecast, truth, region=None, skipna=False):
-    return self._scalar(forecast, truth, region, skipna)
-
 
 @dataclasses.dataclass
 class Bias(_DetMetric):
   """Bias (metrics.py:348-359)."""
 
   _index = _lib.METRIC_INDEX['bias']
-
-  def compute_chunk(self, forecast, truth, region=None, skipna=False):
-    return self._scalar(forecast, truth, region, skipna)
 
 
 @dataclasses.dataclass
@@ -1725,6 +1825,7 @@ class ACC(Metric):
 
   climatology: t.Any = None
   _reads_slabs_in_place = True
+  _fused_regions = True
 
   def compute_chunk(self, forecast, truth, region=None, skipna=False,
                     regions: t.Optional[dict] = None):
@@ -1746,12 +1847,6 @@ class ACC(Metric):
                              regions, dtype)
         per_var[name] = (lead + geo.out_dims, values, dtype)
     return _assemble(forecast, per_var, regions)
-
-  def compute_chunk_regions(self, forecast, truth, regions, skipna=False):
-    return self.compute_chunk(forecast, truth, None, skipna, regions)
-
-  def compute_regions(self, forecast, truth, regions, skipna=False):
-    return self._mean_regions(forecast, truth, regions, skipna)
 
 
 # ---------------------------------------------------------------------------
@@ -1786,30 +1881,10 @@ def _ens_layout(forecast, fvar, tvar, ensemble_dim, allow_gather=False):
   index o is slab  m * stride_member + ens_table[o]  of the forecast array --
   or, for a gathered forecast when the caller can take it (`allow_gather`: K3),
   the slab at address member_ptrs[o, m] (last entry of the result, else None)."""
-  if ensemble_dim not in fvar.dims:
-    raise ValueError(f'{ensemble_dim=} not found in {fvar.dims=}')
-  fdata, frest, layout = _spatial_last(fvar, None)
-  tdata, trest, _ = _spatial_last(tvar, layout)
-  if ensemble_dim in trest:
-    raise ValueError(f'truth must not have the ensemble dim {ensemble_dim!r}')
-  fsizes = dict(zip(frest, fdata.shape[:-2]))
-  n_member = fsizes[ensemble_dim]
-  out_dims = [d for d in frest if d != ensemble_dim]
-  sizes = {d: fsizes[d] for d in out_dims}
-  for d, n in zip(trest, tdata.shape[:-2]):
-    if d not in out_dims:
-      out_dims.append(d)
-      sizes[d] = n
-  out_dims = tuple(out_dims)
-  out_shape = tuple(sizes[d] for d in out_dims)
-  geo = _Geometry(layout, out_dims, out_shape,
-                  _coord_values(forecast, 'latitude'),
-                  _coord_values(forecast, 'longitude'))
-  # member m, outer index o  ->  slab  m * stride_member + ens_table[o]
-  stride, strides = 1, {}
-  for d in reversed(frest):
-    strides[d] = stride
-    stride *= fsizes[d]
+  outer = _ens_outer_layout(forecast, fvar, [tvar], ensemble_dim)
+  geo, n_member, strides = outer.geo, outer.n_member, outer.strides
+  (fdata, frest), (tdata, _) = outer.prepared
+  out_dims, out_shape = geo.out_dims, geo.out_shape
   strided = False
   if isinstance(fdata, torch.Tensor) and not fdata.is_contiguous():
     # a VIEW with intact 2-D slabs (an (init_time=1, lead_time=1) chunk sliced
@@ -1831,18 +1906,10 @@ def _ens_layout(forecast, fvar, tvar, ensemble_dim, allow_gather=False):
       strided = True
     else:
       fdata = fdata.contiguous()
-  ens_table = np.zeros(out_shape, dtype=np.int64)
-  for d in frest:
-    if d == ensemble_dim:
-      continue
-    shape = [1] * len(out_shape)
-    shape[out_dims.index(d)] = fsizes[d]
-    ens_table = ens_table + (np.arange(fsizes[d], dtype=np.int64)
-                             * strides[d]).reshape(shape)
-  ens_table = np.ascontiguousarray(ens_table).ravel()
+  ens_table = outer.ens_table(strides)
   identity = (not strided) and np.array_equal(ens_table,
                                               np.arange(ens_table.size))
-  truth_table = _slab_table(out_dims, out_shape, trest, tdata.shape[:-2])
+  truth_table, = _operand_tables(geo, outer.prepared[1:])
 
   device = engine.require_gpu()
   tten = _to_device(tdata, device)
@@ -1878,13 +1945,7 @@ def _ens_layout(forecast, fvar, tvar, ensemble_dim, allow_gather=False):
     ften = xl.SlabGather(dev_base, index).materialize()
   else:
     ften = _to_device(fdata, device)
-  dtype = torch.promote_types(ften.dtype, tten.dtype)
-  if dtype not in (torch.float32, torch.float64):
-    dtype = torch.float64
-  ften = ften if ften.dtype == dtype else ften.to(dtype)
-  tten = tten if tten.dtype == dtype else tten.to(dtype)
-  _check_grid(geo, ften)
-  _check_grid(geo, tten)
+  (ften, tten), _ = _common_float(geo, [ften, tten])
   return (geo, ften, tten, None if identity else to_dev(ens_table),
           to_dev(truth_table), strides[ensemble_dim], n_member, device, None)
 
@@ -1896,35 +1957,20 @@ def _ens_concat_layout(forecast, fvar, tvar, ensemble_dim):
   every outer index, one member stride for all of them.  None where the window
   cannot be read where it lies (a cast, host data, members that do not follow
   each other at one stride): the caller materialises it as before."""
-  if ensemble_dim not in fvar.dims:
-    raise ValueError(f'{ensemble_dim=} not found in {fvar.dims=}')
-  fdata, frest, layout = _spatial_last(fvar, None)
+  outer = _ens_outer_layout(forecast, fvar, [tvar], ensemble_dim)
+  geo, n_member = outer.geo, outer.n_member
+  (fdata, frest), (tdata, _) = outer.prepared
   in_hbm = lambda x: isinstance(x, torch.Tensor) and x.device.type == 'cuda'
   if not isinstance(fdata, xl.SlabConcat) or not in_hbm(fdata.bases[0]):
     return None
-  tdata, trest, _ = _spatial_last(tvar, layout)
-  if ensemble_dim in trest:
-    raise ValueError(f'truth must not have the ensemble dim {ensemble_dim!r}')
   dtype = fdata.dtype
   on_device = in_hbm(tdata.bases[0] if isinstance(tdata, xl.SlabConcat)
                      else tdata)
   if dtype not in (torch.float32, torch.float64) or not on_device or (
       _torch_dtype_of(tdata) != dtype):
     return None
-  fsizes = dict(zip(frest, fdata.shape[:-2]))
-  n_member = fsizes[ensemble_dim]
-  out_dims = [d for d in frest if d != ensemble_dim]
-  sizes = {d: fsizes[d] for d in out_dims}
-  n_own = len(out_dims)
-  for d, n in zip(trest, tdata.shape[:-2]):
-    if d not in out_dims:
-      out_dims.append(d)
-      sizes[d] = n
-  out_dims = tuple(out_dims)
-  out_shape = tuple(sizes[d] for d in out_dims)
-  geo = _Geometry(layout, out_dims, out_shape,
-                  _coord_values(forecast, 'latitude'),
-                  _coord_values(forecast, 'longitude'))
+  out_dims, out_shape = geo.out_dims, geo.out_shape
+  n_own = len(frest) - 1
   _check_grid(geo, fdata)
   _check_grid(geo, tdata)
   # slab numbers (in the virtual concatenation of the chunks) [outer..., member]
@@ -1947,7 +1993,7 @@ def _ens_concat_layout(forecast, fvar, tvar, ensemble_dim):
   base_of = np.searchsorted(fdata.offsets, first, side='right') - 1
   starts = np.array([b.data_ptr() for b in fdata.bases], dtype=np.int64)
   ens_addr = starts[base_of] + (first - fdata.offsets[base_of]) * step
-  truth_table = _slab_table(out_dims, out_shape, trest, tdata.shape[:-2])
+  truth_table, = _operand_tables(geo, outer.prepared[1:])
   truth_addr, keep = _slab_addresses(tdata, truth_table, fdata.slab_shape[0],
                                      fdata.slab_shape[1], n_outer)
   return dict(geo=geo, dtype=dtype, n_member=n_member,
@@ -1958,76 +2004,55 @@ def _ens_concat_layout(forecast, fvar, tvar, ensemble_dim):
 
 
 def _ens_pass_concat(fvar, tvar, lay, region, skipna):
-  """_ens_pass over a window read in place: (geo, device, plan, metrics)."""
+  """_ens_pass over a window read in place: (geo, by_region, n_member)."""
   geo = lay['geo']
   device = engine.require_gpu()
-  regions, _ = _region_set_for(region)
-  pl = plan_lib.cached_plan(
-      geo.latitude, geo.longitude, geo.layout, regions, device,
-      plan_lib.ENSEMBLE_ROWS_PER_CHUNK)
-  rec = program.recorder()
-  if rec is not None and rec.probe:
-    return geo, pl, rec.fake_metrics(_lib.NMETRIC_ENS, pl.n_region, geo.n_outer,
-                                     device)
-  table = engine.upload_table(
-      np.concatenate([lay['ens_addr'], lay['truth_addr']]), device)
-  like = lay['keep'][0][0]     # (a tensor of the dtype: the kernel is told
-  metrics, _ = engine.ensemble_reduce(   # addresses, not tensors)
-      pl, like, lay['member_stride'], lay['n_member'], None, like, None,
-      geo.n_outer, skipna, addresses=table)
-  if rec is not None:
-    rec.record(kind='ens', plan=pl, ens=None, ens_raw=fvar.data,
-               truth=None, truth_raw=tvar.data, concat=lay,
-               member_stride=lay['member_stride'], n_member=lay['n_member'],
-               ens_table=None, truth_table=lay['truth_table'],
-               n_outer=geo.n_outer, skipna=bool(skipna), metrics=metrics,
-               dtype=lay['dtype'])
-  return geo, pl, metrics
+
+  def launch(pl):
+    rec = program.recorder()
+    if rec is not None and rec.probe:
+      return rec.fake_metrics(_lib.NMETRIC_ENS, pl.n_region, geo.n_outer,
+                              device)
+    table = engine.upload_table(
+        np.concatenate([lay['ens_addr'], lay['truth_addr']]), device)
+    like = lay['keep'][0][0]     # (a tensor of the dtype: the kernel is told
+    metrics, _ = engine.ensemble_reduce(   # addresses, not tensors)
+        pl, like, lay['member_stride'], lay['n_member'], None, like, None,
+        geo.n_outer, skipna, addresses=table)
+    if rec is not None:
+      rec.record(kind='ens', plan=pl, ens=None, ens_raw=fvar.data,
+                 truth=None, truth_raw=tvar.data, concat=lay,
+                 member_stride=lay['member_stride'], n_member=lay['n_member'],
+                 ens_table=None, truth_table=lay['truth_table'],
+                 n_outer=geo.n_outer, skipna=bool(skipna), metrics=metrics,
+                 dtype=lay['dtype'])
+    return metrics
+  by_region = _regional_pass(
+      geo, region, device, plan_lib.ENSEMBLE_ROWS_PER_CHUNK, _lib.NMETRIC_ENS,
+      launch)
+  return geo, by_region, lay['n_member']
 
 
-def _ens_pass(forecast, truth, name, ensemble_dim, region, skipna,
-              want_maps: bool = False):
-  """All ensemble metrics of one variable for the active regions (and, with
-  `want_maps`, the six pointwise maps as a device tensor)."""
-  fvar, tvar = forecast[name], truth[name]
-  pins = [fvar.data, tvar.data]
-  key = _result_key(('ens', ensemble_dim, want_maps), pins, region, skipna,
-                    (forecast, truth))
-  hit = _RESULTS.get(key)
-  if hit is not None:
-    return hit
-  lay = None
-  if isinstance(fvar.data, xl.SlabConcat) and not want_maps:
-    # a window of chunks (evaluate_chunks): read where the chunks lie
-    lay = _ens_concat_layout(forecast, fvar, tvar, ensemble_dim)
-  if lay is not None:
-    geo, pl, metrics = _ens_pass_concat(fvar, tvar, lay, region, skipna)
-    dev = metrics.reshape((_lib.NMETRIC_ENS, pl.n_region) + geo.out_shape)
-    geo.region_wsum = dict(zip(pl.region_names,
-                               (float(w) for w in pl.region_wsum_host)))
-    value = (geo, {nm: dev[:, i] for i, nm in enumerate(pl.region_names)},
-             lay['n_member'])
-    _RESULTS.put(key, tuple(pins), value)
-    return value
+def _ens_pass_layout(forecast, fvar, tvar, ensemble_dim, region, skipna,
+                     want_maps):
+  """_ens_pass over one array: (geo, by_region, n_member) and, with
+  `want_maps`, the maps and their dtype."""
   (geo, ften, tten, ens_table, truth_table, member_slabs, n_member, device,
    member_ptrs) = _ens_layout(forecast, fvar, tvar, ensemble_dim,
                               allow_gather=True)
-  out_shape = geo.out_shape
-  regions, _ = _region_set_for(region)
-  pl = plan_lib.cached_plan(
-      geo.latitude, geo.longitude, geo.layout, regions, device,
-      plan_lib.ENSEMBLE_ROWS_PER_CHUNK)
-  slab_elems = pl.n_row * pl.n_col
+  n_row, n_col = ften.shape[-2:]  # (the plan's: _check_grid)
+  slab_elems = n_row * n_col
   maps = (torch.empty((6, geo.n_outer, slab_elems), dtype=torch.float64,
                       device=device) if want_maps else None)
-  rec = program.recorder()
-  plain = maps is None and member_ptrs is None
-  if rec is not None and rec.probe and plain:
-    # program.py's probe pass: no launch, index-valued results
-    metrics = rec.fake_metrics(_lib.NMETRIC_ENS, pl.n_region, geo.n_outer,
-                               device)
-  else:
-    truth3 = tten.reshape(-1, pl.n_row, pl.n_col)
+
+  def launch(pl):
+    rec = program.recorder()
+    plain = maps is None and member_ptrs is None
+    if rec is not None and rec.probe and plain:
+      # program.py's probe pass: no launch, index-valued results
+      return rec.fake_metrics(_lib.NMETRIC_ENS, pl.n_region, geo.n_outer,
+                              device)
+    truth3 = tten.reshape(-1, n_row, n_col)
     metrics, _ = engine.ensemble_reduce(
         pl, ften, member_slabs * slab_elems, n_member, ens_table, truth3,
         truth_table, geo.n_outer, skipna, maps=maps,
@@ -2042,18 +2067,34 @@ def _ens_pass(forecast, truth, name, ensemble_dim, region, skipna,
                    n_outer=geo.n_outer, skipna=bool(skipna), metrics=metrics)
       else:
         rec.record(kind='unsupported')
-  dev = metrics.reshape((_lib.NMETRIC_ENS, pl.n_region) + geo.out_shape)
-  # total weight of each region: a spatial average of zeros is 0/0 = NaN over
-  # an empty region (CRPSSpread with one member, metrics.py:689-693, 783-784)
-  geo.region_wsum = dict(zip(pl.region_names,
-                             (float(w) for w in pl.region_wsum_host)))
-  value = (geo, {nm: dev[:, i] for i, nm in enumerate(pl.region_names)},
-           n_member)
-  if want_maps:
-    value = value + (maps.reshape((6,) + out_shape + (pl.n_row, pl.n_col)),
-                     ften.dtype)
-  _RESULTS.put(key, tuple(pins), value)
-  return value
+    return metrics
+  by_region = _regional_pass(
+      geo, region, device, plan_lib.ENSEMBLE_ROWS_PER_CHUNK, _lib.NMETRIC_ENS,
+      launch)
+  if not want_maps:
+    return geo, by_region, n_member
+  return (geo, by_region, n_member,
+          maps.reshape((6,) + geo.out_shape + (n_row, n_col)), ften.dtype)
+
+
+def _ens_pass(forecast, truth, name, ensemble_dim, region, skipna,
+              want_maps: bool = False):
+  """All ensemble metrics of one variable for the active regions (and, with
+  `want_maps`, the six pointwise maps as a device tensor)."""
+  fvar, tvar = forecast[name], truth[name]
+  pins = (fvar.data, tvar.data)
+
+  def compute():
+    if isinstance(fvar.data, xl.SlabConcat) and not want_maps:
+      # a window of chunks (evaluate_chunks): read where the chunks lie
+      lay = _ens_concat_layout(forecast, fvar, tvar, ensemble_dim)
+      if lay is not None:
+        return _ens_pass_concat(fvar, tvar, lay, region, skipna)
+    return _ens_pass_layout(forecast, fvar, tvar, ensemble_dim, region, skipna,
+                            want_maps)
+  return _cached_pass(
+      _result_key(('ens', ensemble_dim, want_maps), pins, region, skipna,
+                  (forecast, truth)), pins, compute)
 
 
 @dataclasses.dataclass
@@ -2070,6 +2111,13 @@ class EnsembleMetric(Metric):
   # `truth - forecast...` (skill, CRPS, mean MSE/RMSE, debiased) come out in
   # truth-first order, the ones built from the forecast alone in forecast order.
   _truth_first = True
+  # K3 reads a window of chunks through slab addresses (_ens_pass), and its
+  # pass answers for every region
+  _reads_slabs_in_place = True
+  _fused_regions = True
+
+  def _result_attrs(self, forecast):
+    return {'ensemble_size': forecast.sizes[self.ensemble_dim]}
 
   def compute_chunk(self, forecast, truth, region=None, skipna=False,
                     regions: t.Optional[dict] = None):
@@ -2104,43 +2152,9 @@ class EnsembleMetric(Metric):
                 values[...] = float('nan')
         dims = lead + geo.out_dims
         if self._truth_first:
-          tdims = [d for d in truth[name].dims if d in dims]
-          order = lead + tuple(
-              tdims + [d for d in dims if d not in tdims and d not in lead])
-          values = _transpose(values, [dims.index(d) for d in order])
-          dims = order
+          dims, values = _order_by(dims, values, (lead, truth[name].dims))
         per_var[name] = (dims, values)
     return _assemble(forecast, per_var, regions)
-
-  def compute(self, forecast, truth, region=None, skipna=False):
-    """Evaluate this metric on datasets with full temporal coverages."""
-    forecast, truth = xl.as_dataset(forecast), xl.as_dataset(truth)
-    result = super().compute(forecast, truth, region=region, skipna=skipna)
-    return result.assign_attrs(ensemble_size=forecast.sizes[self.ensemble_dim])
-
-  def _uses_fused_scalars(self) -> bool:
-    """Subclasses with their own compute_chunk / compute (energy scores, maps,
-    rank histograms) keep the generic per-region fan-out."""
-    return (type(self).compute_chunk is EnsembleMetric.compute_chunk
-            and type(self).compute is EnsembleMetric.compute)
-
-  @property
-  def _reads_slabs_in_place(self) -> bool:
-    """K3 reads a window of chunks through slab addresses (_ens_pass):
-    evaluate_chunks may batch chunks for the scalar ensemble metrics."""
-    return self._uses_fused_scalars()
-
-  def compute_chunk_regions(self, forecast, truth, regions, skipna=False):
-    if not self._uses_fused_scalars():
-      return super().compute_chunk_regions(forecast, truth, regions, skipna)
-    return self.compute_chunk(forecast, truth, None, skipna, regions)
-
-  def compute_regions(self, forecast, truth, regions, skipna=False):
-    if not self._uses_fused_scalars():
-      return super().compute_regions(forecast, truth, regions, skipna)
-    forecast = xl.as_dataset(forecast)
-    return self._mean_regions(forecast, truth, regions, skipna).assign_attrs(
-        ensemble_size=forecast.sizes[self.ensemble_dim])
 
 
 @dataclasses.dataclass
@@ -2212,22 +2226,15 @@ def _spatial_inputs(forecast, truth, name, time_first: t.Optional[str] = None):
     order = (time_first,) + tuple(d for d in out_dims if d != time_first)
     out_shape = tuple(out_shape[out_dims.index(d)] for d in order)
     out_dims = order
-  tables = [_slab_table(out_dims, out_shape, p[1], p[0].shape[:-2])
-            for p in prepared]
+  tables = _operand_tables(geo, prepared, out_dims, out_shape)
   device = engine.require_gpu()
-  tensors = [_to_device(p[0], device) for p in prepared]
-  dtype = torch.promote_types(tensors[0].dtype, tensors[1].dtype)
-  if dtype not in (torch.float32, torch.float64):
-    dtype = torch.float64
-  tensors = [x if x.dtype == dtype else x.to(dtype) for x in tensors]
-  for x in tensors:
-    _check_grid(geo, x)
+  tensors, _ = _common_float(geo, [_to_device(p[0], device) for p in prepared])
   slabs = [None if tb is None else engine.upload_table(tb, device)
            for tb in tables]
-  spatial = _SPATIAL if geo.layout == plan_lib.LATLON else _SPATIAL[::-1]
   n_point = len(geo.latitude) * len(geo.longitude)
   spatial_shape = tuple(tensors[0].shape[-2:])
-  return tensors, slabs, out_dims, out_shape, spatial, spatial_shape, n_point
+  return (tensors, slabs, out_dims, out_shape, geo.spatial_dims, spatial_shape,
+          n_point)
 
 
 def _spatial_coords(forecast, dims):
@@ -2244,72 +2251,60 @@ class _SpatialMetric(Metric):
 
   _map = ''
 
-  def compute_chunk(self, forecast, truth, region=None, skipna=False):
-    del skipna  # Ignored
-    forecast, truth = _inputs(forecast, truth)
+  def _dataset(self, forecast, truth, kind, key_tail, compute):
+    """This metric's map of every variable out of `compute(name)` -> (dims,
+    {map name: tensor}), one cached pass per variable for all three maps."""
     out = xl.Dataset()
     for name in _common_vars(forecast, truth):
       pins = (forecast[name].data, truth[name].data)
-      key = ('spatial', _stamp(pins[0]), _stamp(pins[1]),
-             _coord_sig(forecast, truth))
-      hit = _RESULTS.get(key)
-      if hit is None:
-        (tensors, slabs, out_dims, out_shape, spatial, spatial_shape,
-         n_point) = _spatial_inputs(forecast, truth, name)
-        n_outer = int(np.prod(out_shape, dtype=np.int64))
-        maps = engine.spatial_maps(
-            tensors[0].reshape(-1, n_point), slabs[0],
-            tensors[1].reshape(-1, n_point), slabs[1], n_outer, n_point)
-        dims = tuple(out_dims) + tuple(spatial)
-        hit = (dims, {k: v.reshape(out_shape + spatial_shape)
-                      for k, v in maps.items()})
-        _RESULTS.put(key, pins, hit)
-      dims, maps = hit
+      key = (kind, _stamp(pins[0]), _stamp(pins[1]),
+             _coord_sig(forecast, truth)) + key_tail
+      dims, maps = _cached_pass(key, pins, functools.partial(compute, name))
       out.coords.update(_spatial_coords(forecast, dims))
       out.data_vars[name] = xl.DataArray(maps[self._map], dims, out.coords,
                                          name)
     return out
 
+  def compute_chunk(self, forecast, truth, region=None, skipna=False):
+    del skipna  # Ignored
+    forecast, truth = _inputs(forecast, truth)
+
+    def maps_of(name):
+      (tensors, slabs, out_dims, out_shape, spatial, spatial_shape,
+       n_point) = _spatial_inputs(forecast, truth, name)
+      n_outer = int(np.prod(out_shape, dtype=np.int64))
+      maps = engine.spatial_maps(
+          tensors[0].reshape(-1, n_point), slabs[0],
+          tensors[1].reshape(-1, n_point), slabs[1], n_outer, n_point)
+      return (tuple(out_dims) + tuple(spatial),
+              {k: v.reshape(out_shape + spatial_shape)
+               for k, v in maps.items()})
+    return self._dataset(forecast, truth, 'spatial', (), maps_of)
+
   def compute(self, forecast, truth, region=None, skipna=False):
     """Temporal mean of the map, fused: no per-time map is materialised."""
     forecast, truth = _inputs(forecast, truth)
-    if 'time' in forecast.dims:
-      avg_dim = 'time'
-    elif 'init_time' in forecast.dims:
-      avg_dim = 'init_time'
-    else:
-      raise ValueError(
-          f'Forecast has neither valid_time or init_time dimension {forecast}')
-    out = xl.Dataset()
-    for name in _common_vars(forecast, truth):
-      pins = (forecast[name].data, truth[name].data)
-      key = ('spatial_mean', _stamp(pins[0]), _stamp(pins[1]),
-             _coord_sig(forecast, truth), bool(skipna))
-      hit = _RESULTS.get(key)
-      if hit is None:
-        (tensors, slabs, out_dims, out_shape, spatial, spatial_shape,
-         n_point) = _spatial_inputs(forecast, truth, name, time_first=avg_dim)
-        n_time = out_shape[0]
-        n_rest = int(np.prod(out_shape[1:], dtype=np.int64))
-        dev = tensors[0].device
-        total = torch.zeros((3, n_rest, n_point), dtype=torch.float64,
-                            device=dev)
-        count = torch.zeros_like(total) if skipna else None
-        engine.spatial_accumulate(
-            tensors[0].reshape(-1, n_point), slabs[0],
-            tensors[1].reshape(-1, n_point), slabs[1], n_time, n_rest,
-            n_point, skipna, total, count)
-        mean = total / (count if skipna else float(n_time))
-        mean = mean.to(tensors[0].dtype).reshape(
-            (3,) + tuple(out_shape[1:]) + spatial_shape)
-        dims = tuple(out_dims[1:]) + tuple(spatial)
-        hit = (dims, {'bias': mean[0], 'mse': mean[1], 'mae': mean[2]})
-        _RESULTS.put(key, pins, hit)
-      dims, maps = hit
-      out.coords.update(_spatial_coords(forecast, dims))
-      out.data_vars[name] = xl.DataArray(maps[self._map], dims, out.coords,
-                                         name)
-    return out
+    avg_dim = _time_average_dim(forecast)
+
+    def means_of(name):
+      (tensors, slabs, out_dims, out_shape, spatial, spatial_shape,
+       n_point) = _spatial_inputs(forecast, truth, name, time_first=avg_dim)
+      n_time = out_shape[0]
+      n_rest = int(np.prod(out_shape[1:], dtype=np.int64))
+      total = torch.zeros((3, n_rest, n_point), dtype=torch.float64,
+                          device=tensors[0].device)
+      count = torch.zeros_like(total) if skipna else None
+      engine.spatial_accumulate(
+          tensors[0].reshape(-1, n_point), slabs[0],
+          tensors[1].reshape(-1, n_point), slabs[1], n_time, n_rest,
+          n_point, skipna, total, count)
+      mean = total / (count if skipna else float(n_time))
+      mean = mean.to(tensors[0].dtype).reshape(
+          (3,) + tuple(out_shape[1:]) + spatial_shape)
+      return (tuple(out_dims[1:]) + tuple(spatial),
+              {'bias': mean[0], 'mse': mean[1], 'mae': mean[2]})
+    return self._dataset(forecast, truth, 'spatial_mean', (bool(skipna),),
+                         means_of)
 
 
 @dataclasses.dataclass
@@ -2379,19 +2374,16 @@ def compute_spread_skill_ratio(results):
 # ---------------------------------------------------------------------------
 def _gauss_pass(forecast, truth, name, region, skipna):
   mvar, svar, tvar = forecast[name], forecast[f'{name}_std'], truth[name]
-  pins = [mvar.data, svar.data, tvar.data]
-  key = _result_key('gauss', pins, region, skipna, (forecast, truth))
-  hit = _RESULTS.get(key)
-  if hit is not None:
-    return hit
-  geo, prepared = _geometry(forecast, mvar, [svar, tvar])
-  tables = [_slab_table(geo.out_dims, geo.out_shape, p[1], p[0].shape[:-2])
-            for p in prepared]
-  by_region, _ = _run_pass(_lib.MODE_GAUSS, geo, [p[0] for p in prepared],
-                           tables, region, skipna)
-  value = (geo, by_region)
-  _RESULTS.put(key, tuple(pins), value)
-  return value
+  pins = (mvar.data, svar.data, tvar.data)
+
+  def compute():
+    geo, prepared = _geometry(forecast, mvar, [svar, tvar])
+    by_region, _ = _run_pass(_lib.MODE_GAUSS, geo, [p[0] for p in prepared],
+                             _operand_tables(geo, prepared), region, skipna)
+    return geo, by_region
+  return _cached_pass(
+      _result_key('gauss', pins, region, skipna, (forecast, truth)), pins,
+      compute)
 
 
 class _GaussianMetric(Metric):
@@ -2427,27 +2419,21 @@ def _energy_pass(forecast, truth, name, ensemble_dim, region, skipna):
   read of the ensemble (wb2_energy_score: the 2 M - 1 per-member sums of
   metrics.py:1468-1517 accumulated by blocks of members)."""
   fvar, tvar = forecast[name], truth[name]
-  pins = [fvar.data, tvar.data]
-  key = _result_key(('energy', ensemble_dim), pins, region, skipna,
-                    (forecast, truth))
-  hit = _RESULTS.get(key)
-  if hit is not None:
-    return hit
-  (geo, ften, tten, ens_table, truth_table, member_slabs, n_member, device,
-   _) = _ens_layout(forecast, fvar, tvar, ensemble_dim)
-  regions, _ = _region_set_for(region)
-  pl = plan_lib.cached_plan(
-      geo.latitude, geo.longitude, geo.layout, regions, device,
-      plan_lib.ENERGY_ROWS_PER_CHUNK)
-  slab_elems = pl.n_row * pl.n_col
-  out = engine.energy_score(
-      pl, ften, member_slabs * slab_elems, n_member, ens_table,
-      tten.reshape(-1, pl.n_row, pl.n_col), truth_table, geo.n_outer, skipna)
-  dev = out.reshape((3, pl.n_region) + geo.out_shape)
-  value = (geo, {nm: dev[:, i] for i, nm in enumerate(pl.region_names)},
-           n_member)
-  _RESULTS.put(key, tuple(pins), value)
-  return value
+  pins = (fvar.data, tvar.data)
+
+  def compute():
+    (geo, ften, tten, ens_table, truth_table, member_slabs, n_member, device,
+     _) = _ens_layout(forecast, fvar, tvar, ensemble_dim)
+    by_region = _regional_pass(
+        geo, region, device, plan_lib.ENERGY_ROWS_PER_CHUNK, 3,
+        lambda pl: engine.energy_score(
+            pl, ften, member_slabs * pl.n_row * pl.n_col, n_member, ens_table,
+            tten.reshape(-1, pl.n_row, pl.n_col), truth_table, geo.n_outer,
+            skipna))
+    return geo, by_region, n_member
+  return _cached_pass(
+      _result_key(('energy', ensemble_dim), pins, region, skipna,
+                  (forecast, truth)), pins, compute)
 
 
 @dataclasses.dataclass
@@ -2455,6 +2441,7 @@ class _EnergyMetric(EnsembleMetric):
   """Shared body of the three energy-score metrics: rows of the fused pass."""
   _row = 0
   _truth_first = False  # `forecast - truth` / the forecast alone come first
+  _fused_regions = True  # (but the energy kernel reads whole arrays)
 
   def compute_chunk(self, forecast, truth, region=None, skipna=False,
                     regions: t.Optional[dict] = None):
@@ -2473,14 +2460,6 @@ class _EnergyMetric(EnsembleMetric):
         lead, values = _pick(by_region, region, self._row, regions)
         per_var[name] = (lead + geo.out_dims, values, dtype)
     return _assemble(forecast, per_var, regions)
-
-  def compute_chunk_regions(self, forecast, truth, regions, skipna=False):
-    return self.compute_chunk(forecast, truth, None, skipna, regions)
-
-  def compute_regions(self, forecast, truth, regions, skipna=False):
-    forecast = xl.as_dataset(forecast)
-    return self._mean_regions(forecast, truth, regions, skipna).assign_attrs(
-        ensemble_size=forecast.sizes[self.ensemble_dim])
 
 
 @dataclasses.dataclass
@@ -2506,13 +2485,18 @@ class EnergyScore(_EnergyMetric):
 # ---------------------------------------------------------------------------
 # Tier 2: threshold metrics (metrics.py:940-1158 Gaussian, 1524-1891 ensemble)
 # ---------------------------------------------------------------------------
-def _stack_quantiles(forecast, per_threshold: list, quantiles, method: str,
-                     sum_over_quantile: bool) -> xl.Dataset:
-  """metrics.py:966-972: concat over a new leading `quantile` dim (+ attrs)."""
+def _stack_quantiles(forecast, per_threshold: list, thresholds,
+                     sum_over_quantile: bool,
+                     coords_of=_result_coords) -> xl.Dataset:
+  """metrics.py:966-972: the per-threshold {name: (dims, values)} concatenated
+  over a new leading `quantile` dim (+ attrs); maps bring their spatial
+  coordinates along (`coords_of=_spatial_coords`)."""
   out = xl.Dataset()
   first = per_threshold[0]
+  quantiles = [th.quantile for th in thresholds]
+  method = type(thresholds[0]).__name__
   for name, (dims, _) in first.items():
-    out.coords.update(_result_coords(forecast, dims))
+    out.coords.update(coords_of(forecast, dims))
   if not sum_over_quantile:
     out.coords['quantile'] = np.array(list(quantiles), dtype=np.float64)
   for name, (dims, _) in first.items():
@@ -2530,10 +2514,8 @@ def _gauss_threshold_pass(forecast, truth, threshold_ds, name, region, skipna):
   mvar, svar = forecast[name], forecast[f'{name}_std']
   tvar, hvar = truth[name], threshold_ds[name]
   geo, prepared = _geometry(forecast, mvar, [svar, tvar, hvar])
-  tables = [_slab_table(geo.out_dims, geo.out_shape, p[1], p[0].shape[:-2])
-            for p in prepared]
   by_region, _ = _run_pass(_lib.MODE_GAUSS_THR, geo, [p[0] for p in prepared],
-                           tables, region, skipna)
+                           _operand_tables(geo, prepared), region, skipna)
   return geo, by_region
 
 
@@ -2548,14 +2530,6 @@ class ThresholdMetric(Metric):
   # dims of the LEFT operand come first in xarray: scores whose outermost
   # operand is derived from truth / the threshold are truth-first.
   _truth_first = True
-
-
-def _truth_first_order(dims, values, truth_dims):
-  tdims = [d for d in truth_dims if d in dims]
-  order = tuple(tdims + [d for d in dims if d not in tdims])
-  if order == tuple(dims):
-    return dims, values
-  return order, _transpose(values, [dims.index(d) for d in order])
 
 
 def _order_by(dims, values, precedence):
@@ -2599,9 +2573,7 @@ class _GaussianThresholdMetric(ThresholdMetric):
         per_var[name] = _order_by(geo.out_dims, by_region[rkey][self._row],
                                   precedence)
       per_threshold.append(per_var)
-    return _stack_quantiles(forecast, per_threshold,
-                            [th.quantile for th in self.thresholds],
-                            type(self.thresholds[0]).__name__,
+    return _stack_quantiles(forecast, per_threshold, self.thresholds,
                             self._sum_over_quantile)
 
 
@@ -2629,72 +2601,34 @@ class GaussianRPS(_GaussianThresholdMetric):
 def _ens_threshold_layout(forecast, truth, threshold_ds, name, ensemble_dim):
   """Device tensors and slab tables (members, truth, threshold) of one
   variable; the threshold may carry any subset of the output dims."""
-  fvar, tvar, hvar = forecast[name], truth[name], threshold_ds[name]
-  if ensemble_dim not in fvar.dims:
-    raise ValueError(f'{ensemble_dim=} not found in {fvar.dims=}')
-  fdata, frest, layout = _spatial_last(fvar, None)
-  tdata, trest, _ = _spatial_last(tvar, layout)
-  hdata, hrest, _ = _spatial_last(hvar, layout)
-  fsizes = dict(zip(frest, fdata.shape[:-2]))
-  n_member = fsizes[ensemble_dim]
-  out_dims = [d for d in frest if d != ensemble_dim]
-  sizes = {d: fsizes[d] for d in out_dims}
-  for rest, data in ((trest, tdata), (hrest, hdata)):
-    for d, n in zip(rest, data.shape[:-2]):
-      if d not in out_dims:
-        out_dims.append(d)
-        sizes[d] = n
-  out_dims = tuple(out_dims)
-  out_shape = tuple(sizes[d] for d in out_dims)
-  geo = _Geometry(layout, out_dims, out_shape,
-                  _coord_values(forecast, 'latitude'),
-                  _coord_values(forecast, 'longitude'))
-  stride, strides = 1, {}
-  for d in reversed(frest):
-    strides[d] = stride
-    stride *= fsizes[d]
-  ens_table = np.zeros(out_shape, dtype=np.int64)
-  for d in frest:
-    if d == ensemble_dim:
-      continue
-    shape = [1] * len(out_shape)
-    shape[out_dims.index(d)] = fsizes[d]
-    ens_table = ens_table + (np.arange(fsizes[d], dtype=np.int64)
-                             * strides[d]).reshape(shape)
-  ens_table = np.ascontiguousarray(ens_table).ravel()
+  outer = _ens_outer_layout(forecast, forecast[name],
+                            [truth[name], threshold_ds[name]], ensemble_dim)
+  geo = outer.geo
+  ens_table = outer.ens_table()
   identity = np.array_equal(ens_table, np.arange(ens_table.size))
-  t_table = _slab_table(out_dims, out_shape, trest, tdata.shape[:-2])
-  h_table = _slab_table(out_dims, out_shape, hrest, hdata.shape[:-2])
+  t_table, h_table = _operand_tables(geo, outer.prepared[1:])
   device = engine.require_gpu()
-  tens = [_to_device(x, device) for x in (fdata, tdata, hdata)]
-  dtype = tens[0].dtype
-  for x in tens[1:]:
-    dtype = torch.promote_types(dtype, x.dtype)
-  if dtype not in (torch.float32, torch.float64):
-    dtype = torch.float64
-  tens = [x if x.dtype == dtype else x.to(dtype) for x in tens]
-  for x in tens:
-    _check_grid(geo, x)
+  tens, _ = _common_float(
+      geo, [_to_device(data, device) for data, _ in outer.prepared])
   to_dev = lambda tb: None if tb is None else engine.upload_table(tb, device)
   tables = [None if identity else to_dev(ens_table), to_dev(t_table),
             to_dev(h_table)]
-  return geo, tens, tables, strides[ensemble_dim], n_member, device
+  return (geo, tens, tables, outer.strides[ensemble_dim], outer.n_member,
+          device)
 
 
 def _ens_threshold_pass(forecast, truth, threshold_ds, name, ensemble_dim,
                         region, skipna):
   geo, tens, tables, member_slabs, n_member, device = _ens_threshold_layout(
       forecast, truth, threshold_ds, name, ensemble_dim)
-  regions, _ = _region_set_for(region)
-  pl = plan_lib.cached_plan(geo.latitude, geo.longitude, geo.layout, regions,
-                            device, plan_lib.ENSEMBLE_ROWS_PER_CHUNK)
-  slab_elems = pl.n_row * pl.n_col
-  metrics = engine.ensemble_threshold_reduce(
-      pl, tens[0], member_slabs * slab_elems, n_member, tables[0],
-      tens[1].reshape(-1, pl.n_row, pl.n_col), tables[1],
-      tens[2].reshape(-1, pl.n_row, pl.n_col), tables[2], geo.n_outer, skipna)
-  dev = metrics.reshape((4, pl.n_region) + geo.out_shape)
-  return geo, {nm: dev[:, i] for i, nm in enumerate(pl.region_names)}
+  by_region = _regional_pass(
+      geo, region, device, plan_lib.ENSEMBLE_ROWS_PER_CHUNK, 4,
+      lambda pl: engine.ensemble_threshold_reduce(
+          pl, tens[0], member_slabs * pl.n_row * pl.n_col, n_member, tables[0],
+          tens[1].reshape(-1, pl.n_row, pl.n_col), tables[1],
+          tens[2].reshape(-1, pl.n_row, pl.n_col), tables[2], geo.n_outer,
+          skipna))
+  return geo, by_region
 
 
 def _ens_threshold_maps(forecast, truth, threshold_ds, name, ensemble_dim,
@@ -2713,6 +2647,7 @@ def _ens_threshold_maps(forecast, truth, threshold_ds, name, ensemble_dim,
 @dataclasses.dataclass
 class _EnsembleThresholdMetric(ThresholdMetric):
   ensemble_dim: str = REALIZATION
+  _result_attrs = EnsembleMetric._result_attrs
 
   def compute_chunk(self, forecast, truth, region=None, skipna=False):
     forecast, truth = _inputs(forecast, truth)
@@ -2722,16 +2657,14 @@ class _EnsembleThresholdMetric(ThresholdMetric):
       threshold_ds = threshold.compute(truth)
       per_var = {}
       for name in _common_vars(forecast, truth):
-        key = _result_key(('ens_thr', self.ensemble_dim, id(threshold)),
-                          [forecast[name].data, truth[name].data], region,
-                          skipna, (forecast, truth))
-        hit = _RESULTS.get(key)
-        if hit is None:
-          hit = _ens_threshold_pass(forecast, truth, threshold_ds, name,
-                                    self.ensemble_dim, region, skipna)
-          _RESULTS.put(key, (forecast[name].data, truth[name].data, threshold),
-                       hit)
-        geo, by_region = hit
+        pins = (forecast[name].data, truth[name].data)
+        geo, by_region = _cached_pass(
+            _result_key(('ens_thr', self.ensemble_dim, id(threshold)), pins,
+                        region, skipna, (forecast, truth)),
+            pins + (threshold,),  # (its id is in the key)
+            functools.partial(_ens_threshold_pass, forecast, truth,
+                              threshold_ds, name, self.ensemble_dim, region,
+                              skipna))
         _, rkey = _region_set_for(region)
         # dims in xarray's left-operand-first order (:1524-1560, 532-565,
         # 1722-1738, 1805-1817): forecast-led for the plain Brier score and
@@ -2745,15 +2678,8 @@ class _EnsembleThresholdMetric(ThresholdMetric):
                                  precedence)
         per_var[name] = (dims, values)
       per_threshold.append(per_var)
-    return _stack_quantiles(forecast, per_threshold,
-                            [th.quantile for th in self.thresholds],
-                            type(self.thresholds[0]).__name__,
+    return _stack_quantiles(forecast, per_threshold, self.thresholds,
                             self._sum_over_quantile)
-
-  def compute(self, forecast, truth, region=None, skipna=False):
-    forecast = xl.as_dataset(forecast)
-    result = super().compute(forecast, truth, region=region, skipna=skipna)
-    return result.assign_attrs(ensemble_size=forecast.sizes[self.ensemble_dim])
 
 
 @dataclasses.dataclass
@@ -2809,6 +2735,7 @@ class SEEPS(Metric):
   # reads concatenated chunks in place like the deterministic suite (one fused
   # pass through slab addresses): evaluate_chunks may batch chunks for it
   _reads_slabs_in_place = True
+  _fused_regions = True
 
   def _masked_p1(self, climatology, layout) -> np.ndarray:
     """p1 (the climatological dry fraction averaged over hour and day of year,
@@ -2821,8 +2748,7 @@ class SEEPS(Metric):
     if hit is not None and hit[0] == key and hit[1] is climatology:
       return hit[2]
     p1 = self._p1(climatology)
-    want = _SPATIAL if layout == plan_lib.LATLON else _SPATIAL[::-1]
-    p1v = p1.transpose(*want).values
+    p1v = p1.transpose(*_spatial_dims(layout)).values
     with np.errstate(invalid='ignore'):
       keep = np.logical_and(p1v < self.max_p1, p1v > self.min_p1)
     aux = np.where(keep, p1v.astype(np.float64), np.nan)
@@ -2836,48 +2762,28 @@ class SEEPS(Metric):
     fvar, tvar = forecast[name], truth[name]
     wvar = climatology[f'{name}_seeps_threshold']
     geo, prepared = _geometry(forecast, fvar, [tvar])
-    tables = [_slab_table(geo.out_dims, geo.out_shape, p[1], p[0].shape[:-2])
-              for p in prepared]
-    wrest = tuple(d for d in wvar.dims if d not in _SPATIAL)
-    wdata, _, _ = _spatial_last(wvar, geo.layout)
-    prepared.append((wdata, wrest))
-    wtable = _climatology_slabs(climatology, wvar, forecast, geo, wrest)
-    rec = program.recorder()
-    if rec is not None and not rec.probe:
-      sizes = tuple(wvar.sizes[d] for d in wrest)
-
-      def recompute(other, memo, climatology=climatology, wvar=wvar, geo=geo,
-                    wrest=wrest, sizes=sizes):
-        key = (id(climatology), wrest, sizes, geo.out_dims, geo.out_shape)
-        if key not in memo:
-          memo[key] = _climatology_slabs_by_content(climatology, wvar, other,
-                                                    geo, wrest)
-        return memo[key]
-      rec.note_table(wtable, recompute, _climatology_gather(
-          climatology, wvar, forecast, geo, wrest))
-    tables.append(wtable)
+    tables = _operand_tables(geo, prepared)
+    wdata, _, wtable = _climatology_operand(climatology, wvar, forecast, geo)
     aux = self._masked_p1(climatology, geo.layout)
-    return geo, [p[0] for p in prepared], tables, aux
+    return geo, [p[0] for p in prepared] + [wdata], tables + [wtable], aux
 
   def _pass(self, forecast, truth, region):
     """(geo, by_region) of the fused SEEPS pass for the active regions: one
     launch per weight-field group answers every region of it (cached for the
     chunk, like the deterministic passes)."""
     name = self.precip_name
-    pins = [forecast[name].data, truth[name].data]
-    key = _result_key(('seeps', name, self.dry_threshold_mm, self.min_p1,
-                       self.max_p1, id(self.climatology)), pins, region, True,
-                      (forecast, truth))
-    hit = _RESULTS.get(key)
-    if hit is not None:
-      return hit
-    geo, arrays, tables, aux = self._prepare(forecast, truth)
-    by_region, _ = _run_pass(
-        _lib.MODE_SEEPS, geo, arrays, tables, region, True,
-        aux=aux, scalar=self.dry_threshold_mm / 1000.0)
-    value = (geo, by_region)
-    _RESULTS.put(key, tuple(pins), value)
-    return value
+    pins = (forecast[name].data, truth[name].data)
+
+    def compute():
+      geo, arrays, tables, aux = self._prepare(forecast, truth)
+      by_region, _ = _run_pass(
+          _lib.MODE_SEEPS, geo, arrays, tables, region, True,
+          aux=aux, scalar=self.dry_threshold_mm / 1000.0)
+      return geo, by_region
+    return _cached_pass(
+        _result_key(('seeps', name, self.dry_threshold_mm, self.min_p1,
+                     self.max_p1, id(self.climatology)), pins, region, True,
+                    (forecast, truth)), pins, compute)
 
   def compute_chunk(self, forecast, truth, region=None, skipna=False,
                     regions: t.Optional[dict] = None):
@@ -2890,12 +2796,6 @@ class SEEPS(Metric):
     return _assemble(forecast, {self.precip_name: (lead + geo.out_dims,
                                                    values)}, regions)
 
-  def compute_chunk_regions(self, forecast, truth, regions, skipna=False):
-    return self.compute_chunk(forecast, truth, None, skipna, regions)
-
-  def compute_regions(self, forecast, truth, regions, skipna=False):
-    return self._mean_regions(forecast, truth, regions, skipna)
-
 
 # ---------------------------------------------------------------------------
 # Spatial* ensemble metrics (metrics.py:718-772, 1244-1266, 1366-1399): the
@@ -2904,21 +2804,14 @@ class SEEPS(Metric):
 _ENS_MAP_SLOT = {'skill': 0, 'spread': 1, 'mse': 2, 'var': 3, 'debiased': 5}
 
 
-def _device_temporal_mean(metric, forecast, truth, region, skipna,
-                          ensemble_dim=None) -> xl.Dataset:
+def _device_temporal_mean(metric, forecast, truth, region, skipna) -> xl.Dataset:
   """Metric.compute (metrics.py:117-138) for map-valued metrics whose chunk
   result lives on the device: (sum, count) over the time dim via
   wb2_time_accumulate, no host round trip of the per-time maps."""
   forecast_ds = xl.as_dataset(forecast)
-  avg_dim = 'time' if 'time' in forecast_ds.dims else 'init_time'
-  if avg_dim not in forecast_ds.dims:
-    raise ValueError(
-        'Forecast has neither valid_time or init_time dimension '
-        f'{forecast_ds}')
+  avg_dim = _time_average_dim(forecast_ds)
   chunk = metric.compute_chunk(forecast, truth, region=region, skipna=skipna)
-  attrs = dict(chunk.attrs)
-  if ensemble_dim is not None:
-    attrs['ensemble_size'] = forecast_ds.sizes[ensemble_dim]
+  attrs = {**chunk.attrs, **metric._result_attrs(forecast_ds)}
   out = xl.Dataset(coords={k: v for k, v in chunk.coords.items()
                            if k != avg_dim}, attrs=attrs)
   for name, da in chunk.data_vars.items():
@@ -2955,22 +2848,17 @@ class _SpatialEnsembleMetric(EnsembleMetric):
       geo, _, n_member, maps, dtype = _ens_pass(
           forecast, truth, name, self.ensemble_dim, None, skipna,
           want_maps=True)
-      spatial = _SPATIAL if geo.layout == plan_lib.LATLON else _SPATIAL[::-1]
-      dims = tuple(geo.out_dims) + tuple(spatial)
+      dims = tuple(geo.out_dims) + geo.spatial_dims
       data = self._map(maps, dtype, n_member)
       if self._truth_first:
-        tdims = [d for d in truth[name].dims if d in dims]
-        order = tuple(tdims + [d for d in dims if d not in tdims])
-        data = data.permute(*[dims.index(d) for d in order])
-        dims = order
+        dims, data = _order_by(dims, data, (truth[name].dims,))
       out.coords.update(_spatial_coords(forecast, dims))
       out.data_vars[name] = xl.DataArray(data, dims, out.coords, name)
     return out
 
   def compute(self, forecast, truth, region=None, skipna=False):
     """Temporal mean of the map, accumulated on the device."""
-    return _device_temporal_mean(self, forecast, truth, region, skipna,
-                                 self.ensemble_dim)
+    return _device_temporal_mean(self, forecast, truth, region, skipna)
 
 
 @dataclasses.dataclass
@@ -3028,45 +2916,28 @@ class DebiasedSpatialEnsembleMeanMSE(_SpatialEnsembleMetric):
 @dataclasses.dataclass
 class _SpatialEnsembleThresholdMetric(ThresholdMetric):
   ensemble_dim: str = REALIZATION
+  _result_attrs = EnsembleMetric._result_attrs
 
   def compute_chunk(self, forecast, truth, region=None, skipna=False):
     forecast, truth = _inputs(forecast, truth)
     _get_n_ensemble(forecast, self.ensemble_dim)
-    out = xl.Dataset()
-    names = _common_vars(forecast, truth)
-    stacks = {name: [] for name in names}
+    per_threshold = []
     for threshold in self.thresholds:
       threshold_ds = threshold.compute(truth)
-      for name in names:
+      per_var = {}
+      for name in _common_vars(forecast, truth):
         geo, maps = _ens_threshold_maps(forecast, truth, threshold_ds, name,
                                         self.ensemble_dim, skipna)
-        spatial = _SPATIAL if geo.layout == plan_lib.LATLON else _SPATIAL[::-1]
-        dims = tuple(geo.out_dims) + tuple(spatial)
-        data = maps[self._row]
+        dims, data = tuple(geo.out_dims) + geo.spatial_dims, maps[self._row]
         if self._truth_first:
-          tdims = [d for d in truth[name].dims if d in dims]
-          order = tuple(tdims + [d for d in dims if d not in tdims])
-          data = data.permute(*[dims.index(d) for d in order])
-          dims = order
-        stacks[name].append((dims, data))
-    for name in names:
-      dims = stacks[name][0][0]
-      data = torch.stack([d for _, d in stacks[name]])
-      out.coords.update(_spatial_coords(forecast, dims))
-      if self._sum_over_quantile:
-        out.data_vars[name] = xl.DataArray(_nansum_leading(data), dims,
-                                           out.coords, name)
-      else:
-        out.coords['quantile'] = np.array(
-            [th.quantile for th in self.thresholds], dtype=np.float64)
-        out.data_vars[name] = xl.DataArray(data, ('quantile',) + tuple(dims),
-                                           out.coords, name)
-    return out.assign_attrs(
-        threshold_method=type(self.thresholds[0]).__name__)
+          dims, data = _order_by(dims, data, (truth[name].dims,))
+        per_var[name] = (dims, data)
+      per_threshold.append(per_var)
+    return _stack_quantiles(forecast, per_threshold, self.thresholds,
+                            self._sum_over_quantile, _spatial_coords)
 
   def compute(self, forecast, truth, region=None, skipna=False):
-    return _device_temporal_mean(self, forecast, truth, region, skipna,
-                                 self.ensemble_dim)
+    return _device_temporal_mean(self, forecast, truth, region, skipna)
 
 
 @dataclasses.dataclass
@@ -3100,24 +2971,17 @@ class SpatialEnsembleRPS(_SpatialEnsembleThresholdMetric):
 class SpatialSEEPS(SEEPS):
   """SEEPS without spatial averaging (metrics.py:418-509): float64 map."""
 
-  _reads_slabs_in_place = False  # the map kernel reads whole arrays
-  # maps have no regions: the generic per-region fan-out of the base class
-  compute_chunk_regions = Metric.compute_chunk_regions
-  compute_regions = Metric.compute_regions
+  # Its own compute_chunk: the map kernel reads whole arrays, and maps have no
+  # regions (the per-region fan-out of the base class).
 
   def compute_chunk(self, forecast, truth, region=None, skipna=False):
     del region, skipna
     forecast, truth = _inputs(forecast, truth)
     geo, arrays, tables, aux = self._prepare(forecast, truth)
     device = engine.require_gpu()
-    tensors = [_to_device(a, device) for a in arrays]
-    dtype = torch.result_type(tensors[0], tensors[1])
-    dtype = torch.promote_types(dtype, tensors[2].dtype)
-    if dtype not in (torch.float32, torch.float64):
-      dtype = torch.float64
-    tensors = [x if x.dtype == dtype else x.to(dtype) for x in tensors]
-    for x in tensors:
-      _check_grid(geo, x)
+    # (promote_types over the dtypes is what torch.result_type gives for the
+    # tensors themselves: every operand has two or more dims, none is a scalar)
+    tensors, _ = _common_float(geo, [_to_device(a, device) for a in arrays])
     n_point = tensors[0].shape[-2] * tensors[0].shape[-1]
     slabs = [None if tb is None else engine.upload_table(tb, device)
              for tb in tables]
@@ -3125,8 +2989,7 @@ class SpatialSEEPS(SEEPS):
     out_map = engine.seeps_map(
         [x.reshape(-1, n_point) for x in tensors], slabs, geo.n_outer, n_point,
         aux_dev, self.dry_threshold_mm / 1000.0)
-    spatial = _SPATIAL if geo.layout == plan_lib.LATLON else _SPATIAL[::-1]
-    dims = tuple(geo.out_dims) + tuple(spatial)
+    dims = tuple(geo.out_dims) + geo.spatial_dims
     out = xl.Dataset()
     out.coords.update(_spatial_coords(forecast, dims))
     out.data_vars[self.precip_name] = xl.DataArray(
@@ -3202,8 +3065,7 @@ class RankHistogram(EnsembleMetric):
       shape = [1] * len(geo.out_shape)
       shape[ax] = n
       off = off + (np.arange(n, dtype=np.int64) * stride[d]).reshape(shape)
-    row_dim, col_dim = (_SPATIAL if geo.layout == plan_lib.LATLON
-                        else _SPATIAL[::-1])
+    row_dim, col_dim = geo.spatial_dims
     state = np.random.PCG64(self._seed).state['state']
     n_col = len(geo.longitude if geo.layout == plan_lib.LATLON
                 else geo.latitude)
@@ -3253,9 +3115,8 @@ class RankHistogram(EnsembleMetric):
       # the reciprocal when the divisor is a Python scalar)
       hist = hist / torch.full((), float(shape[axis]), dtype=hist.dtype,
                                device=hist.device)
-    spatial = _SPATIAL if geo.layout == plan_lib.LATLON else _SPATIAL[::-1]
     hist = hist.reshape(tuple(out_shape) + tuple(ften.shape[-2:]) + (n_bins,))
-    have = tuple(dims) + tuple(spatial) + ('bins',)
+    have = tuple(dims) + geo.spatial_dims + ('bins',)
     # the reference's result has the dims of its concatenated array (minus the
     # ensemble dim, `bins` last): a permuted VIEW where that order differs
     want = tuple(d for d in self._concat_dims(fvar, tvar)
@@ -3283,14 +3144,8 @@ class RankHistogram(EnsembleMetric):
   def compute(self, forecast, truth, region=None, skipna=False):
     """Rank histogram: the temporal mean of the one-hot encoding."""
     forecast_ds = xl.as_dataset(forecast)
-    avg_dim = 'time' if 'time' in forecast_ds.dims else 'init_time'
-    if avg_dim not in forecast_ds.dims:
-      raise ValueError(
-          'Forecast has neither valid_time or init_time dimension '
-          f'{forecast_ds}')
-    out = self._dataset(forecast, truth, avg_dim)
-    return out.assign_attrs(
-        ensemble_size=forecast_ds.sizes[self.ensemble_dim])
+    out = self._dataset(forecast, truth, _time_average_dim(forecast_ds))
+    return out.assign_attrs(**self._result_attrs(forecast_ds))
 
 
 def central_reliability(hist):

@@ -1457,6 +1457,49 @@ int wb2_window_quantile_geometry(int dtype, int64_t n_year, int32_t n_w,
                                  int64_t* lds_bytes,
                                  int32_t* key_bits_per_pass);
 
+/*
+ * K16: time re-indexing as a one-read slab scatter
+ * (scripts/expand_climatology.py, scripts/index_on_valid_time.py,
+ * scripts/compute_probabilistic_climatological_forecasts.py: datasets built by
+ * re-indexing whole slabs along time, where one source slab feeds many
+ * destinations).
+ *
+ * wb2_slab_scatter: source s is the n_point elements that start
+ * `src_slab[s] * n_point` after `in` (K13's slab convention, so a contiguous
+ * tensor, a time-sliced view and a gather's base differ in the table alone).
+ * For every d in dst_slab[dst_begin[s] .. dst_begin[s + 1]) the slab d of
+ * `out` (n_point elements of out_dtype each) becomes that source cast to
+ * out_dtype.  A source of -1 is read from nowhere and stores quiet NaN; a
+ * source without destinations is skipped; an entry may repeat a source.  The
+ * three tables are DEV int64: src_slab[n_source], dst_begin[n_source + 1]
+ * (CSR offsets, ascending from 0), dst_slab[dst_begin[n_source]].  The
+ * destinations are disjoint by contract and every table value is the
+ * caller's to check: the kernel cannot.  Dtype pairs: f32 -> f32, f64 -> f64
+ * and f64 -> f32 (round to nearest even; beyond float32's range gives inf);
+ * every other pair is refused.
+ * A thread owns adjacent points: 16-byte loads and stores where n_point is a
+ * multiple of the vector (4 points; 2 for f64 -> f64) and `in` and `out` are
+ * 16-byte aligned, scalar ones otherwise.  It loads its points once, before
+ * its first store.  A workgroup owns one tile of points of one source and
+ * blocks of dests_per_group >= 1 consecutive destinations of it.  The
+ * destination counts are on the device only, so the grid is (tiles x lanes) x
+ * sources: lane j takes the blocks j, j + lanes, ... of its source and reads
+ * nothing if it has none; one lane where sources x tiles fill the device, up
+ * to 64 where they do not.  No atomics, no LDS; neither dests_per_group nor
+ * the lane count changes a bit.  Checked before anything is enqueued: the
+ * dtype pair, dests_per_group, negative sizes, null pointers and a grid that
+ * does not fit.  Zero sizes of n_source or n_point are a no-op.
+ * wb2_slab_scatter_geometry: points per workgroup tile (wide != 0: 16-byte
+ * lanes) and the sources per grid row (more are split over a further grid
+ * dimension).
+ */
+int wb2_slab_scatter(int in_dtype, int out_dtype, const void* in,
+                     const int64_t* src_slab, const int64_t* dst_begin,
+                     const int64_t* dst_slab, int64_t n_source, int64_t n_point,
+                     int32_t dests_per_group, void* out, void* stream);
+int wb2_slab_scatter_geometry(int in_dtype, int out_dtype, int wide,
+                              int32_t* tile_points, int32_t* max_grid_outer);
+
 #ifdef __cplusplus
 }
 #endif

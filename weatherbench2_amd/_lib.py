@@ -230,6 +230,10 @@ _SIGNATURES = {
     'wb2_window_quantile_geometry': (_int, [
         _int, _i64, _i32, _c.POINTER(_i32), _c.POINTER(_i32),
         _c.POINTER(_i64), _c.POINTER(_i32)]),
+    'wb2_slab_scatter': (_int, [_int, _int, _vp, _vp, _vp, _vp, _i64, _i64,
+                                _i32, _vp, _vp]),
+    'wb2_slab_scatter_geometry': (_int, [_int, _int, _int, _c.POINTER(_i32),
+                                         _c.POINTER(_i32)]),
 }
 
 _lib = None

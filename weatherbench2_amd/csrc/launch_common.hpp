@@ -1,4 +1,4 @@
-// The launch vocabulary of the derived kernels (K7 - K14): how outer indices
+// The launch vocabulary of the derived kernels (K7 - K16): how outer indices
 // are spread over the grid, when a launch may use 16-byte lanes and how a
 // (dtype, width) pair picks a kernel instance.
 #pragma once

@@ -1532,6 +1532,117 @@ def window_quantile(x: torch.Tensor, slab: t.Optional[torch.Tensor],
   return quant, dry
 
 
+# (input dtype, output dtype) pairs of K16; every other pair is refused
+SCATTER_PAIRS = ((torch.float32, torch.float32), (torch.float64, torch.float64),
+                 (torch.float64, torch.float32))
+
+
+def slab_scatter_geometry(in_dtype: torch.dtype,
+                          out_dtype: t.Optional[torch.dtype] = None,
+                          wide: bool = False) -> dict:
+  """Extents of the K16 kernel: `tile_points` adjacent points per workgroup,
+  `max_grid_outer` sources per grid row."""
+  out_dtype = in_dtype if out_dtype is None else out_dtype
+  return _geometry('wb2_slab_scatter_geometry',
+                   (dtype_code(in_dtype), dtype_code(out_dtype), int(wide)),
+                   [('tile_points', _I32), ('max_grid_outer', _I32)])
+
+
+def scatter_csr(src, dst, n_in_slab: int, n_out_slab: int) -> tuple:
+  """(src_slab, dst_begin, dst_slab) as contiguous int64 HOST arrays, checked:
+  `src` one input slab per entry (-1: a NaN source; an entry may repeat a
+  slab), `dst` either a LIST of one sequence of output slabs per entry or the
+  CSR pair as a TUPLE (dst_begin, dst_slab).  Every output slab of
+  [0, n_out_slab) must be written exactly once and every source lie in
+  [-1, n_in_slab): the kernel trusts the tables."""
+  src = np.ascontiguousarray(src, dtype=np.int64).reshape(-1)
+  if isinstance(dst, tuple):
+    if len(dst) != 2 or np.ndim(dst[0]) != 1 or len(dst[0]) != src.size + 1:
+      raise ValueError('the CSR form is (dst_begin[n_source + 1], dst_slab)')
+    begin = np.ascontiguousarray(dst[0], dtype=np.int64)
+    slabs = np.ascontiguousarray(dst[1], dtype=np.int64).reshape(-1)
+  else:
+    lists = [np.asarray(d, dtype=np.int64).reshape(-1) for d in dst]
+    if len(lists) != src.size:
+      raise ValueError('one destination list per source entry is needed: '
+                       f'{len(lists)} lists, {src.size} sources')
+    begin = np.zeros(src.size + 1, dtype=np.int64)
+    np.cumsum([d.size for d in lists], out=begin[1:])
+    slabs = (np.concatenate(lists) if lists else np.zeros(0, np.int64))
+    slabs = np.ascontiguousarray(slabs, dtype=np.int64)
+  if begin[0] != 0 or np.any(np.diff(begin) < 0) or begin[-1] != slabs.size:
+    raise ValueError('dst_begin must ascend from 0 to the number of '
+                     'destinations')
+  if src.size and (src.min() < -1 or src.max() >= n_in_slab):
+    raise IndexError(f'source slab out of range [-1, {n_in_slab})')
+  if slabs.size and (slabs.min() < 0 or slabs.max() >= n_out_slab):
+    raise IndexError(f'destination slab out of range [0, {n_out_slab})')
+  written = np.bincount(slabs, minlength=n_out_slab)
+  if np.any(written != 1):
+    twice = np.flatnonzero(written > 1)
+    never = np.flatnonzero(written == 0)
+    raise ValueError(
+        'every output slab must be written exactly once: '
+        f'{twice.size} written more than once (first: {twice[:4].tolist()}), '
+        f'{never.size} never (first: {never[:4].tolist()})')
+  return src, begin, slabs
+
+
+def slab_scatter(x: torch.Tensor, src, dst, n_out_slab: int, *,
+                 n_point: t.Optional[int] = None,
+                 out_dtype: t.Optional[torch.dtype] = None,
+                 dests_per_group: int = 4,
+                 out: t.Optional[torch.Tensor] = None,
+                 checked: bool = False) -> torch.Tensor:
+  """K16: [n_out_slab, n_point] of `out_dtype` (default: that of `x`) in which
+  every slab listed for source entry s is the input slab `src[s]` cast to
+  `out_dtype`, and NaN where `src[s]` is -1; each input slab is read once
+  however many destinations it has.  Input slab k is the `n_point` elements
+  (default: everything behind the first dim of `x`) that start `k * n_point`
+  elements after the first element of `x`, so `x` is a contiguous tensor or a
+  view whose table addresses intact slabs of its storage.  `src` and `dst` are
+  HOST tables (`scatter_csr` checks them); `out`, if given, is the contiguous
+  result to fill.  `checked` says that `src` and `dst` are what `scatter_csr`
+  returned for this `n_out_slab` (a planner's CSR, perhaps shared by several
+  variables): only the sources are then held against the storage of `x`.
+  `dests_per_group` changes no result."""
+  out_dtype = x.dtype if out_dtype is None else out_dtype
+  if (x.dtype, out_dtype) not in SCATTER_PAIRS:
+    raise TypeError(f'unsupported dtype pair {x.dtype} -> {out_dtype}')
+  if n_point is None:
+    n_point = int(np.prod(x.shape[1:], dtype=np.int64)) if x.dim() else 1
+  n_point, n_out_slab = int(n_point), int(n_out_slab)
+  if n_point < 0 or n_out_slab < 0 or int(dests_per_group) < 1:
+    raise ValueError('bad sizes')
+  # the elements of the storage from the first element of `x` on
+  store = x.untyped_storage()
+  reach = (store.nbytes() - (x.data_ptr() - store.data_ptr())
+           ) // x.element_size() if x.numel() else 0
+  n_in_slab = reach // max(n_point, 1)
+  if checked:
+    src, (begin, slabs) = src, dst
+    if src.size and src.max() >= n_in_slab:
+      raise IndexError(f'source slab out of range [-1, {n_in_slab})')
+  else:
+    src, begin, slabs = scatter_csr(src, dst, n_in_slab, n_out_slab)
+  if out is None:
+    out = torch.empty((n_out_slab, n_point), dtype=out_dtype, device=x.device)
+  elif (out.dtype != out_dtype or out.numel() != n_out_slab * n_point
+        or not out.is_contiguous() or out.device != x.device):
+    raise ValueError('out must be a contiguous [n_out_slab, n_point] tensor of '
+                     'the output dtype on the device of the input')
+  if src.size == 0 or n_point == 0:
+    return out
+  tables = [upload_table(a, x.device) for a in (src, begin, slabs)]
+  # (an empty input has no address; every source is -1 then, nothing is read)
+  _launch('slab_scatter', 'wb2_slab_scatter', _DTYPES[x.dtype],
+          _DTYPES[out_dtype], _lib.ptr(x if x.numel() else out),
+          *[_lib.ptr(a) for a in tables],
+          int(src.size), n_point, int(dests_per_group), _lib.ptr(out),
+          current_stream_ptr(x.device))
+  return out
+
+
 def ensemble_threshold_reduce(plan: ReductionPlan, ens: torch.Tensor,
                               member_stride: int, n_member: int, ens_slab,
                               truth: torch.Tensor, truth_slab,

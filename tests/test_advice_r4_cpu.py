@@ -2,7 +2,7 @@
 import numpy as np
 import pytest
 
-from weatherbench2_amd import engine, evaluation
+from weatherbench2_amd import engine, evaluation, indexing
 from weatherbench2_amd import xarray_lite as xl
 
 
@@ -20,10 +20,11 @@ def test_datetime_labels_match_across_units():
           np.arange(8) * np.timedelta64(6, 'h'))
   want = (np.datetime64('2020-01-01T00', 'h') +
           np.array([[0, 6], [12, 42]]).astype('timedelta64[h]'))
-  pos = evaluation._positions(have, want, 'time')
+  pos = indexing.sel_positions(have, want, 'time: {label!r}')
   np.testing.assert_array_equal(pos, [[0, 1], [2, 7]])
   with pytest.raises(KeyError):
-    evaluation._positions(have, want + np.timedelta64(1, 'h'), 'time')
+    indexing.sel_positions(have, want + np.timedelta64(1, 'h'),
+                           'time: {label!r}')
   lead_s = np.array([0, 21600], dtype='timedelta64[s]')
   lead_ns = lead_s.astype('timedelta64[ns]')
   assert xl.label_list(lead_s) == xl.label_list(lead_ns)

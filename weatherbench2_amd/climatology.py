@@ -112,6 +112,7 @@ import numpy as np
 import torch
 
 from weatherbench2_amd import engine
+from weatherbench2_amd import indexing
 from weatherbench2_amd import operands
 from weatherbench2_amd import resampling
 from weatherbench2_amd import xarray_lite as xl
@@ -150,19 +151,12 @@ def _weights(window_weights) -> np.ndarray:
 
 def calendar(times) -> tuple:
   """(year, day of year 1..366, hour of day, day number) of a datetime64
-  coordinate, each int64."""
+  coordinate, each int64: `indexing.calendar` of a 1-D time axis."""
   times = np.asarray(times)
   if times.ndim != 1 or times.dtype.kind != 'M':
     raise ValueError('the time coordinate must be a 1-D datetime64 array, '
                      f'not {times.dtype} {times.shape}')
-  if np.isnat(times).any():
-    raise ValueError('the time coordinate holds NaT')
-  day = times.astype('datetime64[D]')
-  year_start = times.astype('datetime64[Y]')
-  year = year_start.astype(np.int64) + 1970
-  doy = (day - year_start.astype('datetime64[D]')).astype(np.int64) + 1
-  hour = times.astype('datetime64[h]').astype(np.int64) % 24
-  return year, doy, hour, day.astype(np.int64)
+  return indexing.calendar(times)
 
 
 def _year_bound(value, which: str) -> t.Optional[int]:

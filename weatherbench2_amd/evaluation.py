@@ -48,6 +48,7 @@ import typing as t
 import numpy as np
 
 from weatherbench2_amd import config
+from weatherbench2_amd import indexing
 from weatherbench2_amd import metrics as metrics_lib
 from weatherbench2_amd import xarray_lite as xl
 
@@ -193,11 +194,9 @@ def select_truth_at_valid_time(truth, forecast, time_dim: str = 'time',
   else:
     valid = init[:, None] + lead[None, :]
   have = np.asarray(truth.coords[time_dim])
-  pos = {v: i for i, v in enumerate(xl.label_list(have))}
-  try:
-    index = np.array([pos[v] for v in xl.label_list(valid)], dtype=np.int64)
-  except KeyError as e:
-    raise KeyError(f'not all valid times found in truth.{time_dim}: {e}') from e
+  index = indexing.sel_positions(
+      have, valid,
+      f'not all valid times found in truth.{time_dim}: {{label!r}}').ravel()
   coords = {k: v for k, v in truth.coords.items()
             if k != time_dim and not (isinstance(v, xl.DataArray)
                                       and time_dim in v.dims)}
@@ -1739,14 +1738,8 @@ def _with_derived(dataset: xl.Dataset, derived: dict) -> xl.Dataset:
 _index_values = xl.coord_values
 
 
-def _positions(have: np.ndarray, want: np.ndarray, what: str) -> np.ndarray:
-  """Positions of the labels `want` in the index `have` (KeyError like .sel)."""
-  pos = {v: i for i, v in enumerate(xl.label_list(have))}
-  try:
-    flat = [pos[v] for v in xl.label_list(want)]
-  except KeyError as e:
-    raise KeyError(f'not all values found in index {what!r}: {e}') from e
-  return np.array(flat, dtype=np.int64).reshape(np.shape(want))
+# (what a label that an index lacks raises, like .sel: indexing.sel_positions)
+_ABSENT = 'not all values found in index {!r}: {{label!r}}'
 
 
 def _slab_source(da: xl.DataArray):
@@ -1792,38 +1785,21 @@ def _gather_dataset(source: xl.Dataset, names, selectors: dict, new_dims: tuple,
       raise ValueError(f'{name}: dims {missing} to select are not in {da.dims}')
     sizes = dict(zip(outer, (prior.shape if prior is not None
                              else base.shape[:-2])))
-    out_dims: list = []
-    for d in outer:
-      for nd in (new_dims if d in selectors else (d,)):
-        if nd not in out_dims:
-          out_dims.append(nd)
-    out_shape = tuple(new_shape[new_dims.index(d)] if d in new_dims
-                      else sizes[d] for d in out_dims)
-    index = np.zeros(out_shape, dtype=np.int64)
-    hole = np.zeros(out_shape, dtype=bool)
-    stride = 1
-    for d in reversed(outer):
-      if d in selectors:
-        pos = np.asarray(selectors[d], dtype=np.int64)
-        shape = [1] * len(out_dims)
-        for nd, n in zip(new_dims, new_shape):
-          shape[out_dims.index(nd)] = n
-        order = [nd for nd in out_dims if nd in new_dims]
-        pos = np.transpose(pos, [new_dims.index(nd) for nd in order]
-                           ).reshape(shape)
-        hole = hole | (pos < 0)
-        index = index + np.maximum(pos, 0) * stride
-      else:
-        shape = [1] * len(out_dims)
-        shape[out_dims.index(d)] = sizes[d]
-        index = index + (np.arange(sizes[d], dtype=np.int64) * stride
-                         ).reshape(shape)
-      stride *= sizes[d]
+    src = tuple(d for d in outer if d in selectors)
+    picks = [np.asarray(selectors[d], dtype=np.int64) for d in src]
+    hole = np.logical_or.reduce([p < 0 for p in picks])
+    table = np.ravel_multi_index([np.where(hole, 0, p) for p in picks],
+                                 [sizes[d] for d in src]) if hole.size \
+        else np.zeros(hole.shape, np.int64)
+    re_ = indexing.Reindex(src, tuple(new_dims),
+                           np.where(hole, -1, table).reshape(new_shape))
+    out_dims = indexing.in_place_dims(outer, src, re_.new_dims)
+    index = indexing.slab_table(outer + spatial, sizes, out_dims + spatial,
+                                re_, 2)
     if prior is not None:  # a gather of a gather: compose the tables
-      index = prior.ravel()[index]
-    index = np.where(hole, -1, index)
+      index = indexing.compose(index, prior.ravel())
     out.data_vars[name] = xl.DataArray(
-        xl.SlabGather(base, index), tuple(out_dims) + spatial, out_coords, name)
+        xl.SlabGather(base, index), out_dims + spatial, out_coords, name)
   return out
 
 
@@ -1842,14 +1818,6 @@ def _when(forecast: xl.Dataset, time_dim: str):
                                           or k in dims):
       carried[k] = v
   return values, dims, carried
-
-
-def _dayofyear_hour(values: np.ndarray):
-  import pandas as pd
-  idx = pd.DatetimeIndex(np.asarray(values).ravel())
-  shape = np.shape(values)
-  return (np.asarray(idx.dayofyear).reshape(shape),
-          np.asarray(idx.hour).reshape(shape))
 
 
 def _climatology_variables(climatology: xl.Dataset, variables) -> dict:
@@ -1880,14 +1848,15 @@ def climatology_like_forecast(forecast, climatology, time_dim: str,
   if variables is None:
     variables = list(forecast.keys())
   values, dims, carried = _when(forecast, time_dim)
-  doy, hour = _dayofyear_hour(values)
-  selectors = {'dayofyear': _positions(_index_values(climatology, 'dayofyear'),
-                                       doy, 'dayofyear')}
+  _, doy, hour, _ = indexing.calendar(values)
+  selectors = {'dayofyear': indexing.sel_positions(
+      _index_values(climatology, 'dayofyear'), doy,
+      _ABSENT.format('dayofyear'))}
   coords = dict(carried)
   coords['dayofyear'] = xl.DataArray(doy, dims)
   if not hour_if_present or 'hour' in climatology.coords:
-    selectors['hour'] = _positions(_index_values(climatology, 'hour'), hour,
-                                   'hour')
+    selectors['hour'] = indexing.sel_positions(
+        _index_values(climatology, 'hour'), hour, _ABSENT.format('hour'))
     coords['hour'] = xl.DataArray(hour, dims)
   if hour_if_present:
     names = _climatology_variables(climatology, variables)
@@ -1912,14 +1881,11 @@ def make_probabilistic_climatology(ds, start_year: int, end_year: int,
   NaN.  Nothing is copied: member `number` of (hour, dayofyear) is the time
   step of `ds` with that (year, dayofyear, hour), kept as a SlabGather index
   over `ds`'s own array, -1 where the year has no such step."""
-  import pandas as pd
   given = ds
   ds = xl.as_dataset(ds)
   hours = np.arange(0, 24, hour_interval)
   years = np.arange(start_year, end_year + 1)
-  times = pd.DatetimeIndex(_index_values(ds, 'time'))
-  t_year, t_doy, t_hour = (np.asarray(times.year), np.asarray(times.dayofyear),
-                           np.asarray(times.hour))
+  t_year, t_doy, t_hour, _ = indexing.calendar(_index_values(ds, 'time'))
   for year in years:  # `.sel(time=str(year))` of a year without data: KeyError
     if not (t_year == year).any():
       raise KeyError(str(year))
@@ -1963,7 +1929,8 @@ def create_persistence_forecast(forecast, obs):
   lead_max = max(np.max(_index_values(forecast, d)) for d in lead_dims)
   keep = time >= time[0] + lead_max  # label slice(start, None), ascending time
   init_values = np.asarray(init.values)[keep]
-  where = _positions(_index_values(obs, 'time'), init_values, 'time')
+  where = indexing.sel_positions(_index_values(obs, 'time'), init_values,
+                                 _ABSENT.format('time'))
   coords = {'time': time[keep]}
   for d in lead_dims:
     coords[d] = _index_values(forecast, d)
@@ -1996,7 +1963,8 @@ def _persistence_like_forecast_chunk(forecast_chunk, truth_chunk, truth,
   lead_dim = _lead_dim(forecast_chunk)
   init = _index_values(forecast_chunk, 'init_time')
   lead = _index_values(forecast_chunk, lead_dim)
-  pos = _positions(_index_values(truth, 'time'), init, 'time')
+  pos = indexing.sel_positions(_index_values(truth, 'time'), init,
+                               _ABSENT.format('time'))
   where = np.broadcast_to(pos[None, :], (len(lead), len(init)))
   coords = {lead_dim: lead, 'init_time': init}
   if 'valid_time' in forecast_chunk.coords:

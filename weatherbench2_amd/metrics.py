@@ -38,6 +38,7 @@ import torch
 
 from weatherbench2_amd import _lib
 from weatherbench2_amd import engine
+from weatherbench2_amd import indexing
 from weatherbench2_amd import plan as plan_lib
 from weatherbench2_amd import program
 from weatherbench2_amd import xarray_lite as xl
@@ -660,47 +661,8 @@ def _get_climatology_chunk(climatology: xl.Dataset, truth: xl.Dataset) -> dict:
   return {v: climatology[k] for k, v in clim_var_dict.items()}
 
 
-def _label_positions(have: np.ndarray, want: np.ndarray, what: str):
-  """Positions of the labels `want` in the index `have` (KeyError like .sel).
-  Numeric labels (dayofyear, hour, level) by binary search -- this runs once per
-  chunk; a dict of the whole index, rebuilt per call, cost more than the
-  lookup."""
-  have, want = np.asarray(have), np.asarray(want)
-  if have.dtype.kind in 'iuf' and want.dtype.kind in 'iuf' and have.size:
-    sorter = np.argsort(have, kind='stable')
-    at = np.searchsorted(have, want.ravel(), sorter=sorter)
-    at = np.minimum(at, have.size - 1)
-    pos = sorter[at]
-    miss = have[pos] != want.ravel()
-    if miss.any():
-      raise KeyError(f'{what} label {want.ravel()[miss][0]!r} not found in '
-                     'climatology')
-    return pos.astype(np.int64).reshape(np.shape(want))
-  pos = {v: i for i, v in enumerate(xl.label_list(have))}
-  try:
-    return np.array([pos[v] for v in xl.label_list(want)],
-                    dtype=np.int64).reshape(np.shape(want))
-  except KeyError as e:
-    raise KeyError(f'{what} label {e} not found in climatology') from e
-
-
-def _dayofyear_hour(vt: np.ndarray):
-  """(dayofyear 1.., hour of day) of datetime64 values, like pandas'
-  DatetimeIndex.dayofyear / .hour (metrics.py:71-75) -- in NumPy: a
-  DatetimeIndex per chunk cost 0.13 ms."""
-  vt = np.asarray(vt)
-  if vt.dtype.kind != 'M':
-    import pandas as pd
-    idx = pd.DatetimeIndex(vt.ravel())
-    return (np.asarray(idx.dayofyear).reshape(vt.shape),
-            np.asarray(idx.hour).reshape(vt.shape))
-  days = vt.astype('datetime64[D]')
-  year0 = vt.astype('datetime64[Y]').astype('datetime64[D]')
-  doy = (days - year0).astype(np.int64) + 1
-  hour = (vt.astype('datetime64[h]') - days.astype('datetime64[h]')).astype(
-      np.int64)
-  return doy, hour
-
+# (a label the climatology lacks, like .sel: indexing.sel_positions)
+_ABSENT = '{} label {{label!r}} not found in climatology'
 
 _CLIM_TABLES: dict = {}  # content key -> table (bounded; see _climatology_slabs)
 
@@ -788,34 +750,6 @@ def _climatology_strides(crest, sizes) -> dict:
   return strides
 
 
-_LABEL_LUTS: dict = {}  # id(label array) -> (array, lookup table or None)
-
-
-def _small_label_positions(have: np.ndarray, want: np.ndarray, what: str):
-  """_label_positions for an index of small non-negative integers (dayofyear
-  1..366, hour 0..23) through a dense lookup table remembered per label array
-  OBJECT: the per-chunk cost of a climatology gather is two tiny fancy
-  indexings instead of two argsorts."""
-  hit = _LABEL_LUTS.get(id(have))
-  if hit is None or hit[0] is not have:
-    lut = None
-    if have.dtype.kind in 'iu' and have.size and have.min() >= 0 and (
-        have.max() < 4096) and len(np.unique(have)) == have.size:
-      lut = np.full(int(have.max()) + 2, -1, dtype=np.int64)
-      lut[have] = np.arange(have.size, dtype=np.int64)
-    if len(_LABEL_LUTS) >= 64:
-      _LABEL_LUTS.clear()
-    hit = _LABEL_LUTS[id(have)] = (have, lut)
-  lut = hit[1]
-  if lut is None or want.dtype.kind not in 'iu':
-    return _label_positions(have, want, what)
-  pos = lut[np.clip(want, -1, lut.size - 1)]
-  if (pos < 0).any():
-    bad = np.asarray(want).ravel()[(pos < 0).ravel()][0]
-    raise KeyError(f'{what} label {bad!r} not found in climatology')
-  return pos
-
-
 def _climatology_time_values(climatology, crest, sizes, vt,
                              memo: t.Optional[dict] = None) -> np.ndarray:
   """The time part of the climatology slab number of every valid time in `vt`
@@ -825,15 +759,17 @@ def _climatology_time_values(climatology, crest, sizes, vt,
   strides = _climatology_strides(crest, sizes)
   when = None if memo is None else memo.get('doy_hour')
   if when is None or when[0] is not vt:
-    when = (vt,) + tuple(_dayofyear_hour(vt))
+    when = (vt,) + indexing.calendar(vt)[1:3]
     if memo is not None:
       memo['doy_hour'] = when
   _, doy, hour = when
-  tpart = _small_label_positions(_coord_values(climatology, 'dayofyear'), doy,
-                                 'dayofyear') * strides['dayofyear']
+  tpart = indexing.sel_positions(
+      _coord_values(climatology, 'dayofyear'), doy,
+      _ABSENT.format('dayofyear')) * strides['dayofyear']
   if 'hour' in climatology.coords and 'hour' in crest:
-    tpart = tpart + _small_label_positions(
-        _coord_values(climatology, 'hour'), hour, 'hour') * strides['hour']
+    tpart = tpart + indexing.sel_positions(
+        _coord_values(climatology, 'hour'), hour,
+        _ABSENT.format('hour')) * strides['hour']
   return tpart
 
 
@@ -859,8 +795,9 @@ def _climatology_structure(climatology, cvar, forecast, geo, crest, vt_shape,
   if 'level' in crest:
     if 'level' not in geo.out_dims:
       raise ValueError('climatology has a level dim but the forecast has none')
-    lv = _label_positions(_coord_values(climatology, 'level'),
-                          _coord_values(forecast, 'level'), 'level')
+    lv = indexing.sel_positions(_coord_values(climatology, 'level'),
+                                _coord_values(forecast, 'level'),
+                                _ABSENT.format('level'))
     shape = [1] * len(geo.out_shape)
     shape[geo.out_dims.index('level')] = len(lv)
     base = base + (lv * strides['level']).reshape(shape)

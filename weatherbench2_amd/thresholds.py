@@ -17,18 +17,13 @@ import typing as t
 import numpy as np
 from scipy import stats
 
+from weatherbench2_amd import indexing
 from weatherbench2_amd import xarray_lite as xl
 
 
 _coord = xl.coord_values
-
-
-def _positions(have: np.ndarray, want: np.ndarray, what: str) -> np.ndarray:
-  pos = {v: i for i, v in enumerate(np.asarray(have).tolist())}
-  try:
-    return np.array([pos[v] for v in np.asarray(want).tolist()], dtype=np.int64)
-  except KeyError as e:
-    raise KeyError(f'{what} label {e} not found in climatology') from e
+# (a label the climatology lacks, like .sel: indexing.sel_positions)
+_ABSENT = '{} label {{label!r}} not found in climatology'
 
 
 def _time_gather(climatology: xl.Dataset, truth: xl.Dataset,
@@ -41,7 +36,6 @@ def _time_gather(climatology: xl.Dataset, truth: xl.Dataset,
   (`truth.sel(time=forecast.valid_time)`, evaluation.py:474) has dims
   (init_time, lead) and BOTH are 2-D coordinates over them; the gathered
   threshold then gets those dims, exactly like xarray's vectorised `.sel`."""
-  import pandas as pd
   time_dim = 'time' if 'time' in truth.dims else 'valid_time'
 
   def labels(name):
@@ -60,19 +54,19 @@ def _time_gather(climatology: xl.Dataset, truth: xl.Dataset,
   hour_labels, hdims = labels(time_dim)
   if hdims != tdims:
     hour_labels = np.transpose(hour_labels, [hdims.index(d) for d in tdims])
-  shape = day_labels.shape
-  doy = np.asarray(pd.DatetimeIndex(day_labels.ravel()).dayofyear)
-  doy_idx = _positions(_coord(climatology, 'dayofyear'), doy,
-                       'dayofyear').reshape(shape)
+  doy_idx = indexing.sel_positions(_coord(climatology, 'dayofyear'),
+                                   indexing.calendar(day_labels)[1],
+                                   _ABSENT.format('dayofyear'))
   has_hour = 'hour' in climatology.coords
   if has_hour:
-    hour = np.asarray(pd.DatetimeIndex(hour_labels.ravel()).hour)
-    hour_idx = _positions(_coord(climatology, 'hour'), hour,
-                          'hour').reshape(shape)
+    hour_idx = indexing.sel_positions(_coord(climatology, 'hour'),
+                                      indexing.calendar(hour_labels)[2],
+                                      _ABSENT.format('hour'))
   level_idx = None
   if 'level' in truth.dims and 'level' in climatology.coords:
-    level_idx = _positions(_coord(climatology, 'level'), _coord(truth, 'level'),
-                           'level')
+    level_idx = indexing.sel_positions(_coord(climatology, 'level'),
+                                       _coord(truth, 'level'),
+                                       _ABSENT.format('level'))
   coords = {k: c for k, c in truth.coords.items()}
   out = xl.Dataset(coords=coords)
   for src, dst in variables.items():

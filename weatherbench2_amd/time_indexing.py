@@ -43,6 +43,7 @@ import torch
 
 from weatherbench2_amd import climatology as _climatology
 from weatherbench2_amd import engine
+from weatherbench2_amd import indexing
 from weatherbench2_amd import operands
 from weatherbench2_amd import resampling
 from weatherbench2_amd import xarray_lite as xl
@@ -101,62 +102,6 @@ def plan_scatter(dest_to_src, n_in_slab: t.Optional[int] = None) -> tuple:
     src = np.repeat(src, pieces)
   return engine.scatter_csr(src, (begin, order.astype(np.int64)), n_in_slab,
                             table.size)
-
-
-class _Reindex(t.NamedTuple):
-  """`table` (int64, one axis per dim of `new_dims`) holds, per position of
-  the new dims, the C-order position in the grid of `src_dims` of the input;
-  -1 = none.  A name may stand in both: a dim that is re-indexed in place."""
-  src_dims: tuple
-  new_dims: tuple
-  table: np.ndarray
-
-
-def _slab_table(in_dims, sizes, out_dims, re_: _Reindex, n_inner: int):
-  """int64 over the output's dims before the last `n_inner`: the input slab
-  (C order over the input's dims before its last `n_inner`) each output slab
-  is a copy of, -1 for a hole."""
-  in_outer = tuple(in_dims[:len(in_dims) - n_inner])
-  out_outer = tuple(out_dims[:len(out_dims) - n_inner])
-  stride, s = {}, 1
-  for d in reversed(in_outer):
-    stride[d] = s
-    s *= sizes[d]
-  # the table's axes in the order the new dims stand in the output
-  perm = sorted(range(len(re_.new_dims)),
-                key=lambda i: out_outer.index(re_.new_dims[i]))
-  table = np.transpose(re_.table, perm)
-  hole = table < 0
-  parts = np.unravel_index(np.where(hole, 0, table).ravel(),
-                           [sizes[d] for d in re_.src_dims]) if table.size \
-      else [np.zeros(0, np.int64)] * len(re_.src_dims)
-  flat = np.zeros(table.size, dtype=np.int64)
-  for d, p in zip(re_.src_dims, parts):
-    flat += p.astype(np.int64) * stride[d]
-  shape = [1] * len(out_outer)
-  for i in perm:
-    shape[out_outer.index(re_.new_dims[i])] = re_.table.shape[i]
-  full = flat.reshape(shape)
-  hole = hole.reshape(shape)
-  for ax, d in enumerate(out_outer):
-    if d in re_.new_dims:
-      continue
-    along = [1] * len(out_outer)
-    along[ax] = sizes[d]
-    full = full + (np.arange(sizes[d], dtype=np.int64) * stride[d]
-                   ).reshape(along)
-    hole = np.broadcast_to(hole, full.shape)
-  return np.where(np.broadcast_to(hole, full.shape), -1, full)
-
-
-def _common_tail(in_dims, out_dims, re_: _Reindex) -> int:
-  k = 0
-  while (k < min(len(in_dims), len(out_dims))
-         and in_dims[-1 - k] == out_dims[-1 - k]
-         and in_dims[-1 - k] not in re_.src_dims
-         and out_dims[-1 - k] not in re_.new_dims):
-    k += 1
-  return k
 
 
 def _float_target(dtype: np.dtype, out_dtype, holes: bool):
@@ -219,8 +164,7 @@ def _device_reindex(da: xl.DataArray, planned: dict, n_inner: int,
     return _torch_reindex(ten.reshape(-1, n_point), table, out_dtype)
   ten, physical = operands.operand(da, da.dims, device, dtype, n_inner)
   if physical is not None:  # a view or a gather: where the slabs really lie
-    src, begin, dst = plan_scatter(
-        np.where(table < 0, -1, physical[np.maximum(table, 0)]))
+    src, begin, dst = plan_scatter(indexing.compose(table, physical))
   else:
     if 'csr' not in planned:
       planned['csr'] = plan_scatter(table)
@@ -230,14 +174,14 @@ def _device_reindex(da: xl.DataArray, planned: dict, n_inner: int,
                              checked=True)
 
 
-def _lazy_reindex(da: xl.DataArray, in_dims, sizes, out_dims, re_: _Reindex,
-                  out_dtype) -> xl.SlabGather:
-  if _common_tail(in_dims, out_dims, re_) < 2:
+def _lazy_reindex(da: xl.DataArray, in_dims, sizes, out_dims,
+                  re_: indexing.Reindex, out_dtype) -> xl.SlabGather:
+  if indexing.common_tail(in_dims, out_dims, re_) < 2:
     raise ValueError(
         f'materialize=False needs the last two dims of {da.name!r} to be a '
         f'slab that is not re-indexed: its dims are {tuple(in_dims)}, '
         f'{re_.src_dims} are re-indexed')
-  table = _slab_table(in_dims, sizes, out_dims, re_, 2)
+  table = indexing.slab_table(in_dims, sizes, out_dims, re_, 2)
   data = da.data
   prior = None
   if isinstance(data, xl.SlabGather):
@@ -255,12 +199,13 @@ def _lazy_reindex(da: xl.DataArray, in_dims, sizes, out_dims, re_: _Reindex,
   data = data.contiguous() if isinstance(data, torch.Tensor) \
       else np.ascontiguousarray(data)
   if prior is not None:  # a gather of a gather: compose the tables
-    table = np.where(table < 0, -1, prior[np.maximum(table, 0)])
+    table = indexing.compose(table, prior)
   return xl.SlabGather(data, table)
 
 
-def _reindex_variable(da: xl.DataArray, out_dims: tuple, re_: _Reindex,
-                      out_dtype, materialize: bool, memo: dict):
+def _reindex_variable(da: xl.DataArray, out_dims: tuple,
+                      re_: indexing.Reindex, out_dtype, materialize: bool,
+                      memo: dict):
   """The data of `da` re-indexed by `re_`, its dims then `out_dims`.  `memo`
   lives for one call of an entry point and one `re_`: the slab table (and its
   CSR) of variables with the same outer dims and slab depth is made once."""
@@ -273,14 +218,15 @@ def _reindex_variable(da: xl.DataArray, out_dims: tuple, re_: _Reindex,
                     for d in out_dims)
   if not materialize:
     return _lazy_reindex(da, in_dims, sizes, out_dims, re_, out_dtype)
-  k = _common_tail(in_dims, out_dims, re_)
+  k = indexing.common_tail(in_dims, out_dims, re_)
   if isinstance(da.data, xl.SlabGather):
     k = min(k, 2)  # (a gather's base is addressed slab by slab)
   n_point = math.prod(out_shape[len(out_shape) - k:])
   key = (tuple((d, sizes[d]) for d in in_dims[:len(in_dims) - k]),
          tuple(out_dims[:len(out_dims) - k]))
   if key not in memo:
-    memo[key] = {'table': _slab_table(in_dims, sizes, out_dims, re_, k)}
+    memo[key] = {'table': indexing.slab_table(in_dims, sizes, out_dims, re_,
+                                              k)}
   table = memo[key]['table']
   if operands.on_device(da.data):
     if table.size * n_point == 0:
@@ -292,32 +238,6 @@ def _reindex_variable(da: xl.DataArray, out_dims: tuple, re_: _Reindex,
                            out_dtype).reshape(out_shape)
   return _host_reindex(np.asarray(da.values), table, n_point,
                        out_dtype).reshape(out_shape)
-
-
-def _in_place_dims(dims: tuple, src_dims: tuple, new_dims: tuple) -> tuple:
-  """xarray's rule for vectorised indexing: walk the dims in order, the first
-  indexed dim becomes `new_dims`, the other indexed dims go."""
-  out: list = []
-  for d in dims:
-    if d in src_dims:
-      if not any(n in out for n in new_dims):
-        out.extend(new_dims)
-    else:
-      out.append(d)
-  return tuple(out)
-
-
-def _positions(labels: np.ndarray, wanted: np.ndarray) -> np.ndarray:
-  """Position in `labels` (int64, unique) of every entry of `wanted`, -1
-  where it is not among them."""
-  labels = np.asarray(labels, dtype=np.int64)
-  wanted = np.asarray(wanted, dtype=np.int64)
-  order = np.argsort(labels, kind='stable')
-  at = np.searchsorted(labels, wanted, sorter=order)
-  at = order[np.minimum(at, max(len(labels) - 1, 0))] if len(labels) \
-      else np.zeros(wanted.shape, np.int64)
-  found = labels[at] == wanted if len(labels) else np.zeros(wanted.shape, bool)
-  return np.where(found, at, -1).astype(np.int64)
 
 
 def _ns(values, kind: str) -> np.ndarray:
@@ -408,9 +328,9 @@ def expand_climatology(climatology, times=None, *, time_start=None,
                                  dtype=np.int64))
   times = np.asarray(times).astype('datetime64[ns]')
   _, doy, hour, _ = _climatology.calendar(times)
-  where = {'dayofyear': _positions(doys, doy)}
+  where = {'dayofyear': indexing.positions(doys, doy)}
   if has_hour:
-    where['hour'] = _positions(hours, hour)
+    where['hour'] = indexing.positions(hours, hour)
   for dim, pos in where.items():
     if (pos < 0).any():
       labels = (doy if dim == 'dayofyear' else hour)[pos < 0]
@@ -427,8 +347,8 @@ def expand_climatology(climatology, times=None, *, time_start=None,
     table = np.ravel_multi_index([where[d] for d in src],
                                  [da.sizes[d] for d in src]) if times.size \
         else np.zeros(0, np.int64)
-    re_ = _Reindex(src, (TIME,), np.asarray(table, dtype=np.int64))
-    dims[name] = _in_place_dims(da.dims, src, (TIME,))
+    re_ = indexing.Reindex(src, (TIME,), np.asarray(table, dtype=np.int64))
+    dims[name] = indexing.in_place_dims(da.dims, src, (TIME,))
     data[name] = _reindex_variable(da, dims[name], re_, None, materialize,
                                    memos.setdefault(src, {}))
   return _rebuild(dataset, coords, data, dims)
@@ -495,20 +415,20 @@ def index_on_valid_time(forecast, desired_time_dims: str = VALID_AND_DELTA, *,
     kept = np.arange(offset, lead.size, spacing)
     valid = np.unique(init[:, None] + lead[kept][None, :])
     # (valid time, lead) comes from the init time valid - lead
-    at = _positions(init, valid[:, None] - lead[kept][None, :])
+    at = indexing.positions(init, valid[:, None] - lead[kept][None, :])
     table = np.where(at < 0, -1, at * lead.size + kept[None, :])
     new_dims, rename = (TIME, DELTA), {TIME: TIME, DELTA: DELTA}
     new_coords = {TIME: _datetimes(valid), DELTA: _timedeltas(lead[kept])}
   else:
     valid = np.unique(init[:, None] + lead[None, :])
     # (init, valid time) comes from the lead valid - init
-    at = _positions(lead, valid[None, :] - init[:, None])
+    at = indexing.positions(lead, valid[None, :] - init[:, None])
     table = np.where(at < 0, -1,
                      np.arange(init.size, dtype=np.int64)[:, None] * lead.size
                      + at)
     new_dims, rename = (INIT, TIME), {TIME: INIT, DELTA: TIME}
     new_coords = {INIT: _datetimes(init), TIME: _datetimes(valid)}
-  re_ = _Reindex((TIME, DELTA), new_dims, table.astype(np.int64))
+  re_ = indexing.Reindex((TIME, DELTA), new_dims, table.astype(np.int64))
   coords = xl.coords_without(dataset.coords, (TIME, DELTA))
   coords.update(new_coords)
   data, dims, memo = {}, {}, {}
@@ -750,7 +670,7 @@ def probabilistic_climatological_forecasts(
       num_years_to_exclude, seed)
   # [realization, lead, init]: the time of the truth each slab is a copy of
   source = (sampled.astype(np.int64)[:, None, :] + deltas[None, :, None])
-  table = _positions(times, source)
+  table = indexing.positions(times, source)
   if (table < 0).any():
     missing = _datetimes(np.unique(source[table < 0]))
     hint = ''
@@ -761,7 +681,7 @@ def probabilistic_climatological_forecasts(
         f'the truth lacks {missing.size} of the times the samples are taken '
         f'from{hint}: {missing[:8]}{" ..." if missing.size > 8 else ""}')
   new_dims = (realization_name, DELTA, time_dim)
-  re_ = _Reindex((time_dim,), new_dims, table)
+  re_ = indexing.Reindex((time_dim,), new_dims, table)
   coords = xl.coords_without(dataset.coords, (time_dim,))
   coords.update({realization_name: np.arange(n_member), DELTA: _timedeltas(deltas),
                  time_dim: inits})

@@ -1500,6 +1500,61 @@ int wb2_slab_scatter(int in_dtype, int out_dtype, const void* in,
 int wb2_slab_scatter_geometry(int in_dtype, int out_dtype, int wide,
                               int32_t* tile_points, int32_t* max_grid_outer);
 
+/*
+ * K17: dataset slicing as one box gather (scripts/slice_dataset.py: .isel,
+ * .sel and .drop_sel on the last two dims of a variable, together with
+ * whatever was selected on the dims before them).
+ *
+ * wb2_box_gather: the input is [n_slab][n_row_in][n_col_in] elements of
+ * elem_size bytes (4 or 8), the output [n_out_slab][n_row_out][n_col_out], and
+ *   out[s][i][j] = in[src_slab[s] * n_row_in * n_col_in
+ *                     + row[i] * n_col_in + col(j)]
+ * with col(j) = col_list[j] where col_list is given and col0 + j * col_step
+ * (any non-zero step) where it is null.  src_slab is DEV int64 in K13's slab
+ * convention (a contiguous tensor, a time-sliced view, a permuted order and a
+ * gather's base differ in the table alone), row and col_list are DEV int32;
+ * null means identity for src_slab and row.  A bit copy: no holes, no casts,
+ * no atomics, no LDS; NaN payloads and -0.0 survive.  Every table value is
+ * the caller's to check: the kernel cannot.
+ * Column forms (wb2_box_gather_form says which one a call takes):
+ *   WB2_BOX_RUN       col_step == 1; `in` and `out` 16-byte aligned, n_col_in,
+ *                     n_col_out and col0 multiples of the 16-byte lane (4
+ *                     elements of 4 bytes, 2 of 8): 16-byte loads and stores
+ *   WB2_BOX_REVERSED  col_step == -1; aligned likewise with col0 + 1 a
+ *                     multiple of the lane: a 16-byte load from the mirrored
+ *                     address, reversed in registers, a 16-byte store
+ *   WB2_BOX_SCALAR    every other affine run: one element per access,
+ *                     coalesced where |col_step| == 1
+ *   WB2_BOX_LIST      the column list: one element per access
+ * A thread owns adjacent output columns (one 16-byte lane, or one element) of
+ * 4 output rows of one output slab and requests all of them before it stores
+ * any.  A workgroup of 256 threads owns a tile of tile_rows x tile_cols points
+ * of one slab, tile_cols the least power of two of lanes that covers
+ * n_col_out (256 lanes at most); slabs go along the grid, max_grid_outer per
+ * grid row.  Loads and stores stream.  Checked before anything is enqueued:
+ * the element size, negative sizes, a zero step, null `in` / `out`, more
+ * output rows than input rows without a row table, an affine run that leaves
+ * [0, n_col_in) and a grid that does not fit.  Zero sizes of n_out_slab,
+ * n_row_out or n_col_out are a no-op.
+ */
+enum {
+  WB2_BOX_RUN = 0,
+  WB2_BOX_REVERSED = 1,
+  WB2_BOX_SCALAR = 2,
+  WB2_BOX_LIST = 3
+};
+int wb2_box_gather(int elem_size, const void* in, const int64_t* src_slab,
+                   int64_t n_out_slab, int32_t n_row_in, int32_t n_col_in,
+                   const int32_t* row, int32_t n_row_out, int32_t col0,
+                   int32_t col_step, const int32_t* col_list,
+                   int32_t n_col_out, void* out, void* stream);
+int wb2_box_gather_form(int elem_size, const void* in, const void* out,
+                        int32_t n_col_in, int32_t col0, int32_t col_step,
+                        int32_t has_col_list, int32_t n_col_out);
+int wb2_box_gather_geometry(int elem_size, int form, int32_t n_col_out,
+                            int32_t* tile_rows, int32_t* tile_cols,
+                            int32_t* max_grid_outer);
+
 #ifdef __cplusplus
 }
 #endif

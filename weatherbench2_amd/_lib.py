@@ -234,6 +234,12 @@ _SIGNATURES = {
                                 _i32, _vp, _vp]),
     'wb2_slab_scatter_geometry': (_int, [_int, _int, _int, _c.POINTER(_i32),
                                          _c.POINTER(_i32)]),
+    'wb2_box_gather': (_int, [_int, _vp, _vp, _i64, _i32, _i32, _vp, _i32,
+                              _i32, _i32, _vp, _i32, _vp, _vp]),
+    'wb2_box_gather_form': (_int, [_int, _vp, _vp, _i32, _i32, _i32, _i32,
+                                   _i32]),
+    'wb2_box_gather_geometry': (_int, [_int, _int, _i32, _c.POINTER(_i32),
+                                       _c.POINTER(_i32), _c.POINTER(_i32)]),
 }
 
 _lib = None

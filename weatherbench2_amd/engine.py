@@ -6,6 +6,7 @@ every FLOP of the hot path runs in libwb2hip.so.
 from __future__ import annotations
 
 import ctypes
+import math
 import operator
 import os
 import threading
@@ -1640,6 +1641,139 @@ def slab_scatter(x: torch.Tensor, src, dst, n_out_slab: int, *,
           *[_lib.ptr(a) for a in tables],
           int(src.size), n_point, int(dests_per_group), _lib.ptr(out),
           current_stream_ptr(x.device))
+  return out
+
+
+# K17 copies bits: every dtype of 4 or 8 bytes the slicing layer hands it
+BOX_DTYPES = (torch.float32, torch.float64, torch.int32, torch.int64)
+BOX_FORMS = ('run', 'reversed', 'scalar', 'list')  # WB2_BOX_*, in order
+
+
+def box_gather_geometry(dtype: torch.dtype, form: str, n_col_out: int) -> dict:
+  """Extents of the K17 kernel for an output row of `n_col_out` columns in the
+  column form `form` (one of BOX_FORMS): a workgroup owns `tile_rows` x
+  `tile_cols` points of one output slab, `max_grid_outer` slabs per grid
+  row."""
+  return _geometry('wb2_box_gather_geometry',
+                   (_box_elem_size(dtype), BOX_FORMS.index(form),
+                    int(n_col_out)),
+                   [('tile_rows', _I32), ('tile_cols', _I32),
+                    ('max_grid_outer', _I32)])
+
+
+def _box_elem_size(dtype: torch.dtype) -> int:
+  if dtype not in BOX_DTYPES:
+    raise TypeError(f'unsupported dtype {dtype}: the box gather moves '
+                    'float32, float64, int32 and int64')
+  return 4 if dtype in (torch.float32, torch.int32) else 8
+
+
+def _upload_i32(table: np.ndarray, device) -> torch.Tensor:
+  """An int32 table on the device, through the int64 table cache (padded to
+  an even count and reinterpreted; the padding is never read)."""
+  padded = np.zeros(table.size + table.size % 2, dtype=np.int32)
+  padded[:table.size] = table
+  return upload_table(padded.view(np.int64), device).view(torch.int32)
+
+
+def _box_table(values, n: int, what: str) -> t.Optional[np.ndarray]:
+  """`values` (None: identity) as a checked contiguous int32 HOST table of
+  positions in [0, n)."""
+  if values is None:
+    return None
+  table = np.ascontiguousarray(values, dtype=np.int64).reshape(-1)
+  if table.size and (table.min() < 0 or table.max() >= n):
+    raise IndexError(f'{what} out of range [0, {n})')
+  return table.astype(np.int32)
+
+
+def box_gather_form(x: torch.Tensor, out: torch.Tensor, n_col_in: int, cols
+                    ) -> str:
+  """The column form (one of BOX_FORMS) a `box_gather` of `x` into `out` with
+  the columns `cols` takes."""
+  is_list = not isinstance(cols, tuple)
+  col0, step, n = (0, 1, len(cols)) if is_list else cols
+  form = _lib.load().wb2_box_gather_form(
+      _box_elem_size(x.dtype), _lib.ptr(x) or None, _lib.ptr(out) or None,
+      int(n_col_in), int(col0), int(step), int(is_list), int(n))
+  if form < 0:
+    _lib.check(form, 'wb2_box_gather_form')
+  return BOX_FORMS[form]
+
+
+def box_gather(x: torch.Tensor, n_row_in: int, n_col_in: int, *,
+               src_slab=None, n_out_slab: t.Optional[int] = None, rows=None,
+               cols=None, out: t.Optional[torch.Tensor] = None
+               ) -> torch.Tensor:
+  """K17: [n_out_slab, n_row_out, n_col_out] of the dtype of `x` with
+  out[s, i, j] = slab src_slab[s], row rows[i], column cols[j] of the input,
+  bit for bit, from ONE launch.  Input slab k is the `n_row_in * n_col_in`
+  elements that start `k` slabs after the first element of `x`, so `x` is a
+  contiguous tensor or a view whose table addresses intact slabs of its
+  storage (K13's convention).  `src_slab` (None: the first `n_out_slab` slabs
+  in order, by default as many as `x` holds) and `rows` (None: all rows in order) are HOST sequences of
+  positions; `cols` is None (all columns), a HOST sequence, or the affine run
+  as a TUPLE (col0, step, count) with any non-zero step.  Every table is
+  checked here against the input's storage: the kernel trusts them.  `out`, if
+  given, is the contiguous result to fill."""
+  elem = _box_elem_size(x.dtype)
+  n_row_in, n_col_in = int(n_row_in), int(n_col_in)
+  if n_row_in < 0 or n_col_in < 0:
+    raise ValueError('bad sizes')
+  slab = n_row_in * n_col_in
+  # the elements of the storage from the first element of `x` on
+  store = x.untyped_storage()
+  reach = (store.nbytes() - (x.data_ptr() - store.data_ptr())
+           ) // x.element_size() if x.numel() else 0
+  n_in_slab = reach // slab if slab else 0
+  if src_slab is None:
+    n_out_slab = (x.numel() // slab if slab else 0) if n_out_slab is None \
+        else int(n_out_slab)
+    if not 0 <= n_out_slab <= n_in_slab and n_out_slab:
+      raise IndexError(f'{n_out_slab} slabs leave the input\'s {n_in_slab}')
+    slabs = None
+  else:
+    slabs = np.ascontiguousarray(src_slab, dtype=np.int64).reshape(-1)
+    if n_out_slab is not None and int(n_out_slab) != slabs.size:
+      raise ValueError('n_out_slab differs from the length of src_slab')
+    n_out_slab = slabs.size
+    if slabs.size and (slabs.min() < 0 or slabs.max() >= n_in_slab):
+      raise IndexError(f'source slab out of range [0, {n_in_slab})')
+  row = _box_table(rows, n_row_in, 'row')
+  n_row_out = n_row_in if row is None else row.size
+  if cols is None:
+    cols = (0, 1, n_col_in)
+  if isinstance(cols, tuple):
+    col0, step, n_col_out = (int(v) for v in cols)
+    col = None
+    if step == 0:
+      raise ValueError('the column step is zero')
+    if n_col_out < 0:
+      raise ValueError('bad sizes')
+    last = col0 + (n_col_out - 1) * step
+    if n_col_out and not (0 <= col0 < n_col_in and 0 <= last < n_col_in):
+      raise IndexError(f'the column run ({col0}, {step}, {n_col_out}) leaves '
+                       f'[0, {n_col_in})')
+  else:
+    col = _box_table(cols, n_col_in, 'column')
+    col0, step, n_col_out = 0, 1, col.size
+  shape = (n_out_slab, n_row_out, n_col_out)
+  if out is None:
+    out = torch.empty(shape, dtype=x.dtype, device=x.device)
+  elif (out.dtype != x.dtype or out.numel() != math.prod(shape)
+        or not out.is_contiguous() or out.device != x.device):
+    raise ValueError('out must be a contiguous [n_out_slab, n_row_out, '
+                     'n_col_out] tensor of the dtype and on the device of the '
+                     'input')
+  if out.numel() == 0:
+    return out
+  slab_dev = None if slabs is None else upload_table(slabs, x.device)
+  row_dev = None if row is None else _upload_i32(row, x.device)
+  col_dev = None if col is None else _upload_i32(col, x.device)
+  _launch('box_gather', 'wb2_box_gather', elem, _lib.ptr(x),
+          _lib.ptr(slab_dev), n_out_slab, n_row_in, n_col_in,
+          _lib.ptr(row_dev), n_row_out, col0, step, _lib.ptr(col_dev),
+          n_col_out, _lib.ptr(out), current_stream_ptr(x.device))
   return out
 
 

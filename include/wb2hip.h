@@ -1555,6 +1555,87 @@ int wb2_box_gather_geometry(int elem_size, int form, int32_t n_col_out,
                             int32_t* tile_rows, int32_t* tile_cols,
                             int32_t* max_grid_outer);
 
+/*
+ * K18: joint exceedance tables for threshold-event verification (reliability
+ * diagram, ROC, Brier decomposition, contingency table).  The reference stops
+ * at one score per threshold (metrics.py:1524-1891) and has no such table.
+ *
+ * One point under one threshold: k = the number of members with x > thr, obs
+ * = truth > thr (IEEE comparisons: a NaN threshold exceeds nothing, equality
+ * is not exceedance; +-inf are ordinary values); the point is invalid iff the
+ * truth or any member is NaN.
+ *   code = obs * (n_member + 1) + k           for a valid point,
+ *   code = 2 * (n_member + 1)                 for an invalid one,
+ *   n_code = 2 * (n_member + 1) + 1.
+ *
+ * wb2_event_counts:
+ *   cnt[t][o][i][c][code] (DEV int32, every element written) = the number of
+ *   columns j with col_class[j] == c in row i of outer index o whose point has
+ *   `code` under threshold t.
+ * Member m of outer index o is the n_row * n_col elements that start
+ * (ens_slab[o] * n_row * n_col + m * member_stride) after `ens`; the truth
+ * slab starts truth_slab[o] slabs after `truth`, threshold t's slab
+ * thr_slab[t * n_outer + o] slabs after threshold[t] (the convention of
+ * wb2_ens_threshold_partials: a contiguous tensor, a lead-sliced view, a
+ * gather's base and a threshold with fewer dims differ in the tables alone).
+ * The slab tables are DEV int64, null = identity; `threshold` is a HOST array
+ * of n_threshold DEV pointers; col_class is DEV int32[n_col] with values in
+ * [0, n_class).  Every table value is the caller's to check: the kernel
+ * cannot.  Layout (lat, lon): rows are latitudes.
+ * A workgroup of 256 threads owns rows_per_group adjacent rows of one outer
+ * index and walks that contiguous run: 16-byte lanes where `ens`, `truth` and
+ * every threshold pointer are 16-byte aligned and n_col and member_stride are
+ * whole lanes (4 float32, 2 float64), one element per access otherwise.  Per
+ * point it loads the truth and the thresholds of the launch, then the members
+ * four at a time (requested before any is compared), and adds 1 to an LDS
+ * histogram [threshold][row][class][code] with integer LDS atomics; after a
+ * barrier the histogram is stored with plain stores.  Integer adds commute:
+ * two runs are bit-equal.  No global atomics, no float atomics.  Up to 4
+ * thresholds share ONE read of the members and the truth ((n_member + 1 + T)
+ * elements per point); more thresholds, or a histogram above the budget, are
+ * split into launches here.  Outer indices go along the grid, max_grid_outer
+ * per grid row.
+ * Checked before anything is enqueued, in this order: the dtype ("unknown
+ * dtype"), 1 <= n_member <= 128 ("n_member="), 1 <= n_class <= 64
+ * ("n_class="), n_threshold >= 1, the histogram of one row of one threshold
+ * against the budget ("LDS budget"), a negative member_stride, negative
+ * sizes, null pointers ("null pointer") and the grid.  Zero n_outer, n_row or
+ * n_col is a no-op whatever the pointers are.
+ *
+ * wb2_event_counts_geometry: thresholds_per_launch = the most of min(
+ * n_threshold, 4) for which a histogram fits 65536 bytes, rows_per_group = the
+ * most of 4, 2, 1 that fits with them, and
+ *   lds_bytes = thresholds_per_launch * rows_per_group * n_class * n_code * 4.
+ * `wide` (16-byte lanes) changes none of them.
+ *
+ * wb2_event_fold: cnt is [n_cell][n_row][n_class][n_code] (n_cell = thresholds
+ * x outer indices), wrow DEV float64[n_region][n_row] (latitude weight x row
+ * multiplicity), mult DEV int32[n_region][n_class] (column multiplicity of a
+ * class), and
+ *   table[cell][r][code] = sum_i wrow[r][i] *
+ *                          (double)(sum_c mult[r][c] * cnt[cell][i][c][code])
+ * with the inner sum in int64 and the rows in increasing order, one plain
+ * sequential float64 sum (acc = acc + wrow * s, no fused multiply-add) from
+ * 0.0: a fixed order.  One thread per output element: the simple path.  Zero
+ * n_cell or n_region is a no-op.
+ */
+int wb2_event_counts(int dtype, const void* ens, const int64_t* ens_slab,
+                     const void* truth, const int64_t* truth_slab,
+                     const void* const* threshold, const int64_t* thr_slab,
+                     int32_t n_threshold, int32_t n_member,
+                     int64_t member_stride, int64_t n_outer, int32_t n_row,
+                     int32_t n_col, const int32_t* col_class, int32_t n_class,
+                     int32_t* cnt, void* stream);
+int wb2_event_fold(const int32_t* cnt, int64_t n_cell, int32_t n_row,
+                   int32_t n_class, int32_t n_code, const double* wrow,
+                   const int32_t* mult, int32_t n_region, double* table,
+                   void* stream);
+int wb2_event_counts_geometry(int dtype, int32_t n_member, int32_t n_class,
+                              int32_t n_threshold, int wide,
+                              int32_t* rows_per_group,
+                              int32_t* thresholds_per_launch,
+                              int64_t* lds_bytes, int32_t* max_grid_outer);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,140 @@
+"""NumPy restatement of the event tables of weatherbench2_amd/events.py.
+
+Semantics, for one variable, one threshold field `thr` and one outer index, at
+grid point (i, j):
+
+  k    = number of members with x > thr (0..M)
+  o    = 1 if truth > thr else 0
+  IEEE comparisons: a NaN threshold makes both false, equality is not
+  exceedance, +-inf are ordinary values.
+  The point is invalid iff the truth or any member is NaN.
+  code = o (M + 1) + k (valid), 2 (M + 1) (invalid); n_code = 2 (M + 1) + 1.
+
+  N[code] = sum_ij W[i, j] [code_ij == code],  p[o, k] = N[o (M+1) + k] /
+  sum_valid N.  skipna=False: a cell with invalid mass is NaN.  skipna=True:
+  invalid points are left out, a cell without valid mass is NaN.
+
+Three forms, from the simplest up:
+  point_code / counts_loop  a per-point Python loop (integers)
+  dense_table               the dense weighted mean of the one-hot field
+  ordered_table             the product's own order: integer column sums, then
+                            one sequential float64 sum over the rows
+
+Bounds used by the tests (u = 2**-53, the unit roundoff of float64):
+
+* dense_table vs the product: both sum the same n = n_lat * n_lon non-negative
+  terms W_ij [code_ij == code] in different orders.  A sum of n non-negative
+  floats in ANY order has relative error <= (n - 1) u + O(u^2) (Higham,
+  Accuracy and Stability of Numerical Algorithms, section 4.2: the bound
+  gamma_{n-1} holds for every ordering), so two orderings differ by at most
+  2 (n - 1) u relative: rtol = 2 n u.  (The valid mass in the denominator is
+  such a sum too; the test takes the issue's figure for the ratio and the
+  products W = w_lat * multiplicity are exact for the multiplicities 0, 1, 2.)
+
+* brier_score(table) vs the oracle's EnsembleBrierScore: the oracle averages
+  the point scores (k / M - o)^2 with the same weights.  Grouping the points by
+  code is a reordering of that sum (2 n u as above); the point score itself
+  carries the roundings of k / M, the difference and the square (3 u), and the
+  table's final sum over the 2 (M + 1) codes adds at most 2 (M + 1) u.  In
+  all: (2 n + 3 + 2 (M + 1) + ...) u <= 4 (n + M) u = rtol.
+"""
+import numpy as np
+
+
+def n_codes(n_member):
+  return 2 * (n_member + 1) + 1
+
+
+def point_code(members, truth, thr):
+  """The code of one point from Python scalars."""
+  m = len(members)
+  if truth != truth or any(x != x for x in members):
+    return 2 * (m + 1)
+  k = sum(1 for x in members if x > thr)
+  o = 1 if truth > thr else 0
+  return o * (m + 1) + k
+
+
+def counts_loop(ens, truth, thrs, col_class, n_class):
+  """int32 [T, O, R, n_class, n_code] from ens [M, O, R, C], truth [O, R, C]
+  and thrs = T arrays [O, R, C]: one Python step per point."""
+  n_member, n_outer, n_row, n_col = ens.shape
+  out = np.zeros((len(thrs), n_outer, n_row, n_class, n_codes(n_member)),
+                 dtype=np.int32)
+  for t, thr in enumerate(thrs):
+    for o in range(n_outer):
+      for i in range(n_row):
+        for j in range(n_col):
+          code = point_code([ens[m, o, i, j] for m in range(n_member)],
+                            truth[o, i, j], thr[o, i, j])
+          out[t, o, i, col_class[j], code] += 1
+  return out
+
+
+def codes(ens, truth, thr):
+  """Codes [..., R, C] of ens [M, ..., R, C], truth and thr [..., R, C]."""
+  n_member = ens.shape[0]
+  with np.errstate(invalid='ignore'):
+    k = (ens > thr[None]).sum(axis=0)
+    o = (truth > thr).astype(np.int64)
+  bad = np.isnan(truth) | np.isnan(ens).any(axis=0)
+  return np.where(bad, 2 * (n_member + 1), o * (n_member + 1) + k)
+
+
+def _normalize(n, n_member, skipna, sequential):
+  n_valid = 2 * (n_member + 1)
+  if sequential:
+    valid = np.zeros(n.shape[:-1])
+    for c in range(n_valid):
+      valid = valid + n[..., c]
+  else:
+    valid = n[..., :n_valid].sum(-1)
+  with np.errstate(all='ignore'):
+    p = n[..., :n_valid] / valid[..., None]
+  dead = valid == 0
+  if not skipna:
+    dead = dead | (n[..., n_valid] != 0)
+  p[dead] = np.nan
+  return p.reshape(p.shape[:-1] + (2, n_member + 1))
+
+
+def dense_table(ens, truth, thr, weights, skipna):
+  """p [..., 2, M + 1]: the weighted mean of the one-hot code field with the
+  dense weights [R, C]."""
+  n_member = ens.shape[0]
+  code = codes(ens, truth, thr)
+  onehot = (code[..., None] == np.arange(n_codes(n_member))).astype(np.float64)
+  n = np.einsum('...ijc,ij->...c', onehot, np.asarray(weights, np.float64))
+  return _normalize(n, n_member, skipna, sequential=False)
+
+
+def ordered_table(ens, truth, thr, wrow, lon_mult, skipna):
+  """The same table in the product's order: per row the integer sum over the
+  columns of lon_mult[j] [code == c], then acc = acc + wrow[i] * float(s) over
+  the rows in increasing order, the valid mass over the codes in increasing
+  order."""
+  n_member = ens.shape[0]
+  n_code = n_codes(n_member)
+  code = codes(ens, truth, thr)
+  acc = np.zeros(code.shape[:-2] + (n_code,))
+  mult = np.asarray(lon_mult, dtype=np.int64)
+  for i in range(code.shape[-2]):
+    hit = code[..., i, :, None] == np.arange(n_code)
+    s = (hit * mult[:, None]).sum(axis=-2)
+    acc = acc + wrow[i] * s.astype(np.float64)
+  return _normalize(acc, n_member, skipna, sequential=True)
+
+
+def fold(cnt, wrow, mult):
+  """wb2_event_fold restated with Python loops over regions and rows."""
+  n_thr, n_outer, n_row, n_class, n_code = cnt.shape
+  out = np.zeros((n_thr, n_outer, len(wrow), n_code))
+  for r in range(len(wrow)):
+    acc = np.zeros((n_thr, n_outer, n_code))
+    for i in range(n_row):
+      s = np.zeros((n_thr, n_outer, n_code), dtype=np.int64)
+      for c in range(n_class):
+        s += int(mult[r][c]) * cnt[:, :, i, c, :].astype(np.int64)
+      acc = acc + float(wrow[r][i]) * s.astype(np.float64)
+    out[:, :, r] = acc
+  return out

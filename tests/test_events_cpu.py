@@ -1,0 +1,503 @@
+"""Event tables without a device: the host path of weatherbench2_amd/events.py
+against the restatement (tests/events_np.py) and the oracle, the score
+functions, the C ABI's refusals and the column classes."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from oracle import metrics_np as om
+from oracle.named import NA
+from tests import events_cases as cases
+from tests import events_np
+from tests import helpers
+from tests.test_cabi_cpu import _oracle_region_weights
+from weatherbench2_amd import events
+from weatherbench2_amd import metrics as gm
+from weatherbench2_amd import regions as greg
+from weatherbench2_amd import xarray_lite as xl
+
+g = helpers.to_gpu_dataset
+NAME = cases.NAME
+U = 2.0 ** -53
+
+
+# ---------------------------------------------------------------------------
+# 1. counts vs a per-point loop
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize('dtype', [np.float32, np.float64])
+@pytest.mark.parametrize('n_member', [1, 2, 7])
+def test_host_counts_equal_a_per_point_loop(n_member, dtype):
+  n_outer, n_row, n_col, n_class = 2, 5, 7, 3
+  ens, truth, thrs = cases.edge_case(n_member, 2, n_outer, n_row, n_col, dtype)
+  cls = cases.classes(n_col, n_class)
+  got = events.host_counts(ens, n_outer * n_row * n_col, n_member, None, truth,
+                           None, thrs, None, n_outer, n_row, n_col, cls,
+                           n_class)
+  want = events_np.counts_loop(ens, truth, thrs, cls, n_class)
+  assert got.dtype == np.int32 and got.shape == want.shape
+  np.testing.assert_array_equal(got, want)
+  # every special kind is there: invalid points and both observed halves
+  n_code = events.n_codes(n_member)
+  assert got[..., n_code - 1].sum() > 0
+  assert got[..., :n_member + 1].sum() > 0 < got[..., n_member + 1:-1].sum()
+  # conservation: the codes of a (row, class) sum to the class's columns
+  np.testing.assert_array_equal(
+      got.sum(-1), np.broadcast_to(np.bincount(cls, minlength=n_class),
+                                   got.shape[:-1]))
+
+
+def test_host_counts_read_through_slab_tables():
+  n_member, n_outer, n_row, n_col = 3, 4, 2, 5
+  ens, truth, thrs = cases.edge_case(n_member, 1, n_outer, n_row, n_col,
+                                     np.float64, seed=3)
+  cls = cases.classes(n_col, 2)
+  want = events_np.counts_loop(ens, truth, thrs, cls, 2)
+  # members innermost, the outer indices reversed; a threshold of one slab
+  moved = np.ascontiguousarray(np.moveaxis(ens[:, ::-1], 0, 1))
+  table = (n_outer - 1 - np.arange(n_outer)) * n_member
+  got = events.host_counts(moved, n_row * n_col, n_member, table, truth, None,
+                           thrs, [np.arange(n_outer)], n_outer, n_row, n_col,
+                           cls, 2)
+  np.testing.assert_array_equal(got, want)
+  one = events.host_counts(ens, n_outer * n_row * n_col, n_member, None, truth,
+                           None, [thrs[0][2]], [np.zeros(n_outer, np.int64)],
+                           n_outer, n_row, n_col, cls, 2)
+  same = events_np.counts_loop(ens, truth, [np.broadcast_to(
+      thrs[0][2], thrs[0].shape)], cls, 2)
+  np.testing.assert_array_equal(one, same)
+
+
+# ---------------------------------------------------------------------------
+# 2. the table vs an independent dense restatement; 3. vs the oracle's Brier
+# ---------------------------------------------------------------------------
+def _tables(ensemble_size, skipna, truth_only=False):
+  truth, forecast, clim = cases.random_case(
+      ensemble_size, nan_frac=0.05 if skipna else 0.0, truth_only=truth_only)
+  oregions = cases.oracle_regions()
+  metric = events.EventTable(thresholds=cases.product_thresholds(clim))
+  got = metric.compute_chunk(g(forecast), g(truth), skipna=skipna,
+                             regions=cases.product_regions(oregions))
+  return truth, forecast, clim, oregions, got
+
+
+@pytest.mark.parametrize('skipna', [False, True])
+@pytest.mark.parametrize('ensemble_size', [None, 2, 7])
+def test_table_equals_the_dense_restatement(ensemble_size, skipna):
+  truth, forecast, clim, oregions, got = _tables(ensemble_size, skipna)
+  n_member = ensemble_size or 1
+  lat, lon = forecast.coord('latitude'), forecast.coord('longitude')
+  da = got[NAME]
+  outer = None
+  for q, th in enumerate(cases.oracle_thresholds(clim)):
+    outer, ens, tru, thr = cases.dense_operands(
+        forecast[NAME], truth[NAME], th.compute(truth)[NAME])
+    for r, (name, region) in enumerate(oregions.items()):
+      weights = _oracle_region_weights(region, lat, lon)
+      want = events_np.dense_table(ens, tru, thr, weights, skipna)
+      np.testing.assert_allclose(
+          da.values[r, q], want, rtol=2 * len(lat) * len(lon) * U, atol=0,
+          equal_nan=True, err_msg=f'{name} q={q}')
+      # bit-equal to the restatement's own ordered form (the row weights and
+      # column multiplicities of the product, checked against the dense ones)
+      spec = greg.decompose_region(helpers.to_gpu_region(region), lat, lon)
+      wrow = gm.plan_lib.get_lat_weights(lat) * spec.lat_mult
+      np.testing.assert_allclose(wrow[:, None] * spec.lon_mult[None, :],
+                                 weights, rtol=1e-15, atol=0)
+      same = events_np.ordered_table(ens, tru, thr, wrow, spec.lon_mult,
+                                     skipna)
+      np.testing.assert_array_equal(da.values[r, q], same,
+                                    err_msg=f'{name} q={q}')
+  assert da.dims == ('region', 'quantile') + outer + (
+      'observed', 'members_exceeding')
+  assert da.dtype == np.float64
+  np.testing.assert_array_equal(got['quantile'].values, cases.QUANTILES)
+  np.testing.assert_array_equal(got['observed'].values, [0, 1])
+  np.testing.assert_array_equal(got['members_exceeding'].values,
+                                np.arange(n_member + 1))
+  assert list(got['region'].values) == list(oregions)
+  assert got.attrs == {'threshold_method': 'GaussianQuantileThreshold',
+                       'ensemble_size': n_member}
+  values = da.values
+  if skipna:
+    assert np.isfinite(values).any()
+  else:
+    assert np.isfinite(values).all()
+    np.testing.assert_allclose(values.sum((-2, -1)), 1.0, rtol=1e-13)
+
+
+def test_nan_without_skipna_voids_the_cell_and_single_region_matches():
+  truth, forecast, clim = cases.random_case(2, nan_frac=0.05)
+  metric = events.EventTable(thresholds=cases.product_thresholds(clim))
+  void = metric.compute_chunk(g(forecast), g(truth), skipna=False)
+  assert np.isnan(void[NAME].values).all()  # 5 % NaN: every cell has some
+  regions = cases.product_regions(cases.oracle_regions())
+  every = metric.compute_chunk(g(forecast), g(truth), skipna=True,
+                               regions=regions)
+  for r, (name, region) in enumerate(regions.items()):
+    one = metric.compute_chunk(g(forecast), g(truth), region=region,
+                               skipna=True)
+    assert one[NAME].dims == every[NAME].dims[1:]
+    np.testing.assert_array_equal(one[NAME].values, every[NAME].values[r],
+                                  err_msg=name)
+  # the entry points every Metric has
+  fan = metric.compute_chunk_regions(g(forecast), g(truth), regions, True)
+  cases.assert_same_dataset(fan, every)
+  mean = metric.compute_regions(g(forecast), g(truth), regions, True)
+  assert 'time' not in mean[NAME].dims
+  np.testing.assert_array_equal(
+      mean[NAME].values,
+      np.nanmean(every[NAME].values, every[NAME].dims.index('time')))
+  assert mean.attrs['ensemble_size'] == 2
+
+
+@pytest.mark.parametrize('skipna', [False, True])
+@pytest.mark.parametrize('ensemble_size', [1, 2, 7, 33])
+def test_brier_of_the_table_equals_the_oracles_brier_score(ensemble_size,
+                                                           skipna):
+  # skipna=True: NaNs in the truth only, where the oracle's skipped point (a
+  # NaN score) and the table's invalid point are the same points
+  truth, forecast, clim, oregions, got = _tables(ensemble_size, skipna,
+                                                 truth_only=True)
+  brier = events.brier_score(got)[NAME]
+  n_point = forecast.sizes['latitude'] * forecast.sizes['longitude']
+  metric = om.EnsembleBrierScore(thresholds=cases.oracle_thresholds(clim))
+  for r, (name, region) in enumerate(oregions.items()):
+    want = metric.compute_chunk(forecast, truth, region=region,
+                                skipna=skipna)[NAME]
+    assert brier.dims[1:] == want.dims, name
+    np.testing.assert_allclose(
+        brier.values[r], want.data, rtol=4 * (n_point + ensemble_size) * U,
+        atol=0, equal_nan=True, err_msg=name)
+
+
+# ---------------------------------------------------------------------------
+# 4. score functions
+# ---------------------------------------------------------------------------
+def _table(p, dims=()):
+  p = np.asarray(p, dtype=np.float64)
+  return xl.DataArray(p, tuple(dims) + ('observed', 'members_exceeding'),
+                      {'observed': np.arange(2),
+                       'members_exceeding': np.arange(p.shape[-1])})
+
+
+def test_scores_of_a_perfect_forecast():
+  # 3 members: all exceed when the event happens (30 %), none otherwise
+  table = _table([[0.7, 0, 0, 0], [0, 0, 0, 0.3]])
+  for m in (1, 2, 3):
+    s = events.categorical_scores(table, min_members=m)
+    for k, want in (('pod', 1), ('csi', 1), ('ets', 1), ('far', 0),
+                    ('pofd', 0), ('frequency_bias', 1)):
+      assert s[k].values == want, (k, m)
+  curve = events.roc(table)
+  assert curve['auc'].values == 1.0
+  assert events.brier_score(table).values == 0.0
+  parts = events.brier_decomposition(table)
+  assert parts['reliability'].values == 0.0
+  np.testing.assert_allclose(parts['resolution'].values, 0.21, rtol=1e-15)
+  np.testing.assert_allclose(parts['uncertainty'].values, 0.21, rtol=1e-15)
+
+
+def test_scores_of_a_constant_no_forecast():
+  table = _table([[0.6, 0, 0], [0.4, 0, 0]])
+  s = events.categorical_scores(table)
+  assert s['pod'].values == 0.0 and s['pofd'].values == 0.0
+  assert np.isnan(s['far'].values)  # 0 / 0: the event is never forecast
+  assert s['csi'].values == 0.0 and s['frequency_bias'].values == 0.0
+  curve = events.roc(table)
+  np.testing.assert_array_equal(curve['pod'].values, [0, 0, 0, 1])
+  np.testing.assert_array_equal(curve['pofd'].values, [0, 0, 0, 1])
+  assert curve['auc'].values == 0.5
+  np.testing.assert_allclose(events.brier_score(table).values, 0.4)
+  rel = events.reliability(table)
+  np.testing.assert_array_equal(rel['forecast_frequency'].values, [1, 0, 0])
+  np.testing.assert_array_equal(rel['observed_frequency'].values,
+                                [0.4, np.nan, np.nan])
+  np.testing.assert_array_equal(rel['forecast_probability'].values,
+                                [0, 0.5, 1])
+
+
+def test_scores_of_a_table_worked_by_hand():
+  # M = 2.  p[0] = (0.40, 0.15, 0.05), p[1] = (0.05, 0.15, 0.20).
+  # min_members = 1: a = 0.15 + 0.20 = 0.35, b = 0.15 + 0.05 = 0.20,
+  #   c = 0.05, d = 0.40.  pod = 0.35 / 0.40 = 0.875, far = 0.20 / 0.55,
+  #   pofd = 0.20 / 0.60 = 1/3, csi = 0.35 / 0.60, bias = 0.55 / 0.40 = 1.375,
+  #   a_r = 0.55 * 0.40 = 0.22, ets = 0.13 / 0.38.
+  # min_members = 2: a = 0.20, b = 0.05, c = 0.20, d = 0.55.
+  # y = (0, 1/2, 1); Brier = 0.15 / 4 + 0.05 + 0.05 + 0.15 / 4 = 0.175.
+  # f = (0.45, 0.30, 0.25), o_k = (1/9, 1/2, 4/5), o = 0.40.
+  #   reliability = 0.45 / 81 + 0 + 0.25 * 0.04 = 0.0155555...
+  #   resolution = 0.45 (1/9 - 0.4)^2 + 0.30 * 0.01 + 0.25 * 0.16
+  #              = 0.0375555... + 0.003 + 0.04 = 0.0805555...
+  #   uncertainty = 0.24;  0.0155555 - 0.0805555 + 0.24 = 0.175.
+  # ROC from (0, 0): (0.05/0.6, 0.2/0.4), (0.2/0.6, 0.35/0.4), (1, 1):
+  #   auc = 1/2 [1/12 * 1/2 + 1/4 * (1/2 + 7/8) + 2/3 * (7/8 + 1)]
+  #       = 1/2 [1/24 + 11/32 + 5/4] = 157/192.
+  table = _table([[0.40, 0.15, 0.05], [0.05, 0.15, 0.20]])
+  c = events.contingency(table)
+  for k, want in (('hits', 0.35), ('false_alarms', 0.20), ('misses', 0.05),
+                  ('correct_negatives', 0.40)):
+    np.testing.assert_allclose(c[k].values, want, rtol=1e-15)
+  c2 = events.contingency(table, min_members=2)
+  for k, want in (('hits', 0.20), ('false_alarms', 0.05), ('misses', 0.20),
+                  ('correct_negatives', 0.55)):
+    np.testing.assert_allclose(c2[k].values, want, rtol=1e-15)
+  s = events.categorical_scores(table)
+  for k, want in (('pod', 0.875), ('far', 0.20 / 0.55), ('pofd', 1 / 3),
+                  ('csi', 0.35 / 0.60), ('frequency_bias', 1.375),
+                  ('ets', 0.13 / 0.38)):
+    np.testing.assert_allclose(s[k].values, want, rtol=1e-14, err_msg=k)
+  np.testing.assert_allclose(events.brier_score(table).values, 0.175,
+                             rtol=1e-15)
+  parts = events.brier_decomposition(table)
+  np.testing.assert_allclose(parts['reliability'].values, 0.45 / 81 + 0.01,
+                             rtol=1e-14)
+  np.testing.assert_allclose(parts['resolution'].values,
+                             0.45 * (1 / 9 - 0.4) ** 2 + 0.043, rtol=1e-14)
+  np.testing.assert_allclose(parts['uncertainty'].values, 0.24, rtol=1e-15)
+  curve = events.roc(table)
+  np.testing.assert_allclose(curve['pofd'].values, [0, 1 / 12, 1 / 3, 1],
+                             rtol=1e-14)
+  np.testing.assert_allclose(curve['pod'].values, [0, 0.5, 0.875, 1],
+                             rtol=1e-14)
+  np.testing.assert_array_equal(curve['min_members'].values, [3, 2, 1, 0])
+  np.testing.assert_allclose(curve['auc'].values, 157 / 192, rtol=1e-14)
+
+
+@pytest.mark.parametrize('n_member', [1, 4, 50])
+def test_score_identities_on_random_tables(n_member):
+  rs = np.random.RandomState(n_member)
+  p = rs.rand(6, 5, 2, n_member + 1)
+  p[0, 0, :, 1] = 0.0  # an unused probability bin: its terms are dropped
+  p /= p.sum((-2, -1), keepdims=True)
+  table = xl.Dataset({'x': _table(p, ('a', 'b'))})
+  parts = events.brier_decomposition(table)['x']
+  np.testing.assert_allclose(
+      events.brier_score(table)['x'].values,
+      parts['reliability'].values - parts['resolution'].values
+      + parts['uncertainty'].values, rtol=0, atol=1e-15)
+  for m in range(n_member + 2):
+    c = events.contingency(table, min_members=m)['x']
+    np.testing.assert_allclose(
+        c['hits'].values + c['false_alarms'].values + c['misses'].values
+        + c['correct_negatives'].values, 1.0, rtol=0, atol=1e-15)
+  curve = events.roc(table)['x']
+  assert curve['pod'].dims == ('a', 'b', 'min_members')
+  for k in ('pod', 'pofd'):
+    v = curve[k].values
+    np.testing.assert_array_equal(v[..., 0], 0.0)
+    np.testing.assert_allclose(v[..., -1], 1.0, rtol=0, atol=1e-15)
+    assert (np.diff(v, axis=-1) >= 0).all()
+  assert ((curve['auc'].values > 0) & (curve['auc'].values < 1)).all()
+  # a NaN table (an empty region) gives NaN scores, not zeros
+  p[1, 2] = np.nan
+  nan_table = _table(p, ('a', 'b'))
+  assert np.isnan(events.brier_score(nan_table).values[1, 2])
+  parts = events.brier_decomposition(nan_table)
+  assert all(np.isnan(parts[k].values[1, 2]) for k in parts.data_vars)
+  with pytest.raises(ValueError, match='not an event table'):
+    events.brier_score(xl.DataArray(p, ('a', 'b', 'c', 'd')))
+
+
+# ---------------------------------------------------------------------------
+# 5. the C ABI without a device
+# ---------------------------------------------------------------------------
+@pytest.fixture(scope='module')
+def lib():
+  from weatherbench2_amd import build
+  build.build(verbose=False)
+  from weatherbench2_amd import _lib
+  return _lib
+
+
+def _counts(h, *, dtype=0, ens=1, truth=1, thr=(1,), n_thr=1, n_member=5,
+            n_outer=2, n_row=3, n_col=4, cls=1, n_class=2, cnt=1,
+            member_stride=12):
+  """wb2_event_counts with dummy non-null addresses: every call here must be
+  refused (or be a no-op) before anything is enqueued."""
+  thr_arr = None if thr is None else (ctypes.c_void_p * len(thr))(
+      *[t or None for t in thr])
+  p = lambda v: 4096 * v or None
+  return h.wb2_event_counts(dtype, p(ens), None, p(truth), None, thr_arr,
+                            None, n_thr, n_member, member_stride, n_outer,
+                            n_row, n_col, p(cls), n_class, p(cnt), None)
+
+
+def test_event_counts_refuses_before_any_launch(lib):
+  h = lib.load()
+  err = lambda: h.wb2_last_error().decode()
+  for kwargs, words in (
+      (dict(dtype=7), 'unknown dtype'),
+      (dict(n_member=0), 'n_member=0'),
+      (dict(n_member=129), 'n_member=129'),
+      (dict(n_class=65), 'n_class=65'),
+      (dict(n_class=0), 'n_class=0'),
+      (dict(n_thr=0), 'n_threshold=0'),
+      (dict(n_member=128, n_class=64), 'LDS budget'),
+      (dict(member_stride=-1), 'member_stride'),
+      (dict(n_outer=-1), 'negative'),
+      (dict(n_row=-1), 'negative'),
+      (dict(ens=0), 'null pointer'),
+      (dict(truth=0), 'null pointer'),
+      (dict(thr=None), 'null pointer'),
+      (dict(thr=(0,)), 'null pointer'),
+      (dict(cls=0), 'null pointer'),
+      (dict(cnt=0), 'null pointer'),
+  ):
+    assert _counts(h, **kwargs) < 0, kwargs
+    assert words in err(), (kwargs, err())
+  # no slabs, no rows, no columns: a legal no-op whatever the pointers are
+  for kwargs in (dict(n_outer=0), dict(n_row=0), dict(n_col=0)):
+    assert _counts(h, ens=0, truth=0, thr=None, cls=0, cnt=0, **kwargs) == 0
+  # ... but the shape is still checked
+  assert _counts(h, n_outer=0, dtype=7) < 0
+
+
+def test_event_fold_refuses_before_any_launch(lib):
+  h = lib.load()
+  fold = lambda cnt=4096, n_cell=2, n_row=3, n_class=2, n_code=5, wrow=4096, \
+      mult=4096, n_region=2, table=4096: h.wb2_event_fold(
+          cnt or None, n_cell, n_row, n_class, n_code, wrow or None,
+          mult or None, n_region, table or None, None)
+  for kwargs, words in ((dict(cnt=0), 'null pointer'),
+                        (dict(wrow=0), 'null pointer'),
+                        (dict(mult=0), 'null pointer'),
+                        (dict(table=0), 'null pointer'),
+                        (dict(n_class=0), 'bad sizes'),
+                        (dict(n_row=-1), 'bad sizes'),
+                        (dict(n_cell=-1), 'negative')):
+    assert fold(**kwargs) < 0, kwargs
+    assert words in h.wb2_last_error().decode(), kwargs
+  assert fold(n_cell=0, cnt=0, wrow=0, mult=0, table=0) == 0
+  assert fold(n_region=0, cnt=0, wrow=0, mult=0, table=0) == 0
+
+
+def test_event_counts_geometry_is_consistent(lib):
+  from weatherbench2_amd import engine
+  import torch
+  for dtype in (torch.float32, torch.float64):
+    for n_member in (1, 2, 7, 50, 128):
+      for n_class in (1, 4, 16, 32, 64):
+        for n_thr in (1, 3, 4, 5):
+          row_bytes = 4 * n_class * (2 * (n_member + 1) + 1)
+          if row_bytes > 65536:
+            with pytest.raises(lib.Wb2HipError, match='LDS budget'):
+              engine.event_counts_geometry(dtype, n_member, n_class, n_thr)
+            continue
+          geo = engine.event_counts_geometry(dtype, n_member, n_class, n_thr)
+          assert geo == engine.event_counts_geometry(dtype, n_member, n_class,
+                                                     n_thr, wide=True)
+          nt, rows = geo['thresholds_per_launch'], geo['rows_per_group']
+          assert 1 <= nt <= min(n_thr, 4) and rows in (1, 2, 4)
+          # the formula of include/wb2hip.h
+          assert geo['lds_bytes'] == nt * rows * n_class * (
+              2 * (n_member + 1) + 1) * 4 <= 65536
+          assert geo['max_grid_outer'] == 32768
+          # greedy: the thresholds first, then the rows
+          if nt < min(n_thr, 4):
+            assert (nt + 1) * row_bytes > 65536
+          if rows < 4:
+            assert nt * 2 * rows * row_bytes > 65536
+  assert engine.event_counts_geometry(torch.float32, 50, 13, 3) == {
+      'rows_per_group': 4, 'thresholds_per_launch': 3,
+      'lds_bytes': 3 * 4 * 13 * 103 * 4, 'max_grid_outer': 32768}
+  with pytest.raises(TypeError):
+    engine.event_counts_geometry(torch.float16, 5, 1, 1)
+  h = lib.load()
+  assert h.wb2_event_counts_geometry(0, 5, 1, 1, 0, None, None, None,
+                                     None) < 0
+  assert b'null pointer' in h.wb2_last_error()
+
+
+# ---------------------------------------------------------------------------
+# 6. column classes
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize('res', [10.0, 5.625])
+def test_column_classes_reproduce_every_regions_multiplicities(res):
+  lat = np.linspace(-90, 90, round(180 / res) + 1)
+  lon = np.linspace(0, 360, round(360 / res), endpoint=False)
+  oregions = cases.oracle_regions()
+  oregions['none'] = None
+  regions = cases.product_regions(oregions)
+  col_class, mult, wrow = events.column_classes(regions, lat, lon)
+  assert col_class.dtype == np.int32 and mult.dtype == np.int32
+  assert wrow.dtype == np.float64
+  n_class = mult.shape[1]
+  assert mult.shape == (len(regions), n_class) and n_class <= 64
+  assert sorted(set(col_class.tolist())) == list(range(n_class))
+  # classes are distinct: no two have the same column of multiplicities
+  assert len({tuple(c) for c in mult.T.tolist()}) == n_class
+  for r, (name, region) in enumerate(regions.items()):
+    spec = greg.decompose_region(region, lat, lon)
+    np.testing.assert_array_equal(mult[r][col_class], spec.lon_mult,
+                                  err_msg=name)
+    dense = wrow[r][:, None] * mult[r][col_class][None, :]
+    want = _oracle_region_weights(oregions[name], lat, lon)
+    np.testing.assert_allclose(dense, want, rtol=1e-15, atol=0, err_msg=name)
+  # europe wraps around the date line: its class is not one run of columns
+  europe = mult[list(regions).index('europe')][col_class] > 0
+  assert europe[0] and europe[-1] and not europe.all()
+  assert mult[list(regions).index('overlap')].max() == 1
+  # ... and the rows both of its latitude slices hold count twice
+  twice = np.abs(lat) <= 10
+  np.testing.assert_array_equal(
+      wrow[list(regions).index('overlap')], wrow[-1] * np.where(twice, 2, 1))
+
+
+def test_a_land_region_is_refused_by_name():
+  lat = np.linspace(-90, 90, 19)
+  lon = np.linspace(0, 360, 36, endpoint=False)
+  lsm = xl.DataArray(np.ones((19, 36)), ('latitude', 'longitude'),
+                     {'latitude': lat, 'longitude': lon})
+  regions = {'global': None, 'the-land': greg.LandRegion(lsm)}
+  with pytest.raises(ValueError, match='the-land.*LandRegion.*2-D'):
+    events.column_classes(regions, lat, lon)
+  truth, forecast, clim = cases.random_case(2)
+  metric = events.EventTable(thresholds=cases.product_thresholds(clim))
+  with pytest.raises(ValueError, match='2-D weight field'):
+    metric.compute_chunk(g(forecast), g(truth), region=greg.LandRegion(
+        xl.DataArray(np.ones((19, 36)), ('latitude', 'longitude'),
+                     {'latitude': forecast.coord('latitude'),
+                      'longitude': forecast.coord('longitude')})))
+
+
+# ---------------------------------------------------------------------------
+# 7. class declarations
+# ---------------------------------------------------------------------------
+def test_event_table_is_a_metric_of_its_own_module():
+  assert issubclass(events.EventTable, gm.ThresholdMetric)
+  assert issubclass(events.EventTable, gm.Metric)
+  assert events.EventTable._fused_regions is True
+  assert events.EventTable._reads_slabs_in_place is False
+  metric = events.EventTable(thresholds=[1])
+  assert metric.ensemble_dim == 'realization'
+  assert events.EventTable(thresholds=[1], ensemble_dim=None).ensemble_dim \
+      is None
+  assert not hasattr(gm, 'EventTable')
+  with pytest.raises(ValueError, match='at least one threshold'):
+    truth, forecast, _ = cases.random_case(2)
+    events.EventTable().compute_chunk(g(forecast), g(truth))
+
+
+def test_a_deterministic_forecast_is_the_one_member_table():
+  truth, forecast, clim = cases.random_case(None)
+  ths = cases.product_thresholds(clim)
+  det = events.EventTable(thresholds=ths).compute_chunk(g(forecast), g(truth))
+  assert det[NAME].shape[-2:] == (2, 2) and det.attrs['ensemble_size'] == 1
+  none = events.EventTable(thresholds=ths, ensemble_dim=None).compute_chunk(
+      g(forecast), g(truth))
+  cases.assert_same_dataset(none, det)
+  # the same field as a one-member ensemble
+  one = forecast.expand_dims('realization', coord=np.arange(1))
+  ens = events.EventTable(thresholds=ths).compute_chunk(g(one), g(truth))
+  np.testing.assert_array_equal(ens[NAME].values, det[NAME].values)
+  # the contingency table of the deterministic forecast, by hand
+  q = 0
+  thr = cases.oracle_thresholds(clim)[q].compute(truth)[NAME]
+  _, x, tru, thr = cases.dense_operands(forecast[NAME], truth[NAME], thr)
+  w = np.broadcast_to(om.get_lat_weights(forecast.coord('latitude')
+                                         ).data[:, None], x.shape[-2:])
+  hits = ((x[0] > thr) & (tru > thr)) * w
+  c = events.contingency(det)[NAME]
+  np.testing.assert_allclose(c['hits'].values[q],
+                             hits.sum((-2, -1)) / w.sum(), rtol=1e-12)

@@ -240,6 +240,14 @@ _SIGNATURES = {
                                    _i32]),
     'wb2_box_gather_geometry': (_int, [_int, _int, _i32, _c.POINTER(_i32),
                                        _c.POINTER(_i32), _c.POINTER(_i32)]),
+    'wb2_event_counts': (_int, [
+        _int, _vp, _vp, _vp, _vp, _c.POINTER(_vp), _vp, _i32, _i32, _i64,
+        _i64, _i32, _i32, _vp, _i32, _vp, _vp]),
+    'wb2_event_fold': (_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _i32,
+                              _vp, _vp]),
+    'wb2_event_counts_geometry': (_int, [
+        _int, _i32, _i32, _i32, _int, _c.POINTER(_i32), _c.POINTER(_i32),
+        _c.POINTER(_i64), _c.POINTER(_i32)]),
 }
 
 _lib = None

@@ -1777,6 +1777,134 @@ def box_gather(x: torch.Tensor, n_row_in: int, n_col_in: int, *,
   return out
 
 
+def event_counts_geometry(dtype: torch.dtype, n_member: int, n_class: int,
+                          n_threshold: int, wide: bool = False) -> dict:
+  """Extents of the K18 counting kernel: a workgroup owns `rows_per_group`
+  rows of one outer index, `thresholds_per_launch` thresholds share one read of
+  the members, the histogram takes `lds_bytes` of LDS, `max_grid_outer` outer
+  indices per grid row."""
+  return _geometry('wb2_event_counts_geometry',
+                   (dtype_code(dtype), int(n_member), int(n_class),
+                    int(n_threshold), int(wide)),
+                   [('rows_per_group', _I32), ('thresholds_per_launch', _I32),
+                    ('lds_bytes', ctypes.c_int64), ('max_grid_outer', _I32)])
+
+
+def _reach(x: torch.Tensor) -> int:
+  """Elements of the storage of `x` from its first element on."""
+  store = x.untyped_storage()
+  return (store.nbytes() - (x.data_ptr() - store.data_ptr())
+          ) // x.element_size() if x.numel() else 0
+
+
+def _event_slabs(table, n_outer: int, x: torch.Tensor, slab: int, extra: int,
+                 what: str) -> t.Optional[np.ndarray]:
+  """The HOST slab table `table` (None: identity) of `n_outer` entries,
+  checked against the storage of `x`: every slab, and `extra` elements past
+  its start (the further members), lie inside."""
+  if table is None:
+    lo, hi = 0, n_outer - 1
+  else:
+    table = np.ascontiguousarray(table, dtype=np.int64).reshape(-1)
+    if table.size != n_outer:
+      raise ValueError(f'the {what} slab table must hold {n_outer} entries')
+    lo, hi = (int(table.min()), int(table.max())) if n_outer else (0, -1)
+  if n_outer and (lo < 0 or hi * slab + extra + slab > _reach(x)):
+    raise IndexError(f'the {what} slabs leave the storage of the operand')
+  return table
+
+
+def event_counts(ens: torch.Tensor, member_stride: int, n_member: int,
+                 ens_slab, truth: torch.Tensor, truth_slab,
+                 thresholds: t.Sequence[torch.Tensor], thr_slabs, n_outer: int,
+                 n_row: int, n_col: int, col_class, n_class: int
+                 ) -> torch.Tensor:
+  """K18: int32 [n_threshold, n_outer, n_row, n_class, n_code] counts of the
+  points of every (row, column class) by code = observed * (M + 1) + members
+  exceeding (2 (M + 1): truth or a member is NaN), n_code = 2 (M + 1) + 1.
+  Member m of outer index o is the slab of `n_row * n_col` elements that starts
+  `ens_slab[o]` slabs and `m * member_stride` ELEMENTS after the first element
+  of `ens`; `truth_slab` and `thr_slabs[t]` address the truth and threshold t
+  likewise.  The slab tables and `col_class` (class of every column, in
+  [0, n_class)) are HOST sequences, None = identity; all of them are checked
+  here against the operands' storage: the kernel trusts them.  Up to 4
+  thresholds share one read of the members; the C side splits the rest."""
+  thresholds = list(thresholds)
+  if not thresholds:
+    raise ValueError('no thresholds')
+  _require_float(ens, truth, *thresholds)
+  dev = ens.device
+  # (`ens` may be a view whose whole slabs its table addresses)
+  _check_contiguous(dev, 'the device of the members', truth, *thresholds,
+                    view=ens)
+  n_member, n_outer, n_row, n_col, n_class, member_stride = (
+      int(v) for v in (n_member, n_outer, n_row, n_col, n_class,
+                       member_stride))
+  if min(n_outer, n_row, n_col) < 0 or member_stride < 0:
+    raise ValueError('bad sizes')
+  thr_slabs = list(thr_slabs) if thr_slabs is not None else [None] * len(
+      thresholds)
+  if len(thr_slabs) != len(thresholds):
+    raise ValueError('one slab table (or None) per threshold')
+  slab = n_row * n_col
+  n_code = 2 * (n_member + 1) + 1
+  out = torch.empty((len(thresholds), n_outer, n_row, n_class, n_code),
+                    dtype=torch.int32, device=dev)
+  cls = np.ascontiguousarray(col_class, dtype=np.int64).reshape(-1)
+  if cls.size != n_col or (n_col and (cls.min() < 0 or cls.max() >= n_class)):
+    raise IndexError(f'col_class must hold {n_col} classes in [0, {n_class})')
+  es = _event_slabs(ens_slab, n_outer, ens, slab,
+                    (max(n_member, 1) - 1) * member_stride, 'member')
+  ts = _event_slabs(truth_slab, n_outer, truth, slab, 0, 'truth')
+  hs = [_event_slabs(tb, n_outer, x, slab, 0, 'threshold')
+        for tb, x in zip(thr_slabs, thresholds)]
+  if slab * n_outer == 0:  # no points: nothing to count
+    return out.zero_()
+  hs_dev = None
+  if any(tb is not None for tb in hs):
+    ident = np.arange(n_outer, dtype=np.int64)
+    hs_dev = upload_table(np.stack([ident if tb is None else tb
+                                    for tb in hs]), dev)
+  _launch('event_counts', 'wb2_event_counts', dtype_code(ens.dtype),
+          _lib.ptr(ens), _lib.ptr(None if es is None else
+                                  upload_table(es, dev)),
+          _lib.ptr(truth), _lib.ptr(None if ts is None else
+                                    upload_table(ts, dev)),
+          _lib.ptr_array(thresholds), _lib.ptr(hs_dev), len(thresholds),
+          n_member, member_stride, n_outer, n_row, n_col,
+          _lib.ptr(_upload_i32(cls.astype(np.int32), dev)), n_class,
+          _lib.ptr(out), current_stream_ptr(dev))
+  return out
+
+
+def event_fold(cnt: torch.Tensor, wrow, mult) -> torch.Tensor:
+  """wb2_event_fold: float64 [n_threshold, n_outer, n_region, n_code] =
+  sum_i wrow[r, i] * float(sum_c mult[r, c] * cnt[.., i, c, code]), the inner
+  sum in int64, the rows in increasing order: a fixed order.  `wrow` (float64
+  [n_region, n_row]) and `mult` (int32 [n_region, n_class]) are HOST arrays."""
+  if cnt.dtype != torch.int32 or cnt.dim() != 5 or not cnt.is_contiguous():
+    raise ValueError('cnt must be a contiguous int32 [threshold, outer, row, '
+                     'class, code] tensor')
+  n_thr, n_outer, n_row, n_class, n_code = (int(n) for n in cnt.shape)
+  wrow = np.ascontiguousarray(wrow, dtype=np.float64)
+  mult = np.ascontiguousarray(mult, dtype=np.int32)
+  n_region = wrow.shape[0] if wrow.ndim == 2 else -1
+  if wrow.shape != (n_region, n_row) or mult.shape != (n_region, n_class):
+    raise ValueError('wrow must be [n_region, n_row] and mult [n_region, '
+                     'n_class]')
+  dev = cnt.device
+  out = torch.empty((n_thr, n_outer, n_region, n_code), dtype=torch.float64,
+                    device=dev)
+  if out.numel() == 0:
+    return out
+  _launch('event_fold', 'wb2_event_fold', _lib.ptr(cnt), n_thr * n_outer,
+          n_row, n_class, n_code,
+          _lib.ptr(upload_f64_table(wrow, dev) if wrow.size else None),
+          _lib.ptr(_upload_i32(mult.reshape(-1), dev)), n_region,
+          _lib.ptr(out), current_stream_ptr(dev))
+  return out
+
+
 def ensemble_threshold_reduce(plan: ReductionPlan, ens: torch.Tensor,
                               member_stride: int, n_member: int, ens_slab,
                               truth: torch.Tensor, truth_slab,

@@ -1636,6 +1636,100 @@ int wb2_event_counts_geometry(int dtype, int32_t n_member, int32_t n_class,
                               int32_t* thresholds_per_launch,
                               int64_t* lds_bytes, int32_t* max_grid_outer);
 
+/*
+ * K19: neighbourhood verification, the sufficient statistics of the fractions
+ * skill score (FSS, Roberts & Lean 2008).  The reference has no counterpart.
+ *
+ * wb2_event_codes: K18's operands and slab-table convention (ens, ens_slab,
+ * truth, truth_slab, a HOST array of n_threshold DEV threshold pointers,
+ * thr_slab[t * n_outer + o], n_member, member_stride, n_outer; tables DEV
+ * int64, null = identity, every value the caller's to check) and K18's
+ * per-point definitions.  Instead of a histogram it writes
+ *   code[t][o][i][j] (DEV uint16, every element written)
+ *     = k | obs << 8 | invalid << 9,   k = obs = 0 where invalid,
+ * k = the members with x > thr (0..128), obs = truth > thr, invalid iff the
+ * truth or any member is NaN.  One thread per 16-byte lane of points (where
+ * ens, truth, every threshold pointer and code are 16-byte aligned and n_col
+ * and member_stride are whole lanes: 4 float32, 2 float64) or per point
+ * otherwise; up to 4 thresholds share ONE read of the members and the truth
+ * ((n_member + 1 + T) elements read and 2 T bytes written per point); the
+ * members are requested four at a time before any is compared.  More
+ * thresholds become further launches here.
+ * Checked before anything is enqueued, in this order: the dtype ("unknown
+ * dtype"), 1 <= n_member <= 128 ("n_member="), n_threshold >= 1, a negative
+ * member_stride, negative sizes, null pointers ("null pointer") and the grid.
+ * Zero n_outer, n_row or n_col is a no-op whatever the pointers are.
+ *
+ * wb2_fss_sums: code is a plane [n_cell][n_row][n_col] of such codes (n_cell =
+ * thresholds x outer indices), window a HOST list of n_window odd window sizes
+ * n = 2 h + 1 in grid points (1 <= n <= 255, n <= n_col), col_class DEV
+ * int32[n_col] with values in [0, n_class) (the caller's to check).  The
+ * window of centre (i, j) is the rows max(0, i - h) .. min(n_row - 1, i + h)
+ * (clipped) and the columns (j - h .. j + h) mod n_col (cyclic).  With
+ *   F = the sum of k over the window,  O = n_member * the sum of obs,
+ *   sums[cell][w][i][c][0..5] (DEV int64, every element written) = the sums
+ *   over the valid centres j of class c in row i of
+ *     (F - O)^2,  F^2,  O^2,  F,  O,  1.
+ * An invalid point counts as k = obs = 0 in every window and is no centre.
+ * Integer work only, no global atomics, no float: two runs are bit-equal.
+ * A workgroup of 256 threads owns one cell and rows_per_group adjacent rows
+ * at full row width, thread t the ceil(n_col / 256) columns from t times that
+ * on.  Per window it keeps the vertical running sum of every column in LDS (k
+ * and obs in the halves of one word), adds the entering and subtracts the
+ * leaving row, re-read from the plane (the first row of a group sums its
+ * window directly); an inclusive scan of that row in LDS makes a horizontal
+ * window two reads, the cyclic wrap an index and a multiple of the row total.
+ * The six sums reach the LDS sums [window][class][6] by a wave reduction where
+ * the columns of a wave are one class, by 64-bit integer LDS adds otherwise,
+ * and leave with plain stores.  All windows of a launch share the walk;
+ * windows_per_launch = the most of min(n_window, 4) for which
+ *   lds_bytes = windows * (n_class * 48 + n_col * 12) + 128
+ * fits 163840 bytes; more windows become further launches here.  Cells go
+ * along the grid, max_grid_outer per grid row.  No overflow: F, O < 2^24, a
+ * sum is below (n_member * n^2)^2 * n_col < 2^63.
+ * Checked before anything is enqueued, in this order: 1 <= n_member <= 128
+ * ("n_member="), 1 <= n_class <= 64 ("n_class="), n_window >= 1, one window
+ * against the budget ("LDS budget"), negative sizes, null pointers ("null
+ * pointer"), every window ("window=") and the grid.  Zero n_cell, n_row or
+ * n_col is a no-op whatever the pointers are.
+ *
+ * wb2_fss_sums_geometry: rows_per_group (32), windows_per_launch, lds_bytes
+ * and max_grid_outer as above, with the same checks.
+ *
+ * wb2_fss_fold: sums as above, w DEV float64[n_window][3][n_region][n_row]
+ * (three groups of row weights per window), mult DEV int32[n_region][n_class],
+ *   table[cell][w][r][q] = sum_i w[w][g(q)][r][i] *
+ *                          (double)(sum_c mult[r][c] * sums[cell][w][i][c][q])
+ * with g(q) = 0 for q = 0, 1, 2, 1 for q = 3, 4 and 2 for q = 5, the inner sum
+ * in int64 and the rows in increasing order, acc = acc + w * s from 0.0 with no
+ * fused multiply-add: wb2_event_fold's rule with int64 inputs and a weight
+ * group per q.  One wave per (cell, w, r) and all six q: lane l takes row
+ * i0 + l of a block of 64 rows (its 48 contiguous bytes of every class, the
+ * integer sums, the six products), then the wave adds the block's products
+ * to the accumulators lane by lane, i.e. in increasing row order; the loads
+ * and the integer work are spread over the lanes, the float sum is the one a
+ * single thread would take.  Still a first form: untuned.  Zero n_cell,
+ * n_window or n_region is a no-op.
+ */
+int wb2_event_codes(int dtype, const void* ens, const int64_t* ens_slab,
+                    const void* truth, const int64_t* truth_slab,
+                    const void* const* threshold, const int64_t* thr_slab,
+                    int32_t n_threshold, int32_t n_member,
+                    int64_t member_stride, int64_t n_outer, int32_t n_row,
+                    int32_t n_col, uint16_t* code, void* stream);
+int wb2_fss_sums(const uint16_t* code, int64_t n_cell, int32_t n_row,
+                 int32_t n_col, int32_t n_member, const int32_t* window,
+                 int32_t n_window, const int32_t* col_class, int32_t n_class,
+                 int64_t* sums, void* stream);
+int wb2_fss_sums_geometry(int32_t n_col, int32_t n_class, int32_t n_window,
+                          int32_t* rows_per_group,
+                          int32_t* windows_per_launch, int64_t* lds_bytes,
+                          int32_t* max_grid_outer);
+int wb2_fss_fold(const int64_t* sums, int64_t n_cell, int32_t n_window,
+                 int32_t n_row, int32_t n_class, const double* w,
+                 const int32_t* mult, int32_t n_region, double* table,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -248,6 +248,16 @@ _SIGNATURES = {
     'wb2_event_counts_geometry': (_int, [
         _int, _i32, _i32, _i32, _int, _c.POINTER(_i32), _c.POINTER(_i32),
         _c.POINTER(_i64), _c.POINTER(_i32)]),
+    'wb2_event_codes': (_int, [
+        _int, _vp, _vp, _vp, _vp, _c.POINTER(_vp), _vp, _i32, _i32, _i64,
+        _i64, _i32, _i32, _vp, _vp]),
+    'wb2_fss_sums': (_int, [_vp, _i64, _i32, _i32, _i32, _c.POINTER(_i32),
+                            _i32, _vp, _i32, _vp, _vp]),
+    'wb2_fss_sums_geometry': (_int, [
+        _i32, _i32, _i32, _c.POINTER(_i32), _c.POINTER(_i32),
+        _c.POINTER(_i64), _c.POINTER(_i32)]),
+    'wb2_fss_fold': (_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _vp,
+                            _vp]),
 }
 
 _lib = None

@@ -1814,6 +1814,69 @@ def _event_slabs(table, n_outer: int, x: torch.Tensor, slab: int, extra: int,
   return table
 
 
+def _event_operands(ens, member_stride, n_member, truth, thresholds, thr_slabs,
+                    n_outer, n_row, n_col):
+  """The operand checks of the event front ends (K18 counts, K19 codes):
+  (thresholds, thr_slabs, n_member, n_outer, n_row, n_col, member_stride) as
+  lists and ints."""
+  thresholds = list(thresholds)
+  if not thresholds:
+    raise ValueError('no thresholds')
+  _require_float(ens, truth, *thresholds)
+  # (`ens` may be a view whose whole slabs its table addresses)
+  _check_contiguous(ens.device, 'the device of the members', truth,
+                    *thresholds, view=ens)
+  n_member, n_outer, n_row, n_col, member_stride = (
+      int(v) for v in (n_member, n_outer, n_row, n_col, member_stride))
+  if min(n_outer, n_row, n_col) < 0 or member_stride < 0:
+    raise ValueError('bad sizes')
+  thr_slabs = list(thr_slabs) if thr_slabs is not None else [None] * len(
+      thresholds)
+  if len(thr_slabs) != len(thresholds):
+    raise ValueError('one slab table (or None) per threshold')
+  return (thresholds, thr_slabs, n_member, n_outer, n_row, n_col,
+          member_stride)
+
+
+def _event_tables(ens, member_stride, n_member, ens_slab, truth, truth_slab,
+                  thresholds, thr_slabs, n_outer, slab):
+  """The HOST slab tables of an event front end, checked against the
+  operands' storage (`_event_slabs`): (member, truth, [threshold]) tables."""
+  es = _event_slabs(ens_slab, n_outer, ens, slab,
+                    (max(n_member, 1) - 1) * member_stride, 'member')
+  ts = _event_slabs(truth_slab, n_outer, truth, slab, 0, 'truth')
+  hs = [_event_slabs(tb, n_outer, x, slab, 0, 'threshold')
+        for tb, x in zip(thr_slabs, thresholds)]
+  return es, ts, hs
+
+
+def _event_args(ens, es, truth, ts, thresholds, hs, n_member, member_stride,
+                n_outer, n_row, n_col) -> tuple:
+  """The leading C arguments that wb2_event_counts and wb2_event_codes share,
+  the tables uploaded."""
+  dev = ens.device
+  hs_dev = None
+  if any(tb is not None for tb in hs):
+    ident = np.arange(n_outer, dtype=np.int64)
+    hs_dev = upload_table(np.stack([ident if tb is None else tb
+                                    for tb in hs]), dev)
+  return (dtype_code(ens.dtype),
+          _lib.ptr(ens), _lib.ptr(None if es is None else
+                                  upload_table(es, dev)),
+          _lib.ptr(truth), _lib.ptr(None if ts is None else
+                                    upload_table(ts, dev)),
+          _lib.ptr_array(thresholds), _lib.ptr(hs_dev), len(thresholds),
+          n_member, member_stride, n_outer, n_row, n_col)
+
+
+def _column_classes(col_class, n_col: int, n_class: int) -> np.ndarray:
+  """`col_class` as int64[n_col], every value in [0, n_class)."""
+  cls = np.ascontiguousarray(col_class, dtype=np.int64).reshape(-1)
+  if cls.size != n_col or (n_col and (cls.min() < 0 or cls.max() >= n_class)):
+    raise IndexError(f'col_class must hold {n_col} classes in [0, {n_class})')
+  return cls
+
+
 def event_counts(ens: torch.Tensor, member_stride: int, n_member: int,
                  ens_slab, truth: torch.Tensor, truth_slab,
                  thresholds: t.Sequence[torch.Tensor], thr_slabs, n_outer: int,
@@ -1829,49 +1892,24 @@ def event_counts(ens: torch.Tensor, member_stride: int, n_member: int,
   [0, n_class)) are HOST sequences, None = identity; all of them are checked
   here against the operands' storage: the kernel trusts them.  Up to 4
   thresholds share one read of the members; the C side splits the rest."""
-  thresholds = list(thresholds)
-  if not thresholds:
-    raise ValueError('no thresholds')
-  _require_float(ens, truth, *thresholds)
+  (thresholds, thr_slabs, n_member, n_outer, n_row, n_col,
+   member_stride) = _event_operands(ens, member_stride, n_member, truth,
+                                    thresholds, thr_slabs, n_outer, n_row,
+                                    n_col)
   dev = ens.device
-  # (`ens` may be a view whose whole slabs its table addresses)
-  _check_contiguous(dev, 'the device of the members', truth, *thresholds,
-                    view=ens)
-  n_member, n_outer, n_row, n_col, n_class, member_stride = (
-      int(v) for v in (n_member, n_outer, n_row, n_col, n_class,
-                       member_stride))
-  if min(n_outer, n_row, n_col) < 0 or member_stride < 0:
-    raise ValueError('bad sizes')
-  thr_slabs = list(thr_slabs) if thr_slabs is not None else [None] * len(
-      thresholds)
-  if len(thr_slabs) != len(thresholds):
-    raise ValueError('one slab table (or None) per threshold')
+  n_class = int(n_class)
   slab = n_row * n_col
   n_code = 2 * (n_member + 1) + 1
   out = torch.empty((len(thresholds), n_outer, n_row, n_class, n_code),
                     dtype=torch.int32, device=dev)
-  cls = np.ascontiguousarray(col_class, dtype=np.int64).reshape(-1)
-  if cls.size != n_col or (n_col and (cls.min() < 0 or cls.max() >= n_class)):
-    raise IndexError(f'col_class must hold {n_col} classes in [0, {n_class})')
-  es = _event_slabs(ens_slab, n_outer, ens, slab,
-                    (max(n_member, 1) - 1) * member_stride, 'member')
-  ts = _event_slabs(truth_slab, n_outer, truth, slab, 0, 'truth')
-  hs = [_event_slabs(tb, n_outer, x, slab, 0, 'threshold')
-        for tb, x in zip(thr_slabs, thresholds)]
+  cls = _column_classes(col_class, n_col, n_class)
+  es, ts, hs = _event_tables(ens, member_stride, n_member, ens_slab, truth,
+                             truth_slab, thresholds, thr_slabs, n_outer, slab)
   if slab * n_outer == 0:  # no points: nothing to count
     return out.zero_()
-  hs_dev = None
-  if any(tb is not None for tb in hs):
-    ident = np.arange(n_outer, dtype=np.int64)
-    hs_dev = upload_table(np.stack([ident if tb is None else tb
-                                    for tb in hs]), dev)
-  _launch('event_counts', 'wb2_event_counts', dtype_code(ens.dtype),
-          _lib.ptr(ens), _lib.ptr(None if es is None else
-                                  upload_table(es, dev)),
-          _lib.ptr(truth), _lib.ptr(None if ts is None else
-                                    upload_table(ts, dev)),
-          _lib.ptr_array(thresholds), _lib.ptr(hs_dev), len(thresholds),
-          n_member, member_stride, n_outer, n_row, n_col,
+  _launch('event_counts', 'wb2_event_counts',
+          *_event_args(ens, es, truth, ts, thresholds, hs, n_member,
+                       member_stride, n_outer, n_row, n_col),
           _lib.ptr(_upload_i32(cls.astype(np.int32), dev)), n_class,
           _lib.ptr(out), current_stream_ptr(dev))
   return out
@@ -1900,6 +1938,106 @@ def event_fold(cnt: torch.Tensor, wrow, mult) -> torch.Tensor:
   _launch('event_fold', 'wb2_event_fold', _lib.ptr(cnt), n_thr * n_outer,
           n_row, n_class, n_code,
           _lib.ptr(upload_f64_table(wrow, dev) if wrow.size else None),
+          _lib.ptr(_upload_i32(mult.reshape(-1), dev)), n_region,
+          _lib.ptr(out), current_stream_ptr(dev))
+  return out
+
+
+def event_codes(ens: torch.Tensor, member_stride: int, n_member: int, ens_slab,
+                truth: torch.Tensor, truth_slab,
+                thresholds: t.Sequence[torch.Tensor], thr_slabs, n_outer: int,
+                n_row: int, n_col: int) -> torch.Tensor:
+  """K19, wb2_event_codes: uint16 [n_threshold, n_outer, n_row, n_col] codes
+  k | observed << 8 | invalid << 9 of every point (k = the members exceeding;
+  k = observed = 0 where the truth or a member is NaN).  The operands, the
+  slab tables and their checks are those of `event_counts`."""
+  (thresholds, thr_slabs, n_member, n_outer, n_row, n_col,
+   member_stride) = _event_operands(ens, member_stride, n_member, truth,
+                                    thresholds, thr_slabs, n_outer, n_row,
+                                    n_col)
+  dev = ens.device
+  slab = n_row * n_col
+  out = torch.empty((len(thresholds), n_outer, n_row, n_col),
+                    dtype=torch.uint16, device=dev)
+  es, ts, hs = _event_tables(ens, member_stride, n_member, ens_slab, truth,
+                             truth_slab, thresholds, thr_slabs, n_outer, slab)
+  if slab * n_outer == 0:  # no points
+    return out
+  _launch('event_codes', 'wb2_event_codes',
+          *_event_args(ens, es, truth, ts, thresholds, hs, n_member,
+                       member_stride, n_outer, n_row, n_col),
+          _lib.ptr(out), current_stream_ptr(dev))
+  return out
+
+
+def fss_sums_geometry(n_col: int, n_class: int, n_window: int) -> dict:
+  """Extents of the K19 box-sum kernel: a workgroup owns `rows_per_group` rows
+  of one cell at full row width, `windows_per_launch` windows share one walk,
+  the running sums, the scanned row and the class sums take `lds_bytes` of
+  LDS, `max_grid_outer` cells per grid row."""
+  return _geometry('wb2_fss_sums_geometry',
+                   (int(n_col), int(n_class), int(n_window)),
+                   [('rows_per_group', _I32), ('windows_per_launch', _I32),
+                    ('lds_bytes', ctypes.c_int64), ('max_grid_outer', _I32)])
+
+
+def fss_sums(code: torch.Tensor, windows, n_member: int, col_class,
+             n_class: int) -> torch.Tensor:
+  """K19, wb2_fss_sums: int64 [n_cell, n_window, n_row, n_class, 6] of a
+  contiguous uint16 code plane [..., n_row, n_col] (`event_codes`; the leading
+  dims are the cells): over the valid centres of every (row, column class)
+  the sums of (F - O)^2, F^2, O^2, F, O and 1, F = the window sum of k, O =
+  n_member * the window sum of observed; windows are odd sizes in grid points,
+  clipped in the rows and cyclic in the columns.  `windows` and `col_class`
+  are HOST sequences; `col_class` is checked here, the windows by the entry
+  point."""
+  if code.dtype != torch.uint16 or code.dim() < 2 or not code.is_contiguous():
+    raise ValueError('code must be a contiguous uint16 [..., row, column] '
+                     'tensor')
+  n_row, n_col = (int(n) for n in code.shape[-2:])
+  n_cell = int(np.prod(code.shape[:-2], dtype=np.int64))
+  windows = np.ascontiguousarray(windows, dtype=np.int32).reshape(-1)
+  n_member, n_class = int(n_member), int(n_class)
+  if windows.size == 0:
+    raise ValueError('no windows')
+  cls = _column_classes(col_class, n_col, n_class)
+  dev = code.device
+  out = torch.empty((n_cell, windows.size, n_row, n_class, 6),
+                    dtype=torch.int64, device=dev)
+  if out.numel() == 0 or n_col == 0:
+    return out.zero_()
+  _launch('fss_sums', 'wb2_fss_sums', _lib.ptr(code), n_cell, n_row, n_col,
+          n_member, windows.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+          windows.size, _lib.ptr(_upload_i32(cls.astype(np.int32), dev)),
+          n_class, _lib.ptr(out), current_stream_ptr(dev))
+  return out
+
+
+def fss_fold(sums: torch.Tensor, w, mult) -> torch.Tensor:
+  """K19, wb2_fss_fold: float64 [n_cell, n_window, n_region, 6] = sum_i
+  w[window, g(q), r, i] * float(sum_c mult[r, c] * sums[.., i, c, q]) with the
+  weight group g(q) = 0 for q = 0, 1, 2, 1 for q = 3, 4 and 2 for q = 5, the
+  inner sum in int64, the rows in increasing order.  `w` (float64 [n_window, 3,
+  n_region, n_row]) and `mult` (int32 [n_region, n_class]) are HOST arrays."""
+  if sums.dtype != torch.int64 or sums.dim() != 5 or sums.shape[-1] != 6 or (
+      not sums.is_contiguous()):
+    raise ValueError('sums must be a contiguous int64 [cell, window, row, '
+                     'class, 6] tensor')
+  n_cell, n_window, n_row, n_class = (int(n) for n in sums.shape[:4])
+  w = np.ascontiguousarray(w, dtype=np.float64)
+  mult = np.ascontiguousarray(mult, dtype=np.int32)
+  n_region = mult.shape[0] if mult.ndim == 2 else -1
+  if w.shape != (n_window, 3, n_region, n_row) or mult.shape != (
+      n_region, n_class):
+    raise ValueError('w must be [n_window, 3, n_region, n_row] and mult '
+                     '[n_region, n_class]')
+  dev = sums.device
+  out = torch.empty((n_cell, n_window, n_region, 6), dtype=torch.float64,
+                    device=dev)
+  if out.numel() == 0:
+    return out
+  _launch('fss_fold', 'wb2_fss_fold', _lib.ptr(sums), n_cell, n_window, n_row,
+          n_class, _lib.ptr(upload_f64_table(w, dev) if w.size else None),
           _lib.ptr(_upload_i32(mult.reshape(-1), dev)), n_region,
           _lib.ptr(out), current_stream_ptr(dev))
   return out

@@ -71,6 +71,23 @@ def counts_loop(ens, truth, thrs, col_class, n_class):
   return out
 
 
+def counts_of_code_planes(plane, n_member, col_class, n_class):
+  """int32 [T, O, R, n_class, n_code] from the uint16 planes [T, O, R, C] of
+  the neighbourhood front end (k | observed << 8 | invalid << 9): every point
+  recoded as o * (M + 1) + k, or 2 (M + 1) where the invalid bit is set, and
+  counted per (row, column class) -- what the event counts hold."""
+  plane = np.asarray(plane).astype(np.int64)
+  code = np.where(plane & 0x200, 2 * (n_member + 1),
+                  ((plane >> 8) & 1) * (n_member + 1) + (plane & 0xff))
+  n_code = n_codes(n_member)
+  out = np.zeros(plane.shape[:3] + (n_class, n_code), dtype=np.int32)
+  cls = np.asarray(col_class, dtype=np.int64)
+  for idx in np.ndindex(*plane.shape[:3]):
+    out[idx] = np.bincount(cls * n_code + code[idx],
+                           minlength=n_class * n_code).reshape(n_class, n_code)
+  return out
+
+
 def codes(ens, truth, thr):
   """Codes [..., R, C] of ens [M, ..., R, C], truth and thr [..., R, C]."""
   n_member = ens.shape[0]

@@ -68,6 +68,27 @@ def test_host_counts_read_through_slab_tables():
   np.testing.assert_array_equal(one, same)
 
 
+@pytest.mark.parametrize('dtype', [np.float32, np.float64])
+@pytest.mark.parametrize('n_col', [7, 8])
+def test_host_codes_recount_to_the_host_counts(n_col, dtype):
+  # the packing of the neighbourhood codes and the counting of the event table
+  # held to each other: the codes, recoded and counted, are the counts.  (Both
+  # sit on `events.host_exceedance`; the definition itself is held to
+  # events_np by the tests above.)
+  from weatherbench2_amd import neighborhood
+  n_member, n_outer, n_row, n_class = 7, 2, 3, 4
+  ens, truth, thrs = cases.edge_case(n_member, 5, n_outer, n_row, n_col, dtype)
+  cls = cases.classes(n_col, n_class)
+  front = (ens, n_outer * n_row * n_col, n_member, None, truth, None, thrs,
+           None, n_outer, n_row, n_col)
+  plane = neighborhood.host_codes(*front)
+  assert plane.dtype == np.uint16
+  counts = events.host_counts(*front, cls, n_class)
+  np.testing.assert_array_equal(
+      events_np.counts_of_code_planes(plane, n_member, cls, n_class), counts)
+  assert counts[..., -1].sum() > 0  # the NaN placements are inside
+
+
 # ---------------------------------------------------------------------------
 # 2. the table vs an independent dense restatement; 3. vs the oracle's Brier
 # ---------------------------------------------------------------------------

@@ -97,6 +97,34 @@ def test_codes_walk_the_slab_tables():
                        None, n_outer, n_row, n_col)
 
 
+@pytest.mark.parametrize('dtype', [np.float32, np.float64])
+@pytest.mark.parametrize('n_col', [7, 8])
+def test_device_codes_recount_to_the_device_counts(n_col, dtype):
+  # what K19's front end and K18 do with (k, obs, bad), held to each other: the
+  # codes, recoded and counted per (row, column class), are the event counts.
+  # (Both kernels call the one exceed_points(); that is held to the host path
+  # by the tests above and by tests/test_events_gpu.py.)
+  from tests import events_cases
+  from tests import events_np
+  n_member, n_outer, n_row, n_class = 7, 2, 3, 4
+  ens, truth, thrs = events_cases.edge_case(n_member, 5, n_outer, n_row,
+                                            n_col, dtype)
+  cls = events_cases.classes(n_col, n_class)
+  flat = torch.empty(ens.size + 1, dtype=DTYPES[dtype], device='cuda')
+  flat[1:] = _dev(ens).reshape(-1)
+  shifted = flat[1:].reshape(ens.shape)
+  assert shifted.data_ptr() % 16 != 0
+  # (the members as they are, and with their base off by one element)
+  for ens_dev in (_dev(ens), shifted):
+    front = (ens_dev, n_outer * n_row * n_col, n_member, None, _dev(truth),
+             None, [_dev(t) for t in thrs], None, n_outer, n_row, n_col)
+    plane = engine.event_codes(*front).cpu().numpy()
+    counts = engine.event_counts(*front, cls, n_class).cpu().numpy()
+    np.testing.assert_array_equal(
+        events_np.counts_of_code_planes(plane, n_member, cls, n_class), counts)
+    assert counts[..., -1].sum() > 0  # the NaN placements are inside
+
+
 # ---------------------------------------------------------------------------
 # 2. wb2_fss_sums on code planes made on the host
 # ---------------------------------------------------------------------------

@@ -9,10 +9,9 @@
 //   wb2_event_fold    table[t][o][r][code] = sum_i wrow[r][i] *
 //                     (double)(sum_c mult[r][c] * cnt[t][o][i][c][code])
 //
-// For one point: k = members with x > thr (IEEE: a NaN threshold exceeds
-// nothing, equality is not exceedance), obs = truth > thr, invalid iff truth
-// or any member is NaN.  code = obs * (M + 1) + k, the invalid code is
-// 2 (M + 1), n_code = 2 (M + 1) + 1.  The region weights factor into a row
+// For one point (k, obs, invalid: event_common.hpp): code = obs * (M + 1) + k,
+// the invalid code is 2 (M + 1), n_code = 2 (M + 1) + 1.  The region weights
+// factor into a row
 // weight and an integer column multiplicity that is constant on a column
 // class, so the counting kernel adds integers only (LDS atomics: integer adds
 // commute, two runs are bit-equal) and the float work is the ordered fold.
@@ -20,17 +19,16 @@
 //
 // Counting: a workgroup of 256 threads owns rows_per_group adjacent rows of one
 // outer index -- one contiguous run of every slab -- and walks it with 16-byte
-// lanes (or one element per access).  A thread loads the truth and up to 4
-// thresholds of its points, then the M members kEventAhead at a time (all
-// requested before any is compared), forms the codes and adds 1 to the LDS
-// histogram [threshold][row][class][code]; after a barrier the histogram goes
+// lanes (or one element per access).  A thread takes its points through
+// exceed_points(), forms the codes and adds 1 to the LDS histogram
+// [threshold][row][class][code]; after a barrier the histogram goes
 // to memory with plain stores.  Members and truth are read ONCE for the
 // thresholds of a launch: (M + 1 + T) elements per point.
 
 #include <cstdint>
 
 #include "common.hpp"
-#include "derived_common.hpp"
+#include "event_common.hpp"
 #include "launch_common.hpp"
 #include "trace.hpp"
 #include "wb2hip.h"
@@ -39,25 +37,15 @@ namespace wb2 {
 namespace {
 
 constexpr int kEventThreads = 256;
-constexpr int kEventThr = 4;     // thresholds that share one read
 constexpr int kEventRows = 4;    // rows of one workgroup, at most
-constexpr int kEventAhead = 4;   // members requested before any is compared
 constexpr long long kEventLds = 64 * 1024;  // bytes of histogram per workgroup
-constexpr int kEventMaxMember = 128;
-constexpr int kEventMaxClass = 64;
+constexpr char kEventTakes[] = "the event table takes";
 
-struct EventParams {
-  const void* ens;
-  const void* truth;
-  const void* thr[kEventThr];
-  const long long* ens_slab;    // [n_outer] or null: member 0's slab
-  const long long* truth_slab;  // [n_outer] or null
-  const long long* thr_slab[kEventThr];  // each [n_outer] or null
+struct EventParams : ExceedOperands {
   const int* col_class;         // [n_col]
   int* cnt;                     // the first threshold of this launch
   long long cnt_thr_stride;     // counts of one threshold
-  long long member_stride, n_outer;
-  int n_member, n_row, n_col, n_class, rows_per_group;
+  int n_row, n_col, n_class, rows_per_group;
 };
 
 template <typename T, int VEC, int NT>
@@ -76,18 +64,15 @@ __global__ void __launch_bounds__(kEventThreads)
   for (int i = threadIdx.x; i < NT * thr_bins; i += kEventThreads) hist[i] = 0;
   __syncthreads();
 
-  const long long slab_elems = (long long)p.n_row * p.n_col;
+  // (once per workgroup: the element loop below loads no table)
+  const long long slab = (long long)p.n_row * p.n_col;
   const long long first = (long long)row0 * p.n_col;
-  const T* xb = static_cast<const T*>(p.ens) +
-                (p.ens_slab ? p.ens_slab[o] : o) * slab_elems + first;
-  const T* tb = static_cast<const T*>(p.truth) +
-                (p.truth_slab ? p.truth_slab[o] : o) * slab_elems + first;
+  const T* xb = exceed_slab<T>(p.ens, p.ens_slab, o, slab, first);
+  const T* tb = exceed_slab<T>(p.truth, p.truth_slab, o, slab, first);
   const T* hb[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t)
-    hb[t] = static_cast<const T*>(p.thr[t]) +
-            (p.thr_slab[t] ? p.thr_slab[t][o] : o) * slab_elems + first;
-
+    hb[t] = exceed_slab<T>(p.thr[t], p.thr_slab[t], o, slab, first);
   const int n_elem = nrow * p.n_col;  // (the host checked that it fits)
   for (int e = (int)threadIdx.x * VEC; e < n_elem; e += kEventThreads * VEC) {
     T tv[VEC], hv[NT][VEC];
@@ -95,39 +80,8 @@ __global__ void __launch_bounds__(kEventThreads)
 #pragma unroll
     for (int t = 0; t < NT; ++t) load_v<T, VEC>(hb[t] + e, hv[t]);
     int k[NT][VEC];
-    bool bad[VEC];
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-      bad[v] = is_nan(tv[v]);
-#pragma unroll
-      for (int t = 0; t < NT; ++t) k[t][v] = 0;
-    }
-    const T* xe = xb + e;
-    int m = 0;
-    for (; m + kEventAhead <= M; m += kEventAhead) {
-      T x[kEventAhead][VEC];
-#pragma unroll
-      for (int u = 0; u < kEventAhead; ++u)
-        load_v<T, VEC>(xe + (m + u) * p.member_stride, x[u]);
-#pragma unroll
-      for (int u = 0; u < kEventAhead; ++u)
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) {
-          bad[v] = bad[v] || is_nan(x[u][v]);
-#pragma unroll
-          for (int t = 0; t < NT; ++t) k[t][v] += x[u][v] > hv[t][v] ? 1 : 0;
-        }
-    }
-    for (; m < M; ++m) {
-      T x[VEC];
-      load_v<T, VEC>(xe + m * p.member_stride, x);
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) {
-        bad[v] = bad[v] || is_nan(x[v]);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) k[t][v] += x[v] > hv[t][v] ? 1 : 0;
-      }
-    }
+    bool obs[NT][VEC], bad[VEC];
+    exceed_points<T, VEC, NT>(xb + e, p.member_stride, M, tv, hv, k, obs, bad);
     // (VEC divides n_col on the wide path: a lane never spans two rows)
     const int r = e / p.n_col;
     const int c = e - r * p.n_col;
@@ -137,7 +91,7 @@ __global__ void __launch_bounds__(kEventThreads)
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         const int code = bad[v] ? 2 * (M + 1)
-                                : (tv[v] > hv[t][v] ? M + 1 : 0) + k[t][v];
+                                : (obs[t][v] ? M + 1 : 0) + k[t][v];
         __hip_atomic_fetch_add(&hist[t * thr_bins + bin + code], 1,
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       }
@@ -214,7 +168,7 @@ struct EventGeometry {
 inline bool event_geometry(int n_member, int n_class, int n_threshold,
                            EventGeometry* g) {
   const long long row_bytes = 4ll * n_class * (2 * (n_member + 1) + 1);
-  const int nt_max = n_threshold < kEventThr ? n_threshold : kEventThr;
+  const int nt_max = n_threshold < kExceedThr ? n_threshold : kExceedThr;
   for (int nt = nt_max; nt >= 1; --nt)
     for (int rows = kEventRows; rows >= 1; rows /= 2)
       if (nt * rows * row_bytes <= kEventLds) {
@@ -224,39 +178,21 @@ inline bool event_geometry(int n_member, int n_class, int n_threshold,
   return false;
 }
 
-#define WB2_REQUIRE_EVENT_SHAPE(dtype, n_member, n_class, n_threshold)        \
-  do {                                                                         \
-    WB2_REQUIRE(dtype == WB2_F32 || dtype == WB2_F64, "unknown dtype %d",      \
-                (int)dtype);                                                   \
-    WB2_REQUIRE(n_member >= 1 && n_member <= kEventMaxMember,                  \
-                "n_member=%d: the event table takes 1 to %d members",          \
-                (int)n_member, kEventMaxMember);                               \
-    WB2_REQUIRE(n_class >= 1 && n_class <= kEventMaxClass,                     \
-                "n_class=%d: the event table takes 1 to %d column classes",    \
-                (int)n_class, kEventMaxClass);                                 \
-    WB2_REQUIRE(n_threshold >= 1, "n_threshold=%d", (int)n_threshold);         \
-  } while (0)
+// exceed_shape() and the column classes: the checks of the geometry query.
+inline int event_shape(int dtype, int n_member, int n_class, int n_threshold) {
+  if (const int rc = exceed_shape(kEventTakes, dtype, n_member, n_threshold))
+    return rc;
+  WB2_REQUIRE(n_class >= 1 && n_class <= kExceedMaxClass,
+              "n_class=%d: %s 1 to %d column classes", n_class, kEventTakes,
+              kExceedMaxClass);
+  return 0;
+}
 
 #define WB2_REQUIRE_EVENT_LDS(n_member, n_class, n_threshold, g)               \
   WB2_REQUIRE(event_geometry(n_member, n_class, n_threshold, &g),              \
               "the histogram of %d classes x %d codes does not fit the LDS "   \
               "budget of %lld bytes", (int)n_class, 2 * ((int)n_member + 1) + 1, \
               kEventLds)
-
-template <typename T, int VEC>
-void launch_counts(int nt, dim3 grid, size_t lds, hipStream_t s,
-                   const EventParams& p) {
-#define WB2_L(NT)                                                        \
-  hipLaunchKernelGGL((event_counts_kernel<T, VEC, NT>), grid,            \
-                     dim3(kEventThreads), lds, s, p)
-  switch (nt) {
-    case 1: WB2_L(1); break;
-    case 2: WB2_L(2); break;
-    case 3: WB2_L(3); break;
-    default: WB2_L(4); break;
-  }
-#undef WB2_L
-}
 
 }  // namespace
 }  // namespace wb2
@@ -270,7 +206,8 @@ int wb2_event_counts_geometry(int dtype, int32_t n_member, int32_t n_class,
                               int64_t* lds_bytes, int32_t* max_grid_outer) {
   using namespace wb2;
   (void)wide;  // the lane width changes neither the rows nor the histogram
-  WB2_REQUIRE_EVENT_SHAPE(dtype, n_member, n_class, n_threshold);
+  if (const int rc = event_shape(dtype, n_member, n_class, n_threshold))
+    return rc;
   WB2_REQUIRE(rows_per_group && thresholds_per_launch && lds_bytes &&
               max_grid_outer, "null pointer argument");
   EventGeometry g;
@@ -291,37 +228,25 @@ int wb2_event_counts(int dtype, const void* ens, const int64_t* ens_slab,
                      int32_t* cnt, void* stream) {
   WB2_TRACE();
   using namespace wb2;
-  WB2_REQUIRE_EVENT_SHAPE(dtype, n_member, n_class, n_threshold);
+  if (const int rc = event_shape(dtype, n_member, n_class, n_threshold))
+    return rc;
   EventGeometry g;
   WB2_REQUIRE_EVENT_LDS(n_member, n_class, n_threshold, g);
-  WB2_REQUIRE(member_stride >= 0, "member_stride=%lld is negative",
-              (long long)member_stride);
-  WB2_EMPTY_OK(n_outer);
-  WB2_EMPTY_OK(n_row);
-  WB2_EMPTY_OK(n_col);
-  WB2_REQUIRE(ens && truth && threshold && col_class && cnt,
-              "null pointer argument");
-  for (int t = 0; t < n_threshold; ++t)
-    WB2_REQUIRE(threshold[t], "null pointer argument (threshold %d)", t);
+  EventParams p{};
+  const int go = exceed_operands(ens, ens_slab, truth, truth_slab, threshold,
+                                 n_threshold, n_member, member_stride, n_outer,
+                                 n_row, n_col, &p);
+  if (go <= 0) return go;
+  WB2_REQUIRE(col_class && cnt, "null pointer argument");
   // (the walk over a row group counts in int, one stride past its end)
   WB2_REQUIRE((long long)g.rows_per_group * n_col < (1ll << 30),
               "n_col=%d: a group of %d rows is too long", (int)n_col,
               g.rows_per_group);
-  const int w = wide_lanes(dtype);
-  bool wide = all_aligned16(ens, truth) && n_col % w == 0 &&
-              member_stride % w == 0;
-  for (int t = 0; t < n_threshold; ++t) wide = wide && aligned16(threshold[t]);
+  const bool wide = exceed_wide(dtype, ens, truth, threshold, n_threshold,
+                                n_col, member_stride);
   const int n_code = 2 * (n_member + 1) + 1;
-  EventParams p{};
-  p.ens = ens;
-  p.truth = truth;
-  p.ens_slab = reinterpret_cast<const long long*>(ens_slab);
-  p.truth_slab = reinterpret_cast<const long long*>(truth_slab);
   p.col_class = col_class;
   p.cnt_thr_stride = (long long)n_outer * n_row * n_class * n_code;
-  p.member_stride = member_stride;
-  p.n_outer = n_outer;
-  p.n_member = n_member;
   p.n_row = n_row;
   p.n_col = n_col;
   p.n_class = n_class;
@@ -332,26 +257,18 @@ int wb2_event_counts(int dtype, const void* ens, const int64_t* ens_slab,
               "the grid does not fit: %lld outer indices of %lld row groups",
               (long long)n_outer, groups);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // more thresholds than one launch takes: further launches, each with its
-  // own read of the members
-  for (int t0 = 0; t0 < n_threshold; t0 += g.thresholds_per_launch) {
-    const int nt = n_threshold - t0 < g.thresholds_per_launch
-                       ? n_threshold - t0 : g.thresholds_per_launch;
-    for (int t = 0; t < kEventThr; ++t) {
-      p.thr[t] = t < nt ? threshold[t0 + t] : nullptr;
-      p.thr_slab[t] = (t < nt && thr_slab)
-          ? reinterpret_cast<const long long*>(thr_slab) +
-                (long long)(t0 + t) * n_outer
-          : nullptr;
-    }
-    p.cnt = cnt + t0 * p.cnt_thr_stride;
-    const size_t lds = (size_t)nt * g.rows_per_group * n_class * n_code * 4;
-    for_field(dtype, wide, [&](auto T0, auto V) {
-      launch_counts<decltype(T0), decltype(V)::value>(nt, grid, lds, s, p);
-    });
-    WB2_HIP_OK(hipGetLastError());
-  }
-  return 0;
+  return exceed_batches(
+      &p, threshold, thr_slab, n_threshold, g.thresholds_per_launch,
+      [&](int t0, int nt) {
+        p.cnt = cnt + t0 * p.cnt_thr_stride;
+        const size_t lds = (size_t)nt * g.rows_per_group * n_class * n_code * 4;
+        for_exceed(dtype, wide, nt, [&](auto T0, auto V, auto NT) {
+          hipLaunchKernelGGL(
+              (event_counts_kernel<decltype(T0), decltype(V)::value,
+                                   decltype(NT)::value>),
+              grid, dim3(kEventThreads), lds, s, p);
+        });
+      });
 }
 
 int wb2_event_fold(const int32_t* cnt, int64_t n_cell, int32_t n_row,

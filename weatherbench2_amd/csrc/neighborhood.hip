@@ -3,8 +3,8 @@
 // counterpart.
 //
 //   wb2_event_codes  code[t][o][i][j] (uint16) = k | obs << 8 | invalid << 9
-//                    of every point under threshold t: K18's per-point compare
-//                    (event_table.hip) with the code stored instead of counted
+//                    of every point under threshold t: the per-point compare
+//                    of event_common.hpp, stored where K18 counts it
 //   wb2_fss_sums     sums[cell][window][i][c][6] (int64): over the valid
 //                    centres j of class c in row i, with F = the window sum of
 //                    k and O = n_member * the window sum of obs,
@@ -36,7 +36,7 @@
 #include <cstdint>
 
 #include "common.hpp"
-#include "derived_common.hpp"
+#include "event_common.hpp"
 #include "launch_common.hpp"
 #include "trace.hpp"
 #include "wb2hip.h"
@@ -46,10 +46,6 @@ namespace {
 
 constexpr int kFssThreads = 256;
 constexpr int kFssWaves = kFssThreads / kWave;
-constexpr int kCodeThr = 4;      // thresholds that share one read
-constexpr int kCodeAhead = 4;    // members requested before any is compared
-constexpr int kFssMaxMember = 128;
-constexpr int kFssMaxClass = 64;
 constexpr int kFssMaxWindow = 255;
 constexpr int kFssWin = 4;       // windows served from one walk
 constexpr int kFssRows = 32;     // rows of one workgroup
@@ -61,17 +57,12 @@ constexpr unsigned kCodeObs = 0x100u, kCodeInvalid = 0x200u;
 // ---------------------------------------------------------------------------
 // wb2_event_codes
 // ---------------------------------------------------------------------------
-struct CodeParams {
-  const void* ens;
-  const void* truth;
-  const void* thr[kCodeThr];
-  const long long* ens_slab;    // [n_outer] or null: member 0's slab
-  const long long* truth_slab;  // [n_outer] or null
-  const long long* thr_slab[kCodeThr];  // each [n_outer] or null
+constexpr char kCodeTakes[] = "the event codes take";
+
+struct CodeParams : ExceedOperands {
   uint16_t* code;               // the first threshold of this launch
   long long code_thr_stride;    // codes of one threshold
-  long long member_stride, n_outer, slab;
-  int n_member;
+  long long slab;
 };
 
 template <int VEC>
@@ -88,8 +79,8 @@ __device__ __forceinline__ void store_codes(uint16_t* p,
   }
 }
 
-// One thread per VEC adjacent points of one slab: the truth and up to 4
-// thresholds, then the members kCodeAhead at a time as in K18.
+// One thread per VEC adjacent points of one slab: exceed_points(), with the
+// code stored.
 template <typename T, int VEC, int NT>
 __global__ void __launch_bounds__(kFssThreads)
     event_codes_kernel(const CodeParams p) {
@@ -98,50 +89,18 @@ __global__ void __launch_bounds__(kFssThreads)
       ((long long)blockIdx.x * kFssThreads + threadIdx.x) * VEC;
   // (VEC divides the slab on the wide path: a lane never leaves it)
   if (o >= p.n_outer || e >= p.slab) return;
-  const int M = p.n_member;
-  const T* xe = static_cast<const T*>(p.ens) +
-                (p.ens_slab ? p.ens_slab[o] : o) * p.slab + e;
+  int k[NT][VEC];
+  bool obs[NT][VEC], bad[VEC];
+  const T* xe = exceed_slab<T>(p.ens, p.ens_slab, o, p.slab, e);
   T tv[VEC], hv[NT][VEC];
-  load_v<T, VEC>(static_cast<const T*>(p.truth) +
-                     (p.truth_slab ? p.truth_slab[o] : o) * p.slab + e, tv);
+  // (the truth is requested before the thresholds' slabs are resolved)
+  load_v<T, VEC>(exceed_slab<T>(p.truth, p.truth_slab, o, p.slab, e), tv);
 #pragma unroll
   for (int t = 0; t < NT; ++t)
-    load_v<T, VEC>(static_cast<const T*>(p.thr[t]) +
-                       (p.thr_slab[t] ? p.thr_slab[t][o] : o) * p.slab + e,
+    load_v<T, VEC>(exceed_slab<T>(p.thr[t], p.thr_slab[t], o, p.slab, e),
                    hv[t]);
-  int k[NT][VEC];
-  bool bad[VEC];
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) {
-    bad[v] = is_nan(tv[v]);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) k[t][v] = 0;
-  }
-  int m = 0;
-  for (; m + kCodeAhead <= M; m += kCodeAhead) {
-    T x[kCodeAhead][VEC];
-#pragma unroll
-    for (int u = 0; u < kCodeAhead; ++u)
-      load_v<T, VEC>(xe + (m + u) * p.member_stride, x[u]);
-#pragma unroll
-    for (int u = 0; u < kCodeAhead; ++u)
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) {
-        bad[v] = bad[v] || is_nan(x[u][v]);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) k[t][v] += x[u][v] > hv[t][v] ? 1 : 0;
-      }
-  }
-  for (; m < M; ++m) {
-    T x[VEC];
-    load_v<T, VEC>(xe + m * p.member_stride, x);
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-      bad[v] = bad[v] || is_nan(x[v]);
-#pragma unroll
-      for (int t = 0; t < NT; ++t) k[t][v] += x[v] > hv[t][v] ? 1 : 0;
-    }
-  }
+  exceed_points<T, VEC, NT>(xe, p.member_stride, p.n_member, tv, hv, k, obs,
+                            bad);
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     uint16_t c[VEC];
@@ -149,23 +108,9 @@ __global__ void __launch_bounds__(kFssThreads)
     for (int v = 0; v < VEC; ++v)
       c[v] = (uint16_t)(bad[v] ? kCodeInvalid
                                : (unsigned)k[t][v] |
-                                     (tv[v] > hv[t][v] ? kCodeObs : 0u));
+                                     (obs[t][v] ? kCodeObs : 0u));
     store_codes<VEC>(p.code + t * p.code_thr_stride + o * p.slab + e, c);
   }
-}
-
-template <typename T, int VEC>
-void launch_codes(int nt, dim3 grid, hipStream_t s, const CodeParams& p) {
-#define WB2_L(NT)                                                       \
-  hipLaunchKernelGGL((event_codes_kernel<T, VEC, NT>), grid,            \
-                     dim3(kFssThreads), 0, s, p)
-  switch (nt) {
-    case 1: WB2_L(1); break;
-    case 2: WB2_L(2); break;
-    case 3: WB2_L(3); break;
-    default: WB2_L(4); break;
-  }
-#undef WB2_L
 }
 
 // ---------------------------------------------------------------------------
@@ -451,9 +396,9 @@ inline bool fss_geometry(int n_col, int n_class, int n_window,
 
 #define WB2_REQUIRE_FSS_SHAPE(n_col, n_class, n_window, g)                     \
   do {                                                                         \
-    WB2_REQUIRE(n_class >= 1 && n_class <= kFssMaxClass,                       \
+    WB2_REQUIRE(n_class >= 1 && n_class <= kExceedMaxClass,                    \
                 "n_class=%d: the fractions sums take 1 to %d column classes",  \
-                (int)n_class, kFssMaxClass);                                   \
+                (int)n_class, kExceedMaxClass);                                \
     WB2_REQUIRE(n_window >= 1, "n_window=%d", (int)n_window);                  \
     WB2_REQUIRE(n_col >= 0, "n_col=%d is negative", (int)n_col);               \
     WB2_REQUIRE(fss_geometry(n_col, n_class, n_window, &g),                    \
@@ -556,58 +501,36 @@ int wb2_event_codes(int dtype, const void* ens, const int64_t* ens_slab,
                     int32_t n_col, uint16_t* code, void* stream) {
   WB2_TRACE();
   using namespace wb2;
-  WB2_REQUIRE(dtype == WB2_F32 || dtype == WB2_F64, "unknown dtype %d",
-              (int)dtype);
-  WB2_REQUIRE(n_member >= 1 && n_member <= kFssMaxMember,
-              "n_member=%d: the event codes take 1 to %d members",
-              (int)n_member, kFssMaxMember);
-  WB2_REQUIRE(n_threshold >= 1, "n_threshold=%d", (int)n_threshold);
-  WB2_REQUIRE(member_stride >= 0, "member_stride=%lld is negative",
-              (long long)member_stride);
-  WB2_EMPTY_OK(n_outer);
-  WB2_EMPTY_OK(n_row);
-  WB2_EMPTY_OK(n_col);
-  WB2_REQUIRE(ens && truth && threshold && code, "null pointer argument");
-  for (int t = 0; t < n_threshold; ++t)
-    WB2_REQUIRE(threshold[t], "null pointer argument (threshold %d)", t);
-  const int w = wide_lanes(dtype);
-  bool wide = all_aligned16(ens, truth) && aligned16(code) && n_col % w == 0 &&
-              member_stride % w == 0;
-  for (int t = 0; t < n_threshold; ++t) wide = wide && aligned16(threshold[t]);
+  if (const int rc = exceed_shape(kCodeTakes, dtype, n_member, n_threshold))
+    return rc;
   CodeParams p{};
-  p.ens = ens;
-  p.truth = truth;
-  p.ens_slab = reinterpret_cast<const long long*>(ens_slab);
-  p.truth_slab = reinterpret_cast<const long long*>(truth_slab);
+  const int go = exceed_operands(ens, ens_slab, truth, truth_slab, threshold,
+                                 n_threshold, n_member, member_stride, n_outer,
+                                 n_row, n_col, &p);
+  if (go <= 0) return go;
+  WB2_REQUIRE(code, "null pointer argument");
+  const bool wide = aligned16(code) &&
+                    exceed_wide(dtype, ens, truth, threshold, n_threshold,
+                                n_col, member_stride);
   p.slab = (long long)n_row * n_col;
   p.code_thr_stride = (long long)n_outer * p.slab;
-  p.member_stride = member_stride;
-  p.n_outer = n_outer;
-  p.n_member = n_member;
   dim3 grid;
-  WB2_REQUIRE(outer_grid(n_outer, point_tiles(p.slab, wide ? w : 1,
-                                              kFssThreads), &grid),
+  WB2_REQUIRE(outer_grid(n_outer,
+                         point_tiles(p.slab, wide ? wide_lanes(dtype) : 1,
+                                     kFssThreads), &grid),
               "the grid does not fit: %lld outer indices of %lld points",
               (long long)n_outer, p.slab);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // more thresholds than one launch takes: further launches, each with its
-  // own read of the members
-  for (int t0 = 0; t0 < n_threshold; t0 += kCodeThr) {
-    const int nt = n_threshold - t0 < kCodeThr ? n_threshold - t0 : kCodeThr;
-    for (int t = 0; t < kCodeThr; ++t) {
-      p.thr[t] = t < nt ? threshold[t0 + t] : nullptr;
-      p.thr_slab[t] = (t < nt && thr_slab)
-          ? reinterpret_cast<const long long*>(thr_slab) +
-                (long long)(t0 + t) * n_outer
-          : nullptr;
-    }
-    p.code = code + t0 * p.code_thr_stride;
-    for_field(dtype, wide, [&](auto T0, auto V) {
-      launch_codes<decltype(T0), decltype(V)::value>(nt, grid, s, p);
-    });
-    WB2_HIP_OK(hipGetLastError());
-  }
-  return 0;
+  return exceed_batches(
+      &p, threshold, thr_slab, n_threshold, kExceedThr, [&](int t0, int nt) {
+        p.code = code + t0 * p.code_thr_stride;
+        for_exceed(dtype, wide, nt, [&](auto T0, auto V, auto NT) {
+          hipLaunchKernelGGL(
+              (event_codes_kernel<decltype(T0), decltype(V)::value,
+                                  decltype(NT)::value>),
+              grid, dim3(kFssThreads), 0, s, p);
+        });
+      });
 }
 
 int wb2_fss_sums_geometry(int32_t n_col, int32_t n_class, int32_t n_window,
@@ -632,9 +555,9 @@ int wb2_fss_sums(const uint16_t* code, int64_t n_cell, int32_t n_row,
                  int64_t* sums, void* stream) {
   WB2_TRACE();
   using namespace wb2;
-  WB2_REQUIRE(n_member >= 1 && n_member <= kFssMaxMember,
+  WB2_REQUIRE(n_member >= 1 && n_member <= kExceedMaxMember,
               "n_member=%d: the fractions sums take 1 to %d members",
-              (int)n_member, kFssMaxMember);
+              (int)n_member, kExceedMaxMember);
   FssGeometry g;
   WB2_REQUIRE_FSS_SHAPE(n_col, n_class, n_window, g);
   WB2_EMPTY_OK(n_cell);

@@ -1814,11 +1814,13 @@ def _event_slabs(table, n_outer: int, x: torch.Tensor, slab: int, extra: int,
   return table
 
 
-def _event_operands(ens, member_stride, n_member, truth, thresholds, thr_slabs,
-                    n_outer, n_row, n_col):
-  """The operand checks of the event front ends (K18 counts, K19 codes):
-  (thresholds, thr_slabs, n_member, n_outer, n_row, n_col, member_stride) as
-  lists and ints."""
+def _event_front(ens, member_stride, n_member, ens_slab, truth, truth_slab,
+                 thresholds, thr_slabs, n_outer, n_row, n_col):
+  """The preparation of the event front ends (K18 counts, K19 codes): the
+  operand checks, then the HOST slab tables, checked against the operands'
+  storage (`_event_slabs`) and uploaded.  ((n_threshold, n_member, n_outer,
+  n_row, n_col) as ints, the leading C arguments that wb2_event_counts and
+  wb2_event_codes share -- None where there is no point: nothing to upload)."""
   thresholds = list(thresholds)
   if not thresholds:
     raise ValueError('no thresholds')
@@ -1834,39 +1836,28 @@ def _event_operands(ens, member_stride, n_member, truth, thresholds, thr_slabs,
       thresholds)
   if len(thr_slabs) != len(thresholds):
     raise ValueError('one slab table (or None) per threshold')
-  return (thresholds, thr_slabs, n_member, n_outer, n_row, n_col,
-          member_stride)
-
-
-def _event_tables(ens, member_stride, n_member, ens_slab, truth, truth_slab,
-                  thresholds, thr_slabs, n_outer, slab):
-  """The HOST slab tables of an event front end, checked against the
-  operands' storage (`_event_slabs`): (member, truth, [threshold]) tables."""
+  slab = n_row * n_col
   es = _event_slabs(ens_slab, n_outer, ens, slab,
                     (max(n_member, 1) - 1) * member_stride, 'member')
   ts = _event_slabs(truth_slab, n_outer, truth, slab, 0, 'truth')
   hs = [_event_slabs(tb, n_outer, x, slab, 0, 'threshold')
         for tb, x in zip(thr_slabs, thresholds)]
-  return es, ts, hs
-
-
-def _event_args(ens, es, truth, ts, thresholds, hs, n_member, member_stride,
-                n_outer, n_row, n_col) -> tuple:
-  """The leading C arguments that wb2_event_counts and wb2_event_codes share,
-  the tables uploaded."""
+  sizes = (len(thresholds), n_member, n_outer, n_row, n_col)
+  if slab * n_outer == 0:
+    return sizes, None
   dev = ens.device
   hs_dev = None
   if any(tb is not None for tb in hs):
     ident = np.arange(n_outer, dtype=np.int64)
     hs_dev = upload_table(np.stack([ident if tb is None else tb
                                     for tb in hs]), dev)
-  return (dtype_code(ens.dtype),
-          _lib.ptr(ens), _lib.ptr(None if es is None else
-                                  upload_table(es, dev)),
-          _lib.ptr(truth), _lib.ptr(None if ts is None else
-                                    upload_table(ts, dev)),
-          _lib.ptr_array(thresholds), _lib.ptr(hs_dev), len(thresholds),
-          n_member, member_stride, n_outer, n_row, n_col)
+  return sizes, (dtype_code(ens.dtype),
+                 _lib.ptr(ens), _lib.ptr(None if es is None else
+                                         upload_table(es, dev)),
+                 _lib.ptr(truth), _lib.ptr(None if ts is None else
+                                           upload_table(ts, dev)),
+                 _lib.ptr_array(thresholds), _lib.ptr(hs_dev), len(thresholds),
+                 n_member, member_stride, n_outer, n_row, n_col)
 
 
 def _column_classes(col_class, n_col: int, n_class: int) -> np.ndarray:
@@ -1892,24 +1883,17 @@ def event_counts(ens: torch.Tensor, member_stride: int, n_member: int,
   [0, n_class)) are HOST sequences, None = identity; all of them are checked
   here against the operands' storage: the kernel trusts them.  Up to 4
   thresholds share one read of the members; the C side splits the rest."""
-  (thresholds, thr_slabs, n_member, n_outer, n_row, n_col,
-   member_stride) = _event_operands(ens, member_stride, n_member, truth,
-                                    thresholds, thr_slabs, n_outer, n_row,
-                                    n_col)
+  (n_thr, n_member, n_outer, n_row, n_col), args = _event_front(
+      ens, member_stride, n_member, ens_slab, truth, truth_slab, thresholds,
+      thr_slabs, n_outer, n_row, n_col)
   dev = ens.device
   n_class = int(n_class)
-  slab = n_row * n_col
-  n_code = 2 * (n_member + 1) + 1
-  out = torch.empty((len(thresholds), n_outer, n_row, n_class, n_code),
+  out = torch.empty((n_thr, n_outer, n_row, n_class, 2 * (n_member + 1) + 1),
                     dtype=torch.int32, device=dev)
   cls = _column_classes(col_class, n_col, n_class)
-  es, ts, hs = _event_tables(ens, member_stride, n_member, ens_slab, truth,
-                             truth_slab, thresholds, thr_slabs, n_outer, slab)
-  if slab * n_outer == 0:  # no points: nothing to count
+  if args is None:  # no points: nothing to count
     return out.zero_()
-  _launch('event_counts', 'wb2_event_counts',
-          *_event_args(ens, es, truth, ts, thresholds, hs, n_member,
-                       member_stride, n_outer, n_row, n_col),
+  _launch('event_counts', 'wb2_event_counts', *args,
           _lib.ptr(_upload_i32(cls.astype(np.int32), dev)), n_class,
           _lib.ptr(out), current_stream_ptr(dev))
   return out
@@ -1951,22 +1935,15 @@ def event_codes(ens: torch.Tensor, member_stride: int, n_member: int, ens_slab,
   k | observed << 8 | invalid << 9 of every point (k = the members exceeding;
   k = observed = 0 where the truth or a member is NaN).  The operands, the
   slab tables and their checks are those of `event_counts`."""
-  (thresholds, thr_slabs, n_member, n_outer, n_row, n_col,
-   member_stride) = _event_operands(ens, member_stride, n_member, truth,
-                                    thresholds, thr_slabs, n_outer, n_row,
-                                    n_col)
+  (n_thr, _, n_outer, n_row, n_col), args = _event_front(
+      ens, member_stride, n_member, ens_slab, truth, truth_slab, thresholds,
+      thr_slabs, n_outer, n_row, n_col)
   dev = ens.device
-  slab = n_row * n_col
-  out = torch.empty((len(thresholds), n_outer, n_row, n_col),
-                    dtype=torch.uint16, device=dev)
-  es, ts, hs = _event_tables(ens, member_stride, n_member, ens_slab, truth,
-                             truth_slab, thresholds, thr_slabs, n_outer, slab)
-  if slab * n_outer == 0:  # no points
-    return out
-  _launch('event_codes', 'wb2_event_codes',
-          *_event_args(ens, es, truth, ts, thresholds, hs, n_member,
-                       member_stride, n_outer, n_row, n_col),
-          _lib.ptr(out), current_stream_ptr(dev))
+  out = torch.empty((n_thr, n_outer, n_row, n_col), dtype=torch.uint16,
+                    device=dev)
+  if args is not None:  # (no points: no codes)
+    _launch('event_codes', 'wb2_event_codes', *args, _lib.ptr(out),
+            current_stream_ptr(dev))
   return out
 
 

@@ -102,6 +102,30 @@ def column_classes(regions: t.Mapping[str, t.Any], latitude, longitude):
 # ---------------------------------------------------------------------------
 # the host path: same integers, same fold order
 # ---------------------------------------------------------------------------
+def host_exceedance(ens: np.ndarray, member_stride: int, n_member: int,
+                    ens_slab, truth: np.ndarray, truth_slab, thresholds,
+                    thr_slabs, n_outer: int, slab: int):
+  """The per-point definition on the host, from the leading arguments of
+  `engine.event_counts` (host arrays): yields (threshold index, outer index,
+  k, obs, bad) over the `slab` points of every slab."""
+  ens, truth = ens.reshape(-1), truth.reshape(-1)
+  thr_slabs = thr_slabs if thr_slabs is not None else [None] * len(thresholds)
+  at = lambda table, o: o if table is None else int(table[o])
+  for o in range(n_outer):
+    e0 = at(ens_slab, o) * slab
+    x = np.stack([ens[e0 + m * member_stride:e0 + m * member_stride + slab]
+                  for m in range(n_member)])
+    t0 = at(truth_slab, o) * slab
+    tv = truth[t0:t0 + slab]
+    bad = np.isnan(tv) | np.isnan(x).any(axis=0)
+    for ti, (thr, table) in enumerate(zip(thresholds, thr_slabs)):
+      h0 = at(table, o) * slab
+      hv = thr.reshape(-1)[h0:h0 + slab]
+      with np.errstate(invalid='ignore'):
+        k, obs = (x > hv[None]).sum(axis=0), tv > hv
+      yield ti, o, k, obs, bad
+
+
 def host_counts(ens: np.ndarray, member_stride: int, n_member: int, ens_slab,
                 truth: np.ndarray, truth_slab, thresholds, thr_slabs,
                 n_outer: int, n_row: int, n_col: int, col_class,
@@ -110,31 +134,17 @@ def host_counts(ens: np.ndarray, member_stride: int, n_member: int, ens_slab,
   arrays instead of tensors), the same int32 [n_threshold, n_outer, n_row,
   n_class, n_code] result."""
   n_code = n_codes(n_member)
-  slab = n_row * n_col
-  ens, truth = ens.reshape(-1), truth.reshape(-1)
-  thr_slabs = thr_slabs if thr_slabs is not None else [None] * len(thresholds)
   out = np.zeros((len(thresholds), n_outer, n_row, n_class, n_code),
                  dtype=np.int32)
   cls = np.asarray(col_class, dtype=np.int64)
   bin0 = ((np.arange(n_row)[:, None] * n_class + cls[None, :]) * n_code
           ).reshape(-1)
-  at = lambda table, o: o if table is None else int(table[o])
-  with np.errstate(invalid='ignore'):
-    for o in range(n_outer):
-      e0 = at(ens_slab, o) * slab
-      x = np.stack([ens[e0 + m * member_stride:e0 + m * member_stride + slab]
-                    for m in range(n_member)])
-      t0 = at(truth_slab, o) * slab
-      tv = truth[t0:t0 + slab]
-      bad = np.isnan(tv) | np.isnan(x).any(axis=0)
-      for ti, (thr, table) in enumerate(zip(thresholds, thr_slabs)):
-        h0 = at(table, o) * slab
-        hv = thr.reshape(-1)[h0:h0 + slab]
-        k = (x > hv[None]).sum(axis=0)
-        code = np.where(bad, 2 * (n_member + 1),
-                        (tv > hv) * (n_member + 1) + k)
-        out[ti, o] = np.bincount(bin0 + code, minlength=n_row * n_class *
-                                 n_code).reshape(n_row, n_class, n_code)
+  for ti, o, k, obs, bad in host_exceedance(
+      ens, member_stride, n_member, ens_slab, truth, truth_slab, thresholds,
+      thr_slabs, n_outer, n_row * n_col):
+    code = np.where(bad, 2 * (n_member + 1), obs * (n_member + 1) + k)
+    out[ti, o] = np.bincount(bin0 + code, minlength=n_row * n_class *
+                             n_code).reshape(n_row, n_class, n_code)
   return out
 
 
@@ -194,6 +204,12 @@ class _Operands:
   @property
   def n_outer(self) -> int:
     return int(np.prod(self.out_shape, dtype=np.int64))
+
+  def front(self, n_row: int, n_col: int) -> tuple:
+    """The leading arguments of `engine.event_counts` and `event_codes`."""
+    return (self.arrays[0], self.member_stride, self.n_member, self.tables[0],
+            self.arrays[1], self.tables[1], self.arrays[2:], self.tables[2:],
+            self.n_outer, n_row, n_col)
 
 
 def _intact_strides(x: torch.Tensor, slab: int) -> t.Optional[tuple]:
@@ -308,9 +324,7 @@ def _region_tables(ops: _Operands, n_row: int, n_col: int, col_class,
                    mult, wrow) -> np.ndarray:
   """float64 [n_threshold, n_outer, n_region, n_code] on the host, through
   K18 for device operands and through NumPy for host ones."""
-  args = (ops.arrays[0], ops.member_stride, ops.n_member, ops.tables[0],
-          ops.arrays[1], ops.tables[1], ops.arrays[2:], ops.tables[2:],
-          ops.n_outer, n_row, n_col, col_class, mult.shape[1])
+  args = ops.front(n_row, n_col) + (col_class, mult.shape[1])
   if ops.device is None:
     return host_fold(host_counts(*args), wrow, mult)
   table = engine.event_fold(engine.event_counts(*args), wrow, mult)
@@ -321,8 +335,105 @@ def _region_tables(ops: _Operands, n_row: int, n_col: int, col_class,
 # ---------------------------------------------------------------------------
 # the metric
 # ---------------------------------------------------------------------------
+class ExceedanceTable(ThresholdMetric):
+  """What the tables over the per-point exceedance share (`EventTable`,
+  `neighborhood.FractionsTable`): the operands of every common variable, the
+  checks on the ensemble, the forecast-led order of the outer dims, the
+  `region` / `quantile` coords and the attrs.  A subclass states its noun, the
+  dims around the outer ones, its checks before the loop (`_setup`) and
+
+    _values(ops, n_row, n_col, col_class, mult, wrow, skipna, setup)
+        one variable: [n_threshold, <lead dims>, n_outer, n_region, <trailing
+        dims>]
+    _extra_coords(n_member, setup)
+        {dim: coord} of the lead and trailing dims, in that order."""
+
+  ensemble_dim = _m.REALIZATION  # (a dataclass field of each subclass)
+  # one pass over the points answers every region; no windows of chunks
+  _fused_regions = True
+  _reads_slabs_in_place = False
+  _noun = 'exceedance table'
+  # the dims of a result: [region,] quantile, lead, <outer dims>, trailing
+  _lead_dims = ()
+  _trailing_dims = ()
+
+  def _ensemble_size(self, forecast) -> int:
+    if self.ensemble_dim is not None and self.ensemble_dim in forecast.dims:
+      return int(forecast.sizes[self.ensemble_dim])
+    return 1
+
+  def _result_attrs(self, forecast):
+    return {'ensemble_size': self._ensemble_size(forecast)}
+
+  def _setup(self, lat, lon, mult, wrow):
+    """The checks before the loop over the variables: (mult, wrow) as the
+    kernels get them and whatever `_values` and `_extra_coords` need."""
+    return mult, wrow, None
+
+  def compute_chunk(self, forecast, truth, region=None, skipna=False,
+                    regions: t.Optional[dict] = None):
+    forecast, truth = _m._inputs(forecast, truth)
+    if not self.thresholds:
+      raise ValueError(f'{type(self).__name__} needs at least one threshold')
+    region_set = regions if regions is not None else {'region': region}
+    lat = xl.coord_values(forecast, 'latitude')
+    lon = xl.coord_values(forecast, 'longitude')
+    col_class, mult, wrow = column_classes(region_set, lat, lon)
+    mult, wrow, setup = self._setup(lat, lon, mult, wrow)
+    threshold_ds = [xl.as_dataset(th.compute(truth))
+                    for th in self.thresholds]
+    out = xl.Dataset()
+    sizes = set()
+    per_var = {}
+    for name in _m._common_vars(forecast, truth):
+      fvar = forecast[name]
+      ops = _operands(forecast, fvar,
+                      [truth[name]] + [ds[name] for ds in threshold_ds],
+                      self.ensemble_dim)
+      if not 1 <= ops.n_member <= MAX_MEMBERS:
+        raise ValueError(f'{ops.n_member} members: the {self._noun} takes 1 '
+                         f'to {MAX_MEMBERS}')
+      sizes.add(ops.n_member)
+      v = self._values(ops, len(lat), len(lon), col_class, mult, wrow, skipna,
+                       setup)
+      first = 1 + len(self._lead_dims)
+      v = v.reshape(v.shape[:first] + ops.out_shape + v.shape[first + 1:])
+      # outer dims as xarray orders the plain Brier score (forecast-led)
+      fdims = tuple(d for d in fvar.dims if d in ops.out_dims)
+      order = []
+      for operand in (fdims, threshold_ds[0][name].dims, truth[name].dims):
+        order += [d for d in operand if d in ops.out_dims and d not in order]
+      # [T, lead.., outer.., R, trailing..] -> ([R,] T, lead.., outer.., ..)
+      at_region = first + len(ops.out_dims)
+      axes = (list(range(first)) +
+              [first + ops.out_dims.index(d) for d in order] +
+              list(range(at_region + 1, v.ndim)))
+      if regions is not None:
+        v = np.transpose(v, [at_region] + axes)
+      else:
+        v = np.transpose(v, axes + [at_region])[..., 0]
+      per_var[name] = (tuple(order), np.ascontiguousarray(v))
+      out.coords.update(_m._result_coords(forecast, tuple(order)))
+    if len(sizes) > 1:
+      raise ValueError(f'the variables differ in ensemble size: {sizes}')
+    n_member = sizes.pop() if sizes else self._ensemble_size(forecast)
+    front = ('region', 'quantile') if regions is not None else ('quantile',)
+    if regions is not None:
+      out.coords['region'] = np.array(list(regions), dtype=object)
+    out.coords['quantile'] = np.array(
+        [th.quantile for th in self.thresholds], dtype=np.float64)
+    out.coords.update(self._extra_coords(n_member, setup))
+    for name, (order, v) in per_var.items():
+      out.data_vars[name] = xl.DataArray(
+          v, front + self._lead_dims + order + self._trailing_dims, out.coords,
+          name)
+    return out.assign_attrs(
+        threshold_method=type(self.thresholds[0]).__name__,
+        ensemble_size=n_member)
+
+
 @dataclasses.dataclass
-class EventTable(ThresholdMetric):
+class EventTable(ExceedanceTable):
   """Joint exceedance table of a forecast against climatological thresholds.
 
   Per common variable the result is p with dims ('quantile', <outer dims in
@@ -339,81 +450,29 @@ class EventTable(ThresholdMetric):
   """
 
   ensemble_dim: t.Optional[str] = _m.REALIZATION
-  # one counting pass answers every region; no windows of chunks
-  _fused_regions = True
-  _reads_slabs_in_place = False
+  _noun = 'event table'
+  _trailing_dims = (OBSERVED, EXCEEDING)
 
-  def _ensemble_size(self, forecast) -> int:
-    if self.ensemble_dim is not None and self.ensemble_dim in forecast.dims:
-      return int(forecast.sizes[self.ensemble_dim])
-    return 1
+  def _values(self, ops, n_row, n_col, col_class, mult, wrow, skipna, setup):
+    table = _region_tables(ops, n_row, n_col, col_class, mult, wrow)
+    return normalize(table, ops.n_member, skipna)  # [T, outer, R, 2, M + 1]
 
-  def _result_attrs(self, forecast):
-    return {'ensemble_size': self._ensemble_size(forecast)}
-
-  def compute_chunk(self, forecast, truth, region=None, skipna=False,
-                    regions: t.Optional[dict] = None):
-    forecast, truth = _m._inputs(forecast, truth)
-    if not self.thresholds:
-      raise ValueError('EventTable needs at least one threshold')
-    region_set = regions if regions is not None else {'region': region}
-    lat = xl.coord_values(forecast, 'latitude')
-    lon = xl.coord_values(forecast, 'longitude')
-    col_class, mult, wrow = column_classes(region_set, lat, lon)
-    threshold_ds = [xl.as_dataset(th.compute(truth))
-                    for th in self.thresholds]
-    out = xl.Dataset()
-    sizes = set()
-    per_var = {}
-    for name in _m._common_vars(forecast, truth):
-      fvar = forecast[name]
-      ops = _operands(forecast, fvar,
-                      [truth[name]] + [ds[name] for ds in threshold_ds],
-                      self.ensemble_dim)
-      if not 1 <= ops.n_member <= MAX_MEMBERS:
-        raise ValueError(f'{ops.n_member} members: the event table takes 1 '
-                         f'to {MAX_MEMBERS}')
-      sizes.add(ops.n_member)
-      table = _region_tables(ops, len(lat), len(lon), col_class, mult, wrow)
-      p = normalize(table, ops.n_member, skipna)  # [T, outer, R, 2, M + 1]
-      p = p.reshape((p.shape[0],) + ops.out_shape + p.shape[2:])
-      # outer dims as xarray orders the plain Brier score (forecast-led)
-      fdims = tuple(d for d in fvar.dims if d in ops.out_dims)
-      order = []
-      for operand in (fdims, threshold_ds[0][name].dims, truth[name].dims):
-        order += [d for d in operand if d in ops.out_dims and d not in order]
-      n_out = len(ops.out_dims)
-      axes = [1 + ops.out_dims.index(d) for d in order]
-      if regions is not None:
-        p = np.transpose(p, [1 + n_out, 0] + axes + [2 + n_out, 3 + n_out])
-        dims = ('region', 'quantile') + tuple(order) + (OBSERVED, EXCEEDING)
-      else:
-        p = np.transpose(p[..., 0, :, :], [0] + axes + [1 + n_out, 2 + n_out])
-        dims = ('quantile',) + tuple(order) + (OBSERVED, EXCEEDING)
-      per_var[name] = (dims, np.ascontiguousarray(p))
-      out.coords.update(_m._result_coords(forecast, tuple(order)))
-    if len(sizes) > 1:
-      raise ValueError(f'the variables differ in ensemble size: {sizes}')
-    n_member = sizes.pop() if sizes else self._ensemble_size(forecast)
-    if regions is not None:
-      out.coords['region'] = np.array(list(regions), dtype=object)
-    out.coords['quantile'] = np.array(
-        [th.quantile for th in self.thresholds], dtype=np.float64)
-    out.coords[OBSERVED] = np.array([0, 1], dtype=np.int64)
-    out.coords[EXCEEDING] = np.arange(n_member + 1, dtype=np.int64)
-    for name, (dims, p) in per_var.items():
-      out.data_vars[name] = xl.DataArray(p, dims, out.coords, name)
-    return out.assign_attrs(
-        threshold_method=type(self.thresholds[0]).__name__,
-        ensemble_size=n_member)
+  def _extra_coords(self, n_member, setup):
+    return {OBSERVED: np.array([0, 1], dtype=np.int64),
+            EXCEEDING: np.arange(n_member + 1, dtype=np.int64)}
 
 
 # ---------------------------------------------------------------------------
 # scores: host arithmetic over the last two dims of a table
 # ---------------------------------------------------------------------------
-def _per_table(fn):
+def _per_table(fn, trailing=((OBSERVED, 2), (EXCEEDING, None)),
+               noun='an event table'):
   """`fn(p, lead dims, coords)` over a table DataArray, or over every variable
-  of a table Dataset ({name: result} where a result is itself a Dataset)."""
+  of a table Dataset ({name: result} where a result is itself a Dataset).
+  `trailing`: the (dim, size or None) pairs a table ends with, which are
+  checked and left to `fn`; `noun` names the table in the error."""
+  n_trail = len(trailing)
+
   def wrapper(table, *args, **kwargs):
     if xl.is_xarray(table):
       table = (xl.from_xarray(table) if hasattr(table, 'data_vars') else
@@ -422,15 +481,18 @@ def _per_table(fn):
                              for k in table.dims if k in table.coords},
                             table.name))
     def one(da):
-      if tuple(da.dims[-2:]) != (OBSERVED, EXCEEDING) or da.shape[-2] != 2:
-        raise ValueError(f'not an event table: dims {da.dims}')
+      lead = tuple(da.dims[:-n_trail])
+      if tuple(da.dims[-n_trail:]) != tuple(d for d, _ in trailing) or any(
+          n is not None and da.shape[i - n_trail] != n
+          for i, (_, n) in enumerate(trailing)):
+        raise ValueError(f'not {noun}: dims {da.dims}')
       p = np.asarray(da.values, dtype=np.float64)
       coords = {k: c for k, c in da.coords.items() if
                 (isinstance(c, xl.DataArray) and
-                 all(d in da.dims[:-2] for d in c.dims)) or
-                (not isinstance(c, xl.DataArray) and k in da.dims[:-2])}
+                 all(d in lead for d in c.dims)) or
+                (not isinstance(c, xl.DataArray) and k in lead)}
       with np.errstate(all='ignore'):
-        return fn(p, tuple(da.dims[:-2]), coords, *args, **kwargs)
+        return fn(p, lead, coords, *args, **kwargs)
     if isinstance(table, xl.DataArray):
       return one(table)
     results = {name: one(da) for name, da in table.items()}

@@ -97,11 +97,8 @@ from weatherbench2_amd import events
 from weatherbench2_amd import metrics as _m
 from weatherbench2_amd import thresholds as thresholds_lib
 from weatherbench2_amd import xarray_lite as xl
-from weatherbench2_amd.metrics import ThresholdMetric
 
-MAX_MEMBERS = 128  # limits of K19
-MAX_CLASSES = 64
-MAX_WINDOW = 255
+MAX_WINDOW = 255  # (members and classes: events.MAX_MEMBERS, MAX_CLASSES)
 N_SUMS = 6
 NEIGHBORHOOD, COMPONENT = 'neighborhood', 'component'
 COMPONENTS = ('fbs', 'fbs_reference', 'forecast_fraction',
@@ -117,25 +114,12 @@ def host_codes(ens: np.ndarray, member_stride: int, n_member: int, ens_slab,
                n_outer: int, n_row: int, n_col: int) -> np.ndarray:
   """`engine.event_codes` in NumPy: the same arguments (contiguous host arrays
   instead of tensors), the same uint16 [n_threshold, n_outer, n_row, n_col]."""
-  slab = n_row * n_col
-  ens, truth = ens.reshape(-1), truth.reshape(-1)
-  thr_slabs = thr_slabs if thr_slabs is not None else [None] * len(thresholds)
   out = np.zeros((len(thresholds), n_outer, n_row, n_col), dtype=np.uint16)
-  at = lambda table, o: o if table is None else int(table[o])
-  with np.errstate(invalid='ignore'):
-    for o in range(n_outer):
-      e0 = at(ens_slab, o) * slab
-      x = np.stack([ens[e0 + m * member_stride:e0 + m * member_stride + slab]
-                    for m in range(n_member)])
-      t0 = at(truth_slab, o) * slab
-      tv = truth[t0:t0 + slab]
-      bad = np.isnan(tv) | np.isnan(x).any(axis=0)
-      for ti, (thr, table) in enumerate(zip(thresholds, thr_slabs)):
-        h0 = at(table, o) * slab
-        hv = thr.reshape(-1)[h0:h0 + slab]
-        k = (x > hv[None]).sum(axis=0)
-        code = np.where(bad, CODE_INVALID, k | (tv > hv) * CODE_OBSERVED)
-        out[ti, o] = code.reshape(n_row, n_col)
+  for ti, o, k, obs, bad in events.host_exceedance(
+      ens, member_stride, n_member, ens_slab, truth, truth_slab, thresholds,
+      thr_slabs, n_outer, n_row * n_col):
+    code = np.where(bad, CODE_INVALID, k | obs * CODE_OBSERVED)
+    out[ti, o] = code.reshape(n_row, n_col)
   return out
 
 
@@ -275,9 +259,7 @@ def _region_tables(ops, n_row: int, n_col: int, windows, col_class, mult,
                    wrow) -> np.ndarray:
   """float64 [n_threshold * n_outer, n_window, n_region, 6] on the host,
   through K19 for device operands and through NumPy for host ones."""
-  front = (ops.arrays[0], ops.member_stride, ops.n_member, ops.tables[0],
-           ops.arrays[1], ops.tables[1], ops.arrays[2:], ops.tables[2:],
-           ops.n_outer, n_row, n_col)
+  front = ops.front(n_row, n_col)
   w = window_weights(wrow, ops.n_member, windows)
   n_class = mult.shape[1]
   if ops.device is None:
@@ -292,7 +274,7 @@ def _region_tables(ops, n_row: int, n_col: int, windows, col_class, mult,
 
 
 @dataclasses.dataclass
-class FractionsTable(ThresholdMetric):
+class FractionsTable(events.ExceedanceTable):
   """Neighbourhood fractions of a forecast against thresholds, the sufficient
   statistics of the fractions skill score.
 
@@ -311,82 +293,29 @@ class FractionsTable(ThresholdMetric):
 
   neighborhoods: t.Sequence[int] = (1, 3, 5, 9, 17)
   ensemble_dim: t.Optional[str] = _m.REALIZATION
-  # one walk answers every region; no windows of chunks
-  _fused_regions = True
-  _reads_slabs_in_place = False
+  _noun = 'fractions table'
+  _lead_dims = (NEIGHBORHOOD,)
+  _trailing_dims = (COMPONENT,)
 
-  def _ensemble_size(self, forecast) -> int:
-    if self.ensemble_dim is not None and self.ensemble_dim in forecast.dims:
-      return int(forecast.sizes[self.ensemble_dim])
-    return 1
-
-  def _result_attrs(self, forecast):
-    return {'ensemble_size': self._ensemble_size(forecast)}
-
-  def compute_chunk(self, forecast, truth, region=None, skipna=False,
-                    regions: t.Optional[dict] = None):
-    forecast, truth = _m._inputs(forecast, truth)
-    if not self.thresholds:
-      raise ValueError('FractionsTable needs at least one threshold')
-    region_set = regions if regions is not None else {'region': region}
-    lat = xl.coord_values(forecast, 'latitude')
-    lon = xl.coord_values(forecast, 'longitude')
-    n_row, n_col = len(lat), len(lon)
-    windows = _check_windows(self.neighborhoods, n_col)
+  def _setup(self, lat, lon, mult, wrow):
+    windows = _check_windows(self.neighborhoods, len(lon))
     _check_cyclic(lon)
-    col_class, mult, wrow = events.column_classes(region_set, lat, lon)
     # the pseudo-region: its q5 is the slab's number of valid centres
     mult = np.concatenate([mult, np.ones((1, mult.shape[1]), np.int32)])
-    wrow = np.concatenate([wrow, np.ones((1, n_row), np.float64)])
-    threshold_ds = [xl.as_dataset(th.compute(truth))
-                    for th in self.thresholds]
-    out = xl.Dataset()
-    sizes = set()
-    per_var = {}
-    for name in _m._common_vars(forecast, truth):
-      fvar = forecast[name]
-      ops = events._operands(forecast, fvar,
-                             [truth[name]] + [ds[name] for ds in threshold_ds],
-                             self.ensemble_dim)
-      if not 1 <= ops.n_member <= MAX_MEMBERS:
-        raise ValueError(f'{ops.n_member} members: the fractions table takes '
-                         f'1 to {MAX_MEMBERS}')
-      _check_range(ops.n_member, windows, n_col, mult)
-      sizes.add(ops.n_member)
-      table = _region_tables(ops, n_row, n_col, windows, col_class, mult, wrow)
-      c = components(table, n_row * n_col, skipna)  # [T * outer, W, R, 4]
-      c = c.reshape((len(threshold_ds),) + ops.out_shape + c.shape[1:])
-      # outer dims as xarray orders the plain Brier score (forecast-led)
-      fdims = tuple(d for d in fvar.dims if d in ops.out_dims)
-      order = []
-      for operand in (fdims, threshold_ds[0][name].dims, truth[name].dims):
-        order += [d for d in operand if d in ops.out_dims and d not in order]
-      n_out = len(ops.out_dims)
-      axes = [1 + ops.out_dims.index(d) for d in order]
-      # [T, outer..., W, R, 4] -> ([R,] T, W, outer..., 4)
-      if regions is not None:
-        c = np.transpose(c, [2 + n_out, 0, 1 + n_out] + axes + [3 + n_out])
-        dims = ('region', 'quantile', NEIGHBORHOOD) + tuple(order) + (
-            COMPONENT,)
-      else:
-        c = np.transpose(c[..., 0, :], [0, 1 + n_out] + axes + [2 + n_out])
-        dims = ('quantile', NEIGHBORHOOD) + tuple(order) + (COMPONENT,)
-      per_var[name] = (dims, np.ascontiguousarray(c))
-      out.coords.update(_m._result_coords(forecast, tuple(order)))
-    if len(sizes) > 1:
-      raise ValueError(f'the variables differ in ensemble size: {sizes}')
-    n_member = sizes.pop() if sizes else self._ensemble_size(forecast)
-    if regions is not None:
-      out.coords['region'] = np.array(list(regions), dtype=object)
-    out.coords['quantile'] = np.array(
-        [th.quantile for th in self.thresholds], dtype=np.float64)
-    out.coords[NEIGHBORHOOD] = np.array(windows, dtype=np.int64)
-    out.coords[COMPONENT] = np.array(COMPONENTS, dtype=object)
-    for name, (dims, c) in per_var.items():
-      out.data_vars[name] = xl.DataArray(c, dims, out.coords, name)
-    return out.assign_attrs(
-        threshold_method=type(self.thresholds[0]).__name__,
-        ensemble_size=n_member)
+    wrow = np.concatenate([wrow, np.ones((1, len(lat)), np.float64)])
+    return mult, wrow, windows
+
+  def _values(self, ops, n_row, n_col, col_class, mult, wrow, skipna,
+              windows):
+    _check_range(ops.n_member, windows, n_col, mult)
+    table = _region_tables(ops, n_row, n_col, windows, col_class, mult, wrow)
+    c = components(table, n_row * n_col, skipna)  # [T * outer, W, R, 4]
+    c = c.reshape((len(self.thresholds), ops.n_outer) + c.shape[1:])
+    return np.moveaxis(c, 2, 1)  # [T, W, outer, R, 4]
+
+  def _extra_coords(self, n_member, windows):
+    return {NEIGHBORHOOD: np.array(windows, dtype=np.int64),
+            COMPONENT: np.array(COMPONENTS, dtype=object)}
 
 
 # ---------------------------------------------------------------------------
@@ -450,34 +379,9 @@ class ConstantThreshold(thresholds_lib.Threshold):
 # scores: host arithmetic over the last dim of a table
 # ---------------------------------------------------------------------------
 def _per_table(fn):
-  """`fn(c, lead dims, coords)` over a fractions table DataArray, or over
-  every variable of a table Dataset: the conventions of `events._per_table`."""
-  def wrapper(table, *args, **kwargs):
-    if xl.is_xarray(table):
-      table = (xl.from_xarray(table) if hasattr(table, 'data_vars') else
-               xl.DataArray(table.values, tuple(table.dims),
-                            {k: np.asarray(table.coords[k].values)
-                             for k in table.dims if k in table.coords},
-                            table.name))
-    def one(da):
-      if da.dims[-1] != COMPONENT or da.shape[-1] != len(COMPONENTS):
-        raise ValueError(f'not a fractions table: dims {da.dims}')
-      c = np.asarray(da.values, dtype=np.float64)
-      coords = {k: v for k, v in da.coords.items() if
-                (isinstance(v, xl.DataArray) and
-                 all(d in da.dims[:-1] for d in v.dims)) or
-                (not isinstance(v, xl.DataArray) and k in da.dims[:-1])}
-      with np.errstate(all='ignore'):
-        return fn(c, tuple(da.dims[:-1]), coords, *args, **kwargs)
-    if isinstance(table, xl.DataArray):
-      return one(table)
-    results = {name: one(da) for name, da in table.items()}
-    coords = {}
-    for r in results.values():
-      coords.update(r.coords)
-    return xl.Dataset(results, coords, table.attrs)
-  wrapper.__name__, wrapper.__doc__ = fn.__name__, fn.__doc__
-  return wrapper
+  """`events._per_table` for a fractions table: `fn(c, lead dims, coords)`."""
+  return events._per_table(fn, ((COMPONENT, len(COMPONENTS)),),
+                           'a fractions table')
 
 
 def _fss(c):

@@ -1730,6 +1730,89 @@ int wb2_fss_fold(const int64_t* sums, int64_t n_cell, int32_t n_window,
                  const int32_t* mult, int32_t n_region, double* table,
                  void* stream);
 
+/*
+ * K20: the per-rank-bin sums of Hersbach's CRPS decomposition (Wea.
+ * Forecasting 2000): reliability, potential CRPS, the bin widths g_i and the
+ * observed frequencies o_i are host arithmetic on them.  The reference has the
+ * CRPS (metrics.py:760-830) and no counterpart of the decomposition.
+ *
+ * One point with truth y and the members sorted x_1 <= ... <= x_M, all
+ * arithmetic in float64 after an exact widening, bins b = 0 .. M:
+ *   b = 0:      alpha = 0,                    beta = max(x_1 - y, 0)
+ *   b = M:      alpha = max(y - x_M, 0),      beta = 0
+ *   0 < b < M:  c = min(max(y, x_b), x_{b+1}), alpha = c - x_b,
+ *               beta = x_{b+1} - c
+ *   below = y < x_1, above = y > x_M (strict: a tie is no outlier).
+ * The point is invalid iff the truth or any member is NaN (K18's rule).
+ * Points that hold +-inf are not pinned.
+ *
+ * wb2_crps_bin_sums: K18's operands and slab-table convention (ens, ens_slab,
+ * truth, truth_slab, n_member, member_stride, n_outer; tables DEV int64, null
+ * = identity; col_class DEV int32[n_col] with values in [0, n_class); every
+ * table value the caller's to check).  With n_bin = n_member + 1,
+ *   sums[o][i][c][0][b], sums[o][i][c][1][b] (DEV float64, every element
+ *     written) = the sums of alpha_b and beta_b over the valid points of the
+ *     columns j with col_class[j] == c in row i of outer index o,
+ *   cnt[o][i][c][0..2] (DEV int32, every element written) = the numbers of
+ *     those points with `below`, with `above`, and of all of them.  (The
+ *     invalid count is the column count of the class minus cnt[..][2].)
+ * THE ORDER OF THE SUM of one (o, i, c, term, b): one sequential float64
+ * chain s = s + v from +0.0 over the valid points of the class in INCREASING
+ * COLUMN ORDER; an invalid point adds nothing.  It does not depend on the
+ * tile, on the other classes or on the launch: two runs are bit-equal, and a
+ * host loop over the columns reproduces the bits.
+ * One wave (a workgroup of its own: rows_per_group = 1) owns one row of one
+ * outer index and walks it in tiles of tile_cols = 64 columns.  Per tile a
+ * lane requests the truth and the n_member members of its point, all before
+ * any is looked at -- each element is read ONCE: (n_member + 1) elements per
+ * point --, sorts the members in registers (the networks of K3, +inf padding
+ * to the next power of two >= 2) and stores them and the truth in a
+ * wave-private LDS tile [n_bin][65].  Then lane b takes bin b (lane 0: beta_0
+ * and alpha_M, whose signs are the two outlier flags) and the wave walks the
+ * points of the tile in column order, eight at a time: each lane reads x_b,
+ * x_{b+1} and y of the eight from the tile, forms its alphas and betas and
+ * adds them to its running sums one after the other.  Where the class of the
+ * column changes (wave-uniform) the lane stores its sums to `sums` and takes
+ * up those of the new class -- read back from `sums` if the row met the class
+ * before, +0.0 otherwise.  Plain stores; no atomics at all.
+ * Checked before anything is enqueued, in this order: the dtype ("unknown
+ * dtype"), 1 <= n_member <= 64 ("n_member="), 1 <= n_class <= 64
+ * ("n_class="), a negative member_stride, negative sizes, null pointers
+ * ("null pointer") and the grid.  Zero n_outer, n_row or n_col is a no-op
+ * whatever the pointers are.
+ *
+ * wb2_crps_bins_geometry: min_member = 1, max_member = 64 (both dtypes),
+ * tile_cols = 64, rows_per_group = 1,
+ *   lds_bytes = (n_member + 1) * 65 * sizeof(element)   (at most 33800),
+ * max_grid_outer outer indices per grid row.  The same checks of dtype,
+ * n_member and n_class.
+ *
+ * wb2_crps_bin_fold: sums is [n_cell][n_row][n_class][n_slot] (n_slot =
+ * 2 n_bin), wrow DEV float64[n_region][n_row], mult DEV int32[n_region][
+ * n_class], and
+ *   table[cell][r][s] = sum_i wrow[r][i] *
+ *                       (sum_c (double)mult[r][c] * sums[cell][i][c][s])
+ * with the classes and then the rows in increasing order, both plain
+ * sequential float64 sums from +0.0 (t = t + m * v, acc = acc + wrow * t, no
+ * fused multiply-add): a fixed order.  One thread per output element: the
+ * simple path.  The counts go through wb2_event_fold (n_code = 3 or 4).  Zero
+ * n_cell or n_region is a no-op.
+ */
+int wb2_crps_bin_sums(int dtype, const void* ens, const int64_t* ens_slab,
+                      const void* truth, const int64_t* truth_slab,
+                      int32_t n_member, int64_t member_stride, int64_t n_outer,
+                      int32_t n_row, int32_t n_col, const int32_t* col_class,
+                      int32_t n_class, double* sums, int32_t* cnt,
+                      void* stream);
+int wb2_crps_bin_fold(const double* sums, int64_t n_cell, int32_t n_row,
+                      int32_t n_class, int32_t n_slot, const double* wrow,
+                      const int32_t* mult, int32_t n_region, double* table,
+                      void* stream);
+int wb2_crps_bins_geometry(int dtype, int32_t n_member, int32_t n_class,
+                           int32_t* min_member, int32_t* max_member,
+                           int32_t* tile_cols, int32_t* rows_per_group,
+                           int64_t* lds_bytes, int32_t* max_grid_outer);
+
 #ifdef __cplusplus
 }
 #endif

@@ -258,6 +258,15 @@ _SIGNATURES = {
         _c.POINTER(_i64), _c.POINTER(_i32)]),
     'wb2_fss_fold': (_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _vp,
                             _vp]),
+    'wb2_crps_bin_sums': (_int, [
+        _int, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _i32,
+        _vp, _vp, _vp]),
+    'wb2_crps_bin_fold': (_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _i32,
+                                 _vp, _vp]),
+    'wb2_crps_bins_geometry': (_int, [
+        _int, _i32, _i32, _c.POINTER(_i32), _c.POINTER(_i32),
+        _c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i64),
+        _c.POINTER(_i32)]),
 }
 
 _lib = None

@@ -1947,6 +1947,101 @@ def event_codes(ens: torch.Tensor, member_stride: int, n_member: int, ens_slab,
   return out
 
 
+def crps_bins_geometry(dtype: torch.dtype, n_member: int = 1,
+                       n_class: int = 1) -> dict:
+  """Extents of the K20 sums kernel: the member counts it takes
+  (`min_member` .. `max_member`), the `tile_cols` columns a wave sorts at a
+  time, `rows_per_group` = 1 (a row is one wave, a workgroup of its own), the
+  `lds_bytes` of its tile, `max_grid_outer` outer indices per grid row."""
+  return _geometry('wb2_crps_bins_geometry',
+                   (dtype_code(dtype), int(n_member), int(n_class)),
+                   [('min_member', _I32), ('max_member', _I32),
+                    ('tile_cols', _I32), ('rows_per_group', _I32),
+                    ('lds_bytes', ctypes.c_int64), ('max_grid_outer', _I32)])
+
+
+def crps_bin_sums(ens: torch.Tensor, member_stride: int, n_member: int,
+                  ens_slab, truth: torch.Tensor, truth_slab, n_outer: int,
+                  n_row: int, n_col: int, col_class, n_class: int) -> tuple:
+  """K20, wb2_crps_bin_sums: (float64 [n_outer, n_row, n_class, 2, n_member +
+  1] sums of alpha and beta, int32 [n_outer, n_row, n_class, 3] below / above /
+  valid counts) of the points of every (row, column class).  The operands,
+  the HOST slab tables and `col_class` are those of `event_counts`, checked
+  here against the operands' storage in the same way: the kernel trusts
+  them."""
+  _require_float(ens, truth)
+  _check_contiguous(ens.device, 'the device of the members', truth, view=ens)
+  n_member, n_outer, n_row, n_col, member_stride, n_class = (
+      int(v) for v in (n_member, n_outer, n_row, n_col, member_stride,
+                       n_class))
+  if min(n_outer, n_row, n_col) < 0 or member_stride < 0:
+    raise ValueError('bad sizes')
+  geo = crps_bins_geometry(ens.dtype, 1, 1)
+  if not geo['min_member'] <= n_member <= geo['max_member']:
+    raise ValueError(f'{n_member} members: the CRPS bin sums take '
+                     f"{geo['min_member']} to {geo['max_member']}")
+  slab = n_row * n_col
+  es = _event_slabs(ens_slab, n_outer, ens, slab,
+                    (n_member - 1) * member_stride, 'member')
+  ts = _event_slabs(truth_slab, n_outer, truth, slab, 0, 'truth')
+  cls = _column_classes(col_class, n_col, n_class)
+  dev = ens.device
+  sums = torch.empty((n_outer, n_row, n_class, 2, n_member + 1),
+                     dtype=torch.float64, device=dev)
+  cnt = torch.empty((n_outer, n_row, n_class, 3), dtype=torch.int32,
+                    device=dev)
+  if slab * n_outer == 0:  # no points: nothing to add
+    return sums.zero_(), cnt.zero_()
+  _launch('crps_bin_sums', 'wb2_crps_bin_sums', dtype_code(ens.dtype),
+          _lib.ptr(ens), _lib.ptr(None if es is None else
+                                  upload_table(es, dev)),
+          _lib.ptr(truth), _lib.ptr(None if ts is None else
+                                    upload_table(ts, dev)),
+          n_member, member_stride, n_outer, n_row, n_col,
+          _lib.ptr(_upload_i32(cls.astype(np.int32), dev)), n_class,
+          _lib.ptr(sums), _lib.ptr(cnt), current_stream_ptr(dev))
+  return sums, cnt
+
+
+def crps_bin_fold(sums: torch.Tensor, cnt: torch.Tensor, class_cols, wrow,
+                  mult) -> tuple:
+  """(float64 [n_outer, n_region, 2, n_bin], float64 [n_outer, n_region, 4]):
+  wb2_crps_bin_fold of the sums -- sum_i wrow[r, i] * (sum_c float(mult[r, c])
+  * sums[o, i, c]), classes then rows in increasing order, plain float64 -- and
+  wb2_event_fold of the counts (below, above, valid, invalid = `class_cols[c]`
+  - valid).  `class_cols` (columns per class), `wrow` (float64 [n_region,
+  n_row]) and `mult` (int32 [n_region, n_class]) are HOST arrays."""
+  if (sums.dtype != torch.float64 or sums.dim() != 5 or sums.shape[3] != 2 or
+      not sums.is_contiguous() or cnt.dtype != torch.int32 or
+      tuple(cnt.shape) != tuple(sums.shape[:3]) + (3,) or
+      not cnt.is_contiguous() or cnt.device != sums.device):
+    raise ValueError('sums must be a contiguous float64 [outer, row, class, '
+                     '2, bin] tensor and cnt its int32 [outer, row, class, 3]')
+  n_outer, n_row, n_class, _, n_bin = (int(n) for n in sums.shape)
+  wrow = np.ascontiguousarray(wrow, dtype=np.float64)
+  mult = np.ascontiguousarray(mult, dtype=np.int32)
+  n_region = wrow.shape[0] if wrow.ndim == 2 else -1
+  if wrow.shape != (n_region, n_row) or mult.shape != (n_region, n_class):
+    raise ValueError('wrow must be [n_region, n_row] and mult [n_region, '
+                     'n_class]')
+  cols = np.ascontiguousarray(class_cols, dtype=np.int32).reshape(-1)
+  if cols.size != n_class:
+    raise ValueError(f'class_cols must hold {n_class} column counts')
+  dev = sums.device
+  table = torch.empty((n_outer, n_region, 2, n_bin), dtype=torch.float64,
+                      device=dev)
+  if table.numel():
+    _launch('crps_bin_fold', 'wb2_crps_bin_fold', _lib.ptr(sums), n_outer,
+            n_row, n_class, 2 * n_bin,
+            _lib.ptr(upload_f64_table(wrow, dev) if wrow.size else None),
+            _lib.ptr(_upload_i32(mult.reshape(-1), dev)), n_region,
+            _lib.ptr(table), current_stream_ptr(dev))
+  invalid = _upload_i32(cols, dev)[:n_class].reshape(1, 1, n_class
+                                                      ) - cnt[..., 2]
+  cnt4 = torch.cat([cnt, invalid[..., None].to(torch.int32)], dim=-1)
+  return table, event_fold(cnt4[None].contiguous(), wrow, mult)[0]
+
+
 def fss_sums_geometry(n_col: int, n_class: int, n_window: int) -> dict:
   """Extents of the K19 box-sum kernel: a workgroup owns `rows_per_group` rows
   of one cell at full row width, `windows_per_launch` windows share one walk,

@@ -1813,6 +1813,93 @@ int wb2_crps_bins_geometry(int dtype, int32_t n_member, int32_t n_class,
                            int32_t* tile_cols, int32_t* rows_per_group,
                            int64_t* lds_bytes, int32_t* max_grid_outer);
 
+/*
+ * K21: the sums of the threshold-weighted CRPS (twCRPS; Gneiting & Ranjan
+ * 2011, in the chaining-function form of Allen, Ginsbourger & Ziegel 2023)
+ * with the tail weights 1[z >= t] (upper) and 1[z <= t] (lower).  The
+ * reference has the CRPS (metrics.py:760-830) and no counterpart.
+ *
+ * One point with truth y, the members sorted x_1 <= ... <= x_M and the
+ * threshold value t, all arithmetic in float64 after an exact widening:
+ *   v(z) = z < t ? t : z   (upper, lower == 0: max(z, t))
+ *   v(z) = z > t ? t : z   (lower != 0: min(z, t))
+ *   A = sum_{i=1..M} |v(x_i) - v(y)|, added in sorted-member order from +0.0
+ *   B = sum_{k=1..M-1} (double)(k (M - k)) * (v(x_{k+1}) - v(x_k)), added in
+ *       increasing k from +0.0, each product rounded before it is added (no
+ *       fused multiply-add); B = 0 for M = 1.  This is the gap form of
+ *       sum_{i<j} |v(x_i) - v(x_j)|: every term is >= 0, a gap wholly beyond
+ *       the threshold is exactly 0.
+ * twCRPS = A / M - B / M^2; the divisions are the caller's.  v is monotone, so
+ * one sort serves every threshold.  The point is invalid FOR THRESHOLD t iff
+ * the truth, any member or that threshold's value at the point is NaN (K18's
+ * rule, per threshold: it does not depend on how the thresholds are grouped
+ * into launches).  t = -inf (upper) and t = +inf (lower) are ordinary and give
+ * the plain CRPS terms; any other +-inf is not pinned.
+ *
+ * wb2_twcrps_sums: K18's operands and slab-table convention (ens, ens_slab,
+ * truth, truth_slab, a HOST array of n_threshold DEV threshold pointers,
+ * thr_slab[t * n_outer + o], n_member, member_stride, n_outer; tables DEV
+ * int64, null = identity; col_class DEV int32[n_col] with values in [0,
+ * n_class); every table value the caller's to check).
+ *   sums[t][o][i][c][0], sums[t][o][i][c][1] (DEV float64, every element
+ *     written) = the sums of A and of B over the points, valid for threshold
+ *     t, of the columns j with col_class[j] == c in row i of outer index o,
+ *   cnt[t][o][i][c] (DEV int32, every element written) = their number.  (The
+ *     invalid count is the column count of the class minus cnt.)
+ * Threshold-major: the folds below take n_cell = n_threshold * n_outer.
+ * THE ORDER OF THE SUM of one (t, o, i, c, term): one sequential float64 chain
+ * s = s + v from +0.0 over the points of the class in INCREASING COLUMN ORDER,
+ * where a point that is invalid for t enters as +0.0.  Every summand is >=
+ * +0.0, so that +0.0 changes no bit: the chain is the one over the valid
+ * points.  It does not depend on the tile, on the other classes or thresholds
+ * or on the launch: two runs are bit-equal, and a host loop over the columns
+ * reproduces the bits.
+ * One wave (a workgroup of its own: rows_per_group = 1) owns one row of one
+ * outer index and walks it in tiles of tile_cols = 64 columns.  Per tile a
+ * lane requests the truth, the thresholds of the launch and the n_member
+ * members of its point, all before any is looked at -- each element is read
+ * ONCE: (n_member + 1 + T) elements per point --, and sorts the members in
+ * registers (the networks of K3, +inf padding to the next power of two >= 2).
+ * Each of the up to 4 thresholds of a launch is then a pass over the sorted
+ * registers that leaves the lane's A and B in a wave-private LDS tile
+ * [2 T][65] of float64.  Then lane s < 2 T takes slot (threshold s / 2, term
+ * s % 2) and walks the points of the tile in column order, eight LDS reads at
+ * a time, adding each to its running sum.  Where the class of the column
+ * changes (wave-uniform) the lane stores its sum to `sums` and takes up that
+ * of the new class -- read back from `sums` if the row met the class before,
+ * +0.0 otherwise.  The counts are popcounts of the validity ballots.  Plain
+ * stores; no atomics at all.  More than 4 thresholds become further launches
+ * here, each with its own read of the members.
+ * Checked before anything is enqueued, in this order: the dtype ("unknown
+ * dtype"), 1 <= n_member <= 64 ("n_member="), 1 <= n_class <= 64
+ * ("n_class="), n_threshold >= 1 ("n_threshold="), a negative member_stride,
+ * negative sizes, null pointers ("null pointer") and the grid.  Zero n_outer,
+ * n_row or n_col is a no-op whatever the pointers are.
+ *
+ * wb2_twcrps_geometry: min_member = 1, max_member = 64 (both dtypes),
+ * thresholds_per_launch = min(n_threshold, 4), tile_cols = 64, rows_per_group
+ * = 1,
+ *   lds_bytes = 2 * thresholds_per_launch * 65 * 8   (at most 4160),
+ * max_grid_outer outer indices per grid row.  The same checks of dtype,
+ * n_member, n_class and n_threshold.
+ *
+ * The fold: the sums go through wb2_crps_bin_fold (n_cell = n_threshold *
+ * n_outer, n_slot = 2), the counts through wb2_event_fold (n_code = 2: valid,
+ * invalid).
+ */
+int wb2_twcrps_sums(int dtype, const void* ens, const int64_t* ens_slab,
+                    const void* truth, const int64_t* truth_slab,
+                    const void* const* threshold, const int64_t* thr_slab,
+                    int32_t n_threshold, int32_t n_member,
+                    int64_t member_stride, int64_t n_outer, int32_t n_row,
+                    int32_t n_col, const int32_t* col_class, int32_t n_class,
+                    int lower, double* sums, int32_t* cnt, void* stream);
+int wb2_twcrps_geometry(int dtype, int32_t n_member, int32_t n_class,
+                        int32_t n_threshold, int32_t* min_member,
+                        int32_t* max_member, int32_t* thresholds_per_launch,
+                        int32_t* tile_cols, int32_t* rows_per_group,
+                        int64_t* lds_bytes, int32_t* max_grid_outer);
+
 #ifdef __cplusplus
 }
 #endif

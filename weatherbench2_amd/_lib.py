@@ -267,6 +267,13 @@ _SIGNATURES = {
         _int, _i32, _i32, _c.POINTER(_i32), _c.POINTER(_i32),
         _c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i64),
         _c.POINTER(_i32)]),
+    'wb2_twcrps_sums': (_int, [
+        _int, _vp, _vp, _vp, _vp, _c.POINTER(_vp), _vp, _i32, _i32, _i64,
+        _i64, _i32, _i32, _vp, _i32, _int, _vp, _vp, _vp]),
+    'wb2_twcrps_geometry': (_int, [
+        _int, _i32, _i32, _i32, _c.POINTER(_i32), _c.POINTER(_i32),
+        _c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i32),
+        _c.POINTER(_i64), _c.POINTER(_i32)]),
 }
 
 _lib = None

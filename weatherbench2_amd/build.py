@@ -15,7 +15,8 @@ SOURCES = ('common.cpp', 'comm.cpp', 'staging.cpp', 'program.cpp', 'stream_reduc
            'derived_column.hip', 'derived_lead.hip', 'regrid.hip', 'quantile.hip',
            'time_window.hip', 'climatology.hip',
            'climatology_quantile.hip', 'slab_scatter.hip', 'box_gather.hip',
-           'event_table.hip', 'neighborhood.hip', 'crps_bins.hip')
+           'event_table.hip', 'neighborhood.hip', 'crps_bins.hip',
+           'twcrps.hip')
 # compiled once per member count listed in sort3_networks.inc (WB2_SORT3_SIZES)
 EXACT_SOURCE = 'ensemble_exact.hip'
 

@@ -2042,6 +2042,101 @@ def crps_bin_fold(sums: torch.Tensor, cnt: torch.Tensor, class_cols, wrow,
   return table, event_fold(cnt4[None].contiguous(), wrow, mult)[0]
 
 
+def twcrps_geometry(dtype: torch.dtype, n_member: int = 1, n_class: int = 1,
+                    n_threshold: int = 1) -> dict:
+  """Extents of the K21 sums kernel: the member counts it takes (`min_member`
+  .. `max_member`), the `thresholds_per_launch` that share one read and one
+  sort of the members, the `tile_cols` columns a wave sorts at a time,
+  `rows_per_group` = 1 (a row is one wave, a workgroup of its own), the
+  `lds_bytes` of its tile, `max_grid_outer` outer indices per grid row."""
+  return _geometry('wb2_twcrps_geometry',
+                   (dtype_code(dtype), int(n_member), int(n_class),
+                    int(n_threshold)),
+                   [('min_member', _I32), ('max_member', _I32),
+                    ('thresholds_per_launch', _I32), ('tile_cols', _I32),
+                    ('rows_per_group', _I32), ('lds_bytes', ctypes.c_int64),
+                    ('max_grid_outer', _I32)])
+
+
+def twcrps_sums(ens: torch.Tensor, member_stride: int, n_member: int,
+                ens_slab, truth: torch.Tensor, truth_slab,
+                thresholds: t.Sequence[torch.Tensor], thr_slabs, n_outer: int,
+                n_row: int, n_col: int, col_class, n_class: int,
+                lower: bool = False) -> tuple:
+  """K21, wb2_twcrps_sums: (float64 [n_threshold, n_outer, n_row, n_class, 2]
+  sums of A and B, int32 [n_threshold, n_outer, n_row, n_class, 1] valid
+  counts) of the points of every (threshold, row, column class); `lower`
+  picks the tail (v = min(z, t) instead of max(z, t)).  The operands, the HOST
+  slab tables and `col_class` are those of `event_counts`, checked here against
+  the operands' storage in the same way: the kernel trusts them.  Up to 4
+  thresholds share one read and one sort of the members; the C side splits the
+  rest."""
+  n_class = int(n_class)
+  thresholds = list(thresholds)
+  _require_float(ens, truth, *thresholds)
+  geo = twcrps_geometry(ens.dtype)
+  if not geo['min_member'] <= int(n_member) <= geo['max_member']:
+    raise ValueError(f'{int(n_member)} members: the twCRPS sums take '
+                     f"{geo['min_member']} to {geo['max_member']}")
+  (n_thr, n_member, n_outer, n_row, n_col), args = _event_front(
+      ens, member_stride, n_member, ens_slab, truth, truth_slab, thresholds,
+      thr_slabs, n_outer, n_row, n_col)
+  cls = _column_classes(col_class, n_col, n_class)
+  dev = ens.device
+  sums = torch.empty((n_thr, n_outer, n_row, n_class, 2), dtype=torch.float64,
+                     device=dev)
+  cnt = torch.empty((n_thr, n_outer, n_row, n_class, 1), dtype=torch.int32,
+                    device=dev)
+  if args is None:  # no points: nothing to add
+    return sums.zero_(), cnt.zero_()
+  _launch('twcrps_sums', 'wb2_twcrps_sums', *args,
+          _lib.ptr(_upload_i32(cls.astype(np.int32), dev)), n_class,
+          int(bool(lower)), _lib.ptr(sums), _lib.ptr(cnt),
+          current_stream_ptr(dev))
+  return sums, cnt
+
+
+def twcrps_fold(sums: torch.Tensor, cnt: torch.Tensor, class_cols, wrow,
+                mult) -> tuple:
+  """(float64 [n_threshold, n_outer, n_region, 2], float64 [n_threshold,
+  n_outer, n_region, 2]): wb2_crps_bin_fold of the sums of A and B (n_cell =
+  n_threshold * n_outer, n_slot = 2) -- sum_i wrow[r, i] * (sum_c float(mult[r,
+  c]) * sums[t, o, i, c]), classes then rows in increasing order, plain
+  float64 -- and wb2_event_fold of the counts (valid, invalid = `class_cols[c]`
+  - valid).  `class_cols` (columns per class), `wrow` (float64 [n_region,
+  n_row]) and `mult` (int32 [n_region, n_class]) are HOST arrays."""
+  if (sums.dtype != torch.float64 or sums.dim() != 5 or sums.shape[4] != 2 or
+      not sums.is_contiguous() or cnt.dtype != torch.int32 or
+      tuple(cnt.shape) != tuple(sums.shape[:4]) + (1,) or
+      not cnt.is_contiguous() or cnt.device != sums.device):
+    raise ValueError('sums must be a contiguous float64 [threshold, outer, '
+                     'row, class, 2] tensor and cnt its int32 [threshold, '
+                     'outer, row, class, 1]')
+  n_thr, n_outer, n_row, n_class, _ = (int(n) for n in sums.shape)
+  wrow = np.ascontiguousarray(wrow, dtype=np.float64)
+  mult = np.ascontiguousarray(mult, dtype=np.int32)
+  n_region = wrow.shape[0] if wrow.ndim == 2 else -1
+  if wrow.shape != (n_region, n_row) or mult.shape != (n_region, n_class):
+    raise ValueError('wrow must be [n_region, n_row] and mult [n_region, '
+                     'n_class]')
+  cols = np.ascontiguousarray(class_cols, dtype=np.int32).reshape(-1)
+  if cols.size != n_class:
+    raise ValueError(f'class_cols must hold {n_class} column counts')
+  dev = sums.device
+  table = torch.empty((n_thr, n_outer, n_region, 2), dtype=torch.float64,
+                      device=dev)
+  if table.numel():
+    _launch('twcrps_fold', 'wb2_crps_bin_fold', _lib.ptr(sums),
+            n_thr * n_outer, n_row, n_class, 2,
+            _lib.ptr(upload_f64_table(wrow, dev) if wrow.size else None),
+            _lib.ptr(_upload_i32(mult.reshape(-1), dev)), n_region,
+            _lib.ptr(table), current_stream_ptr(dev))
+  invalid = _upload_i32(cols, dev)[:n_class].reshape(1, 1, 1, n_class, 1
+                                                      ) - cnt
+  cnt2 = torch.cat([cnt, invalid.to(torch.int32)], dim=-1)
+  return table, event_fold(cnt2.contiguous(), wrow, mult)
+
+
 def fss_sums_geometry(n_col: int, n_class: int, n_window: int) -> dict:
   """Extents of the K19 box-sum kernel: a workgroup owns `rows_per_group` rows
   of one cell at full row width, `windows_per_launch` windows share one walk,

@@ -1900,6 +1900,83 @@ int wb2_twcrps_geometry(int dtype, int32_t n_member, int32_t n_class,
                         int32_t* tile_cols, int32_t* rows_per_group,
                         int64_t* lds_bytes, int32_t* max_grid_outer);
 
+/*
+ * K22: box pooling of (latitude, longitude) slabs -- the mean or the maximum
+ * over an odd window n = 2 h + 1 in grid points ("upscaling", Ebert 2008; the
+ * average- and max-pooled scores of Price et al. 2025).  The reference has no
+ * counterpart.
+ *
+ * The window of point (i, j) of a slab of n_row x n_col is K19's: the rows
+ * r0 = max(0, i - h) .. r1 = min(n_row - 1, i + h) (clipped at the poles), the
+ * columns (j - h .. j + h) mod n_col (cyclic), N_i = n * (r1 - r0 + 1) points.
+ * THE TWO ORDERS:
+ *   kind = WB2_POOL_MEAN: float64 after an exact widening.
+ *     H[r][j] = the sequential chain s = s + x[r][(j + d) mod n_col] over the
+ *       column offsets d = -h, ..., +h in that order, STARTED FROM THE FIRST
+ *       TERM (not from +0.0: -0.0 survives n = 1),
+ *     V[i][j] = the sequential chain of H[r][j] over r = r0 .. r1, increasing,
+ *       started from H[r0][j],
+ *     out = V / (double)N_i, rounded once to the input dtype (to nearest
+ *       even).  No fused multiply-add.  NaN and +-inf follow IEEE in that
+ *       order -- a window that holds a NaN is NaN, +inf and -inf in one window
+ *       are NaN --; nothing is special-cased; the payload and the sign of a
+ *       NaN are not pinned.
+ *   kind = WB2_POOL_MAX: the input dtype, the same two passes with
+ *     m = first; for each next v: m = (v > m || v != v) ? v : m.
+ *     A NaN propagates; the sign of a zero result is that of the first zero
+ *     met in that order.
+ * n = 1 returns the input's values (bit-equal but for NaN payloads).  Running
+ * or prefix sums round differently and are not an implementation of this.
+ *
+ * wb2_pool_fields: K18's operand convention.  Field (o, m), o < n_outer, m <
+ * n_member, starts in_slab[o] * n_row * n_col + m * member_stride ELEMENTS
+ * after `in` (in_slab DEV int64[n_outer], null = identity; every table value
+ * the caller's to check); a field without members is n_member = 1.
+ * `windows` is a HOST int32[n_window].  out[w][o][m][i][j] (DEV, contiguous,
+ * the input dtype, every element written).
+ * A workgroup of 1024 threads owns one field and a tile of tile_rows x
+ * tile_cols outputs.  It stages the tile and its halo for the largest window
+ * of the launch in LDS once (rows clipped, the column index wrapped), then per
+ * window writes the horizontal chains of the rows that window reaches to a
+ * second LDS tile (8 bytes a chain) and walks them vertically.  Consecutive
+ * lanes hold consecutive columns in both passes.  Up to windows_per_launch = 4
+ * windows share one staging; further windows are further launches, each staged
+ * for its own largest window.  Where `in`, `out` are 16-byte aligned and n_col
+ * and member_stride are multiples of 16 / sizeof(element), the tile's own
+ * columns are read with 16-byte loads and the results leave in 16-byte
+ * streaming stores; otherwise one element per access.  The halo is always one
+ * element per access.  Both forms give the same bits.  Plain stores, no
+ * atomics: two runs are bit-equal.
+ * Checked before anything is enqueued, in this order: the dtype ("unknown
+ * dtype"), kind ("kind="), 1 <= n_member <= 128 ("n_member="), n_window >= 1
+ * ("n_window="), a negative member_stride, n_outer, n_row or n_col ("is
+ * negative"), `windows` ("null pointer"), every window odd, 1 to 255 and at
+ * most n_col ("window=") and at most max_window ("max_window"); then zero
+ * n_outer, n_row or n_col is a no-op whatever `in` and `out` are; then `in`
+ * and `out` ("null pointer") and the grid.
+ *
+ * wb2_pool_geometry: tile_cols = 64; tile_rows = the first of 32, 16, 8 whose
+ * staging for the LARGEST window of the call,
+ *   lds_bytes = round8((tile_rows + 2 h) * (64 + 2 h) * sizeof(element))
+ *               + (tile_rows + 2 h) * 64 * 8,
+ * is at most 160 KiB (every launch of the call uses that tile);
+ * windows_per_launch = min(n_window, 4); max_window = the largest window whose
+ * staging fits at tile_rows = 8 (123 for float32, 99 for float64);
+ * max_grid_outer fields per grid row.  The same checks of dtype, n_window,
+ * n_col and the windows.
+ */
+#define WB2_POOL_MEAN 0
+#define WB2_POOL_MAX 1
+int wb2_pool_fields(int dtype, const void* in, const int64_t* in_slab,
+                    int32_t n_member, int64_t member_stride, int64_t n_outer,
+                    int32_t n_row, int32_t n_col, const int32_t* windows,
+                    int32_t n_window, int kind, void* out, void* stream);
+int wb2_pool_geometry(int dtype, int32_t n_col, const int32_t* windows,
+                      int32_t n_window, int32_t* windows_per_launch,
+                      int32_t* tile_rows, int32_t* tile_cols,
+                      int64_t* lds_bytes, int32_t* max_window,
+                      int32_t* max_grid_outer);
+
 #ifdef __cplusplus
 }
 #endif

@@ -274,6 +274,13 @@ _SIGNATURES = {
         _int, _i32, _i32, _i32, _c.POINTER(_i32), _c.POINTER(_i32),
         _c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i32),
         _c.POINTER(_i64), _c.POINTER(_i32)]),
+    'wb2_pool_fields': (_int, [
+        _int, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _c.POINTER(_i32), _i32,
+        _int, _vp, _vp]),
+    'wb2_pool_geometry': (_int, [
+        _int, _i32, _c.POINTER(_i32), _i32, _c.POINTER(_i32),
+        _c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i64),
+        _c.POINTER(_i32), _c.POINTER(_i32)]),
 }
 
 _lib = None

@@ -2137,6 +2137,67 @@ def twcrps_fold(sums: torch.Tensor, cnt: torch.Tensor, class_cols, wrow,
   return table, event_fold(cnt2.contiguous(), wrow, mult)
 
 
+POOL_KINDS = {'mean': 0, 'max': 1}  # WB2_POOL_MEAN, WB2_POOL_MAX
+
+
+def pool_geometry(dtype: torch.dtype, n_col: int = 1, windows=(1,)) -> dict:
+  """Extents of the K22 pooling kernel for a call with `windows` on rows of
+  `n_col`: a workgroup owns a tile of `tile_rows` x `tile_cols` outputs of one
+  field, `windows_per_launch` windows share one staging of `lds_bytes` (that
+  of the call's largest window), `max_window` is the largest window whose
+  halo fits the LDS at the smallest tile, `max_grid_outer` fields per grid
+  row.  `windows` is a HOST sequence."""
+  windows = np.ascontiguousarray(windows, dtype=np.int32).reshape(-1)
+  return _geometry('wb2_pool_geometry',
+                   (dtype_code(dtype), int(n_col),
+                    windows.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                    windows.size),
+                   [('windows_per_launch', _I32), ('tile_rows', _I32),
+                    ('tile_cols', _I32), ('lds_bytes', ctypes.c_int64),
+                    ('max_window', _I32), ('max_grid_outer', _I32)])
+
+
+def pool_fields(x: torch.Tensor, member_stride: int, n_member: int, slabs,
+                n_outer: int, n_row: int, n_col: int, windows,
+                kind: str = 'mean') -> torch.Tensor:
+  """K22, wb2_pool_fields: [n_window, n_outer, n_member, n_row, n_col] in the
+  dtype of `x`, the `kind` ('mean' or 'max') of every point's window -- odd
+  sizes in grid points, rows clipped, columns cyclic; the two fixed orders are
+  stated in wb2hip.h.  Field (o, m) is the slab of `n_row * n_col` elements
+  that starts `slabs[o]` slabs and `m * member_stride` ELEMENTS after the
+  first element of `x` (a field without members: n_member = 1).  `slabs`
+  (None = identity) and `windows` are HOST sequences; the table is checked here
+  against the storage of `x` -- the kernel trusts it --, the windows by the
+  entry point."""
+  if kind not in POOL_KINDS:
+    raise ValueError(f'kind={kind!r}: the pooling takes '
+                     f'{" or ".join(map(repr, POOL_KINDS))}')
+  _require_float(x)
+  n_member, n_outer, n_row, n_col, member_stride = (
+      int(v) for v in (n_member, n_outer, n_row, n_col, member_stride))
+  if min(n_outer, n_row, n_col) < 0 or member_stride < 0:
+    raise ValueError('bad sizes')
+  windows = np.ascontiguousarray(windows, dtype=np.int32).reshape(-1)
+  if windows.size == 0:
+    raise ValueError('no windows')
+  slab = n_row * n_col
+  table = _event_slabs(slabs, n_outer, x, slab,
+                       (max(n_member, 1) - 1) * member_stride, 'field')
+  dev = x.device
+  out = torch.empty((windows.size, n_outer, max(n_member, 0), n_row, n_col),
+                    dtype=x.dtype, device=dev)
+  # (no points: nothing to upload or launch; the entry point still checks)
+  if table is not None and out.numel():
+    table = upload_table(table, dev)
+  _launch('pool_fields', 'wb2_pool_fields', dtype_code(x.dtype), _lib.ptr(x),
+          _lib.ptr(table if out.numel() else None), n_member, member_stride,
+          n_outer, n_row, n_col,
+          windows.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+          windows.size, POOL_KINDS[kind], _lib.ptr(out),
+          current_stream_ptr(dev))
+  return out
+
+
 def fss_sums_geometry(n_col: int, n_class: int, n_window: int) -> dict:
   """Extents of the K19 box-sum kernel: a workgroup owns `rows_per_group` rows
   of one cell at full row width, `windows_per_launch` windows share one walk,

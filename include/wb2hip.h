@@ -1977,6 +1977,78 @@ int wb2_pool_geometry(int dtype, int32_t n_col, const int32_t* windows,
                       int64_t* lds_bytes, int32_t* max_window,
                       int32_t* max_grid_outer);
 
+/*
+ * K23: count-weighted means of a time axis, one per bootstrap replicate (the
+ * block bootstrap of per-time results, weatherbench2_amd/bootstrap.py).  The
+ * reference has no counterpart.
+ *
+ * The data is K13's: T[n_outer][n_time][n_point], T = dtype; time step t of
+ * outer index o starts `slab[o * n_time + t] * n_point` elements after `in`
+ * (DEV int64; NULL = the identity o * n_time + t; every table value the
+ * caller's to check).  Replicate b draws time step t counts[b][t] >= 0 times
+ * (how the counts are passed: below).
+ * out is a contiguous DEV double[n_rep][n_outer][n_point], every element
+ * written.
+ *
+ * THE ORDER.  For replicate b, outer index o, point p:
+ *   walk t = 0 .. n_time - 1 in increasing order, n = counts[b][t];
+ *   a step with n == 0 is LEFT OUT: it is not multiplied, so a NaN or +-inf at
+ *     a time the replicate did not draw cannot reach it;
+ *   x = the value widened exactly to float64; with skipna != 0 a NaN x is
+ *     left out;
+ *   term = (double)n * x, one rounding;
+ *   the first used term starts the chain, every later one is S = S + term, one
+ *     rounding (started at -0.0 the chain has the same bits: (-0.0) + term is
+ *     term, and that is how the kernel and the host path do it);
+ *   W = the integer sum of the used n;
+ *   out = S / (double)W, one rounding; with no used term 0.0 / 0.0 (NaN).
+ * No fused multiply-add for float64 input.  For float32 input n * x is exact
+ * in float64, so there an fma gives the same bits and is used.  NaN and +-inf
+ * at a used step follow IEEE in that order; the payload and the sign of a NaN
+ * are not pinned.  Plain stores, no atomics: two runs are bit-equal.
+ *
+ * The counts arrive widened to float64 and laid out for the kernel, with R =
+ * replicates_per_group, A = steps_ahead and n_group = ceil(n_rep / R):
+ *   weights  DEV double[n_group][ceil(n_time / A) * A][R]: weights[g][t][r] =
+ *            (double)counts[g * R + r][t]; the replicates >= n_rep and the
+ *            steps >= n_time are padding and hold +0.0
+ *   totals   DEV double[n_group * R]: the row sums of the counts
+ * so the counts a group needs next are the next bytes.  The caller guarantees
+ * counts >= 0 and row sums < 2^31 (engine.resampled_means checks them on the
+ * host and builds both tables).  A count is zero iff all bits of its weight
+ * are; W = totals minus, with skipna, the counts of the point's NaNs, both
+ * exact.
+ *
+ * A workgroup of 256 threads owns a tile of points and R consecutive
+ * replicates, whose chains every thread keeps in registers: a loaded value
+ * serves R replicates.  A thread owns adjacent points (16-byte loads where
+ * n_point is a multiple of the vector and `in` and `out` are 16-byte aligned,
+ * one element per access otherwise, with the same bits) and requests the A
+ * time steps after the ones it is combining before it combines any.  The
+ * counts do not depend on the thread: they are fetched with scalar loads, and
+ * a zero count is a branch the whole wave takes.  With skipna a NaN enters as
+ * -0.0 (S + n * (-0.0) has the bits of S: left out).  Grid: (point tiles x
+ * replicate groups) x outer indices.  No LDS.
+ *
+ * Refused before anything is enqueued: an unknown dtype ("unknown dtype");
+ * n_rep, n_time or n_point < 1 or a negative n_outer ("bad sizes"); then
+ * n_outer == 0 is a no-op; then null `in`, `weights`, `totals` or `out`
+ * ("null pointer"); a problem that does not fit a grid ("bad sizes").
+ * wb2_resampled_means_geometry: points per workgroup tile (wide != 0: 16-byte
+ * loads), the replicates of a group, the time steps a thread requests ahead
+ * (4 for float64, 2 for float32; it does not depend on `wide`), and the outer
+ * indices per grid row.
+ */
+int wb2_resampled_means(int dtype, int skipna, const void* in,
+                        const int64_t* slab, int64_t n_outer, int32_t n_time,
+                        int64_t n_point, const double* weights,
+                        const double* totals, int32_t n_rep, double* out,
+                        void* stream);
+int wb2_resampled_means_geometry(int dtype, int wide, int32_t* tile_points,
+                                 int32_t* replicates_per_group,
+                                 int32_t* steps_ahead,
+                                 int32_t* max_grid_outer);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2198,6 +2198,89 @@ def pool_fields(x: torch.Tensor, member_stride: int, n_member: int, slabs,
   return out
 
 
+def resampled_means_geometry(dtype: torch.dtype, wide: bool = False) -> dict:
+  """Extents of the K23 kernel: `tile_points` adjacent points per workgroup,
+  `replicates_per_group` replicates whose chains a thread keeps in registers,
+  `steps_ahead` time steps it requests before it combines any,
+  `max_grid_outer` outer indices per grid row."""
+  return _geometry('wb2_resampled_means_geometry',
+                   (dtype_code(dtype), int(wide)),
+                   [('tile_points', _I32), ('replicates_per_group', _I32),
+                    ('steps_ahead', _I32), ('max_grid_outer', _I32)])
+
+
+def checked_counts(counts, n_time: int) -> np.ndarray:
+  """`counts` as a HOST int64 [n_replicate, n_time], refused (ValueError) when
+  it is not an integer array of that shape with entries >= 0 and row sums below
+  2^31."""
+  counts = np.asarray(counts)
+  if counts.dtype.kind not in 'iu' or counts.ndim != 2:
+    raise ValueError('counts must be an integer array [n_replicate, n_time], '
+                     f'not {counts.dtype} {counts.shape}')
+  if counts.shape[0] < 1 or counts.shape[1] != n_time or n_time < 1:
+    raise ValueError(f'counts {counts.shape} do not match n_time={n_time} '
+                     '(at least one replicate and one time)')
+  if counts.dtype.kind == 'u' and counts.size and counts.max() >= 2 ** 31:
+    raise ValueError('counts: a row sum reaches 2^31')
+  counts = counts.astype(np.int64)
+  if counts.min() < 0:
+    raise ValueError('counts hold a negative entry')
+  if counts.sum(axis=1).max() >= 2 ** 31:
+    raise ValueError('counts: a row sum reaches 2^31')
+  return counts
+
+
+def resampled_means_tables(counts: np.ndarray, dtype: torch.dtype) -> tuple:
+  """The two HOST tables wb2_resampled_means reads, of checked counts
+  [n_replicate, n_time]: the counts widened to float64 as [n_group, n_time
+  padded to a multiple of steps_ahead, replicates_per_group] (the padding is
+  zero) and their row sums, float64 [n_group * replicates_per_group]."""
+  geo = resampled_means_geometry(dtype)
+  per, ahead = geo['replicates_per_group'], geo['steps_ahead']
+  n_rep, n_time = counts.shape
+  n_group = -(-n_rep // per)
+  lay = np.zeros((n_group * per, -(-n_time // ahead) * ahead),
+                 dtype=np.float64)
+  lay[:n_rep, :n_time] = counts
+  weights = np.ascontiguousarray(
+      lay.reshape(n_group, per, -1).transpose(0, 2, 1))
+  return torch.from_numpy(weights), torch.from_numpy(lay.sum(axis=1))
+
+
+def resampled_means(x: torch.Tensor, slab, n_outer: int, n_time: int,
+                    n_point: int, counts, skipna: bool = False
+                    ) -> torch.Tensor:
+  """K23, wb2_resampled_means: float64 [n_replicate, n_outer, n_point], the
+  mean of the series x[o, :, i] with time step t taken counts[b, t] times, in
+  the order stated in wb2hip.h (a step with count 0 is left out; with `skipna`
+  a NaN is).  Time step t of outer index o starts `slab[o * n_time + t] *
+  n_point` elements after the first element of `x`; `slab` (None = identity)
+  and `counts` are HOST arrays.  Both and every size are checked here, the
+  table against the storage of `x` -- the kernel trusts it --, before anything
+  is uploaded or launched."""
+  _require_float(x)
+  n_outer, n_time, n_point = int(n_outer), int(n_time), int(n_point)
+  if n_outer < 0 or n_time < 1 or n_point < 1:
+    raise ValueError(f'bad sizes: n_outer={n_outer} n_time={n_time} '
+                     f'n_point={n_point}')
+  counts = checked_counts(counts, n_time)
+  n_rep = counts.shape[0]
+  table = _event_slabs(slab, n_outer * n_time, x, n_point, 0, 'time step')
+  dev = x.device
+  out = torch.empty((n_rep, n_outer, n_point), dtype=torch.float64, device=dev)
+  if n_outer == 0:
+    return out
+  weights, totals = resampled_means_tables(counts, x.dtype)
+  weights, totals = weights.to(dev), totals.to(dev)
+  if table is not None:
+    table = upload_table(table, dev)
+  _launch('resampled_means', 'wb2_resampled_means', dtype_code(x.dtype),
+          int(bool(skipna)), _lib.ptr(x), _lib.ptr(table), n_outer, n_time,
+          n_point, _lib.ptr(weights), _lib.ptr(totals), n_rep, _lib.ptr(out),
+          current_stream_ptr(dev))
+  return out
+
+
 def fss_sums_geometry(n_col: int, n_class: int, n_window: int) -> dict:
   """Extents of the K19 box-sum kernel: a workgroup owns `rows_per_group` rows
   of one cell at full row width, `windows_per_launch` windows share one walk,

@@ -2049,6 +2049,88 @@ int wb2_resampled_means_geometry(int dtype, int wide, int32_t* tile_points,
                                  int32_t* steps_ahead,
                                  int32_t* max_grid_outer);
 
+/*
+ * K24: the per-bin sums of conditional verification: the spread-error
+ * diagnostic (Leutbecher & Palmer 2008) and the conditional bias (Murphy &
+ * Winkler 1987).  The reference has the region means (EnsembleVariance,
+ * EnsembleMeanMSE, Bias) and no stratified counterpart.
+ *
+ * One point with truth y and the members x_0 .. x_{M-1} in STORAGE order
+ * (nothing is sorted), all arithmetic in float64 after an exact widening, no
+ * fused multiply-add, every product rounded before it is added:
+ *   S = x_0;  S = S + x_m  (m = 1 .. M-1);  mu = S / (double)M
+ *   d_m = x_m - mu;  Q = d_0 d_0;  Q = Q + d_m d_m  (m = 1 .. M-1)
+ *   s2 = Q / (double)(M - 1);  M = 1: s2 = +0.0
+ *   e = mu - y;  se = e e
+ *   v = s2 (mode 0, spread), mu (mode 1, forecast) or y (mode 2, truth)
+ *   bin = #{k : edges[k] <= v}  (searchsorted side='right': a value on an
+ *         edge belongs to the upper bin; n_bin = n_edge + 1, the first and the
+ *         last bin are open-ended)
+ * For mode 0 the caller passes SQUARED edges: variances are compared and no
+ * root is taken.  The point is invalid iff the truth or any member is NaN
+ * (K18's rule).  Points that hold +-inf are not pinned.
+ *
+ * wb2_conditional_sums: K20's operands and slab-table convention (ens,
+ * ens_slab, truth, truth_slab, n_member, member_stride, n_outer; tables DEV
+ * int64, null = identity; col_class DEV int32[n_col] with values in [0,
+ * n_class); every table value the caller's to check) and edges, a DEV
+ * float64[n_edge], finite and strictly increasing (the caller's to check; null
+ * is allowed for n_edge = 0).
+ *   sums[o][i][c][b][0..3] (DEV float64, every element written) = the sums of
+ *     mu, y, s2 and se over the valid points of bin b among the columns j with
+ *     col_class[j] == c in row i of outer index o,
+ *   cnt[o][i][c][b] (DEV int32, every element written) = their number.  (The
+ *     invalid count is the column count of the class minus the bins' total.)
+ * THE ORDER OF THE SUM of one (o, i, c, b, term): one sequential float64 chain
+ * s = s + v from +0.0 over the columns of the class in INCREASING COLUMN
+ * ORDER, where a point that is invalid or lies in another bin enters as +0.0.
+ * A chain started at +0.0 never holds -0.0 (x + (-x) and +0.0 + (-0.0) both
+ * round to +0.0), so that +0.0 changes no bit: the chain is the one over the
+ * bin's own points.  It does not depend on the tile, on the other classes or
+ * bins or on the launch: two runs are bit-equal, and a host loop over the
+ * columns reproduces the bits.
+ * One wave (a workgroup of its own: rows_per_group = 1) owns one row of one
+ * outer index and walks it in tiles of tile_cols = 64 columns.  Per tile a
+ * lane requests the truth and the n_member members of its point, all before
+ * any is looked at -- each element is read ONCE: (n_member + 1) elements per
+ * point --, forms mu, y, s2, se and the bin in registers (lane k keeps edge k;
+ * the edges go round by v_readlane) and stores them in a wave-private LDS tile
+ * of [4][64] float64 and [64] int32 (bin -1: invalid or past the row end).
+ * Then lane b < n_bin takes bin b and walks the points of the tile in column
+ * order, eight at a time: it reads the bin and the four values of each point
+ * (broadcasts) and adds the value, or +0.0, to each of its four running sums.
+ * Where the class of the column changes (wave-uniform) the lane stores its
+ * sums and count and takes up those of the new class -- read back from `sums`
+ * and `cnt` if the row met the class before, 0 otherwise.  Plain stores; no
+ * atomics at all.
+ * Checked before anything is enqueued, in this order: the dtype ("unknown
+ * dtype"), 1 <= n_member <= 64 ("n_member="), 1 <= n_class <= 64
+ * ("n_class="), 0 <= n_edge <= 63 ("n_edge="), the mode ("mode="), a negative
+ * member_stride, negative sizes, null pointers ("null pointer") and the grid.
+ * Zero n_outer, n_row or n_col is a no-op whatever the pointers are.
+ *
+ * wb2_conditional_geometry: min_member = 1, max_member = 64 (both dtypes),
+ * max_edges = 63, tile_cols = 64, rows_per_group = 1,
+ *   lds_bytes = 4 * 64 * 8 + 64 * 4 = 2304,
+ * max_grid_outer outer indices per grid row.  The same checks of dtype,
+ * n_member, n_class and n_edge.
+ *
+ * The fold: the sums go through wb2_crps_bin_fold (n_slot = 4 n_bin), the
+ * counts through wb2_event_fold (n_code = n_bin + 1: the bins, then invalid).
+ */
+int wb2_conditional_sums(int dtype, const void* ens, const int64_t* ens_slab,
+                         const void* truth, const int64_t* truth_slab,
+                         int32_t n_member, int64_t member_stride,
+                         int64_t n_outer, int32_t n_row, int32_t n_col,
+                         const int32_t* col_class, int32_t n_class, int mode,
+                         const double* edges, int32_t n_edge, double* sums,
+                         int32_t* cnt, void* stream);
+int wb2_conditional_geometry(int dtype, int32_t n_member, int32_t n_class,
+                             int32_t n_edge, int32_t* min_member,
+                             int32_t* max_member, int32_t* max_edges,
+                             int32_t* tile_cols, int32_t* rows_per_group,
+                             int64_t* lds_bytes, int32_t* max_grid_outer);
+
 #ifdef __cplusplus
 }
 #endif

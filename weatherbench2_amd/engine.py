@@ -2137,6 +2137,137 @@ def twcrps_fold(sums: torch.Tensor, cnt: torch.Tensor, class_cols, wrow,
   return table, event_fold(cnt2.contiguous(), wrow, mult)
 
 
+CONDITIONAL_MODES = {'spread': 0, 'forecast': 1, 'truth': 2}
+CONDITIONAL_TERMS = 4  # mu, y, s2, se
+
+
+def conditional_geometry(dtype: torch.dtype, n_member: int = 1,
+                         n_class: int = 1, n_edge: int = 0) -> dict:
+  """Extents of the K24 sums kernel: the member counts it takes (`min_member`
+  .. `max_member`), the `max_edges` bin edges (one bin more), the `tile_cols`
+  columns a wave bins at a time, `rows_per_group` = 1 (a row is one wave, a
+  workgroup of its own), the `lds_bytes` of its tile, `max_grid_outer` outer
+  indices per grid row."""
+  return _geometry('wb2_conditional_geometry',
+                   (dtype_code(dtype), int(n_member), int(n_class),
+                    int(n_edge)),
+                   [('min_member', _I32), ('max_member', _I32),
+                    ('max_edges', _I32), ('tile_cols', _I32),
+                    ('rows_per_group', _I32), ('lds_bytes', ctypes.c_int64),
+                    ('max_grid_outer', _I32)])
+
+
+def conditional_edges(edges, max_edges: int = 63) -> np.ndarray:
+  """`edges` as the float64 [n_edge] array the K24 kernel compares against:
+  finite, strictly increasing, at most `max_edges` (ValueError otherwise)."""
+  e = np.ascontiguousarray(edges, dtype=np.float64)
+  if e.ndim != 1:
+    raise ValueError('the bin edges must be a 1-D sequence')
+  if e.size > max_edges:
+    raise ValueError(f'{e.size} bin edges: the conditional sums take 0 to '
+                     f'{max_edges}')
+  if not np.isfinite(e).all():
+    raise ValueError('the bin edges must be finite')
+  if e.size > 1 and not (e[1:] > e[:-1]).all():
+    raise ValueError('the bin edges must be strictly increasing')
+  return e
+
+
+def conditional_sums(ens: torch.Tensor, member_stride: int, n_member: int,
+                     ens_slab, truth: torch.Tensor, truth_slab, n_outer: int,
+                     n_row: int, n_col: int, col_class, n_class: int,
+                     mode, edges) -> tuple:
+  """K24, wb2_conditional_sums: (float64 [n_outer, n_row, n_class, n_bin, 4]
+  sums of mu, y, s2 and se, int32 [n_outer, n_row, n_class, n_bin] counts) of
+  the valid points of every (row, column class, bin).  `mode` is 'spread',
+  'forecast' or 'truth' (or 0, 1, 2): what is binned; `edges` is a HOST
+  sequence of n_bin - 1 finite, strictly increasing values in the units of
+  that quantity (for 'spread': of the VARIANCE, that is, already squared).
+  The operands, the HOST slab tables and `col_class` are those of
+  `event_counts`; all of them and the edges are checked here: the kernel
+  trusts them."""
+  _require_float(ens, truth)
+  _check_contiguous(ens.device, 'the device of the members', truth, view=ens)
+  n_member, n_outer, n_row, n_col, member_stride, n_class = (
+      int(v) for v in (n_member, n_outer, n_row, n_col, member_stride,
+                       n_class))
+  if min(n_outer, n_row, n_col) < 0 or member_stride < 0:
+    raise ValueError('bad sizes')
+  mode = CONDITIONAL_MODES.get(mode, mode)
+  if mode not in (0, 1, 2):
+    raise ValueError(f'mode={mode!r}: the conditional sums take '
+                     f'{", ".join(map(repr, CONDITIONAL_MODES))}')
+  geo = conditional_geometry(ens.dtype)
+  if not geo['min_member'] <= n_member <= geo['max_member']:
+    raise ValueError(f'{n_member} members: the conditional sums take '
+                     f"{geo['min_member']} to {geo['max_member']}")
+  e = conditional_edges(edges, geo['max_edges'])
+  n_bin = e.size + 1
+  slab = n_row * n_col
+  es = _event_slabs(ens_slab, n_outer, ens, slab,
+                    (n_member - 1) * member_stride, 'member')
+  ts = _event_slabs(truth_slab, n_outer, truth, slab, 0, 'truth')
+  cls = _column_classes(col_class, n_col, n_class)
+  dev = ens.device
+  sums = torch.empty((n_outer, n_row, n_class, n_bin, CONDITIONAL_TERMS),
+                     dtype=torch.float64, device=dev)
+  cnt = torch.empty((n_outer, n_row, n_class, n_bin), dtype=torch.int32,
+                    device=dev)
+  if slab * n_outer == 0:  # no points: nothing to add
+    return sums.zero_(), cnt.zero_()
+  _launch('conditional_sums', 'wb2_conditional_sums', dtype_code(ens.dtype),
+          _lib.ptr(ens), _lib.ptr(None if es is None else
+                                  upload_table(es, dev)),
+          _lib.ptr(truth), _lib.ptr(None if ts is None else
+                                    upload_table(ts, dev)),
+          n_member, member_stride, n_outer, n_row, n_col,
+          _lib.ptr(_upload_i32(cls.astype(np.int32), dev)), n_class, mode,
+          _lib.ptr(upload_f64_table(e, dev) if e.size else None), e.size,
+          _lib.ptr(sums), _lib.ptr(cnt), current_stream_ptr(dev))
+  return sums, cnt
+
+
+def conditional_fold(sums: torch.Tensor, cnt: torch.Tensor, class_cols, wrow,
+                     mult) -> tuple:
+  """(float64 [n_outer, n_region, n_bin, 4], float64 [n_outer, n_region,
+  n_bin + 1]): wb2_crps_bin_fold of the sums (n_slot = 4 n_bin) -- sum_i
+  wrow[r, i] * (sum_c float(mult[r, c]) * sums[o, i, c]), classes then rows in
+  increasing order, plain float64 -- and wb2_event_fold of the counts (the
+  bins, then invalid = `class_cols[c]` - the bins' total).  `class_cols`
+  (columns per class), `wrow` (float64 [n_region, n_row]) and `mult` (int32
+  [n_region, n_class]) are HOST arrays."""
+  if (sums.dtype != torch.float64 or sums.dim() != 5 or
+      sums.shape[4] != CONDITIONAL_TERMS or not sums.is_contiguous() or
+      cnt.dtype != torch.int32 or tuple(cnt.shape) != tuple(sums.shape[:4]) or
+      not cnt.is_contiguous() or cnt.device != sums.device):
+    raise ValueError('sums must be a contiguous float64 [outer, row, class, '
+                     'bin, 4] tensor and cnt its int32 [outer, row, class, '
+                     'bin]')
+  n_outer, n_row, n_class, n_bin, _ = (int(n) for n in sums.shape)
+  wrow = np.ascontiguousarray(wrow, dtype=np.float64)
+  mult = np.ascontiguousarray(mult, dtype=np.int32)
+  n_region = wrow.shape[0] if wrow.ndim == 2 else -1
+  if wrow.shape != (n_region, n_row) or mult.shape != (n_region, n_class):
+    raise ValueError('wrow must be [n_region, n_row] and mult [n_region, '
+                     'n_class]')
+  cols = np.ascontiguousarray(class_cols, dtype=np.int32).reshape(-1)
+  if cols.size != n_class:
+    raise ValueError(f'class_cols must hold {n_class} column counts')
+  dev = sums.device
+  table = torch.empty((n_outer, n_region, n_bin, CONDITIONAL_TERMS),
+                      dtype=torch.float64, device=dev)
+  if table.numel():
+    _launch('conditional_fold', 'wb2_crps_bin_fold', _lib.ptr(sums), n_outer,
+            n_row, n_class, CONDITIONAL_TERMS * n_bin,
+            _lib.ptr(upload_f64_table(wrow, dev) if wrow.size else None),
+            _lib.ptr(_upload_i32(mult.reshape(-1), dev)), n_region,
+            _lib.ptr(table), current_stream_ptr(dev))
+  invalid = _upload_i32(cols, dev)[:n_class].reshape(1, 1, n_class
+                                                      ) - cnt.sum(dim=-1)
+  codes = torch.cat([cnt, invalid[..., None].to(torch.int32)], dim=-1)
+  return table, event_fold(codes[None].contiguous(), wrow, mult)[0]
+
+
 POOL_KINDS = {'mean': 0, 'max': 1}  # WB2_POOL_MEAN, WB2_POOL_MAX
 
 

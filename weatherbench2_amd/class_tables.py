@@ -1,0 +1,138 @@
+"""What the tables over per-(row, column class) float64 sums share.
+
+`crps_decomposition.CRPSTable` (K20), `threshold_weighted.ThresholdWeightedCRPS`
+(K21) and `conditional.ConditionalTable` (K24) sum their points per (row, column
+class) in one fixed order and fold the classes and rows in another
+(csrc/class_sums.hpp is the same layer under the kernels).  Here: the host
+fold, the choice between the host and the device path, the checks of a
+variable, and the truth-led (<outer dims>, 'term', 'bin') table that `CRPSTable`
+and `ConditionalTable` are (`ThresholdWeightedCRPS`, forecast-led and with
+thresholds, is an `events.ExceedanceTable`).
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from weatherbench2_amd import engine
+from weatherbench2_amd import events
+from weatherbench2_amd import metrics as _m
+from weatherbench2_amd import xarray_lite as xl
+from weatherbench2_amd.metrics import Metric
+
+TERM, BIN = 'term', 'bin'
+
+
+def host_fold(sums: np.ndarray, wrow: np.ndarray, mult: np.ndarray,
+              n_lead: int = 1) -> np.ndarray:
+  """`engine._class_fold` in NumPy: float64 class sums [<n_lead cell axes>,
+  n_row, n_class, <slot axes>] -> [<cell axes>, n_region, <slot axes>]: s = s +
+  float(mult[r, c]) * sums[.., i, c] over the classes, then acc = acc + wrow[r,
+  i] * s over the rows, both in increasing order from 0.0."""
+  n_row, n_class = sums.shape[n_lead:n_lead + 2]
+  flat = sums.reshape((-1, n_row, n_class, int(np.prod(sums.shape[n_lead + 2:],
+                                                       dtype=np.int64))))
+  multf = mult.astype(np.float64)
+  acc = np.zeros((flat.shape[0], wrow.shape[0], flat.shape[3]),
+                 dtype=np.float64)
+  for i in range(n_row):
+    s = np.zeros_like(acc)
+    for c in range(n_class):
+      s = s + multf[None, :, c, None] * flat[:, None, i, c]
+    acc = acc + wrow[None, :, i, None] * s
+  return acc.reshape(sums.shape[:n_lead] + (wrow.shape[0],) +
+                     sums.shape[n_lead + 2:])
+
+
+def region_sums(device, args: tuple, host: tuple, device_path: tuple,
+                class_cols, wrow, mult) -> tuple:
+  """(region sums, weighted counts) as host arrays: fold(*sums(*args),
+  class_cols, wrow, mult) with `host` = (sums, fold) for host operands
+  (`device` is None) and `device_path` = the engine's pair otherwise."""
+  if device is None:
+    sums, fold = host
+    return fold(*sums(*args), class_cols, wrow, mult)
+  sums, fold = device_path
+  table, counts = fold(*sums(*args), class_cols, wrow, mult)
+  engine.order_read(table)
+  engine.order_read(counts)
+  return table.cpu().numpy(), counts.cpu().numpy()
+
+
+def check_variable(name: str, fvar, tvar, ensemble_dim, noun: str,
+                   members: tuple) -> int:
+  """The checks of one variable before anything is launched: float32 or
+  float64 data and an ensemble size within `members` = (min, max); `noun`
+  words the messages ('the CRPS table').  Returns the ensemble size (1 for a
+  forecast without `ensemble_dim`)."""
+  for da in (fvar, tvar):
+    if _m._torch_dtype_of(da.data) not in (torch.float32, torch.float64):
+      raise ValueError(f'variable {name!r} is {da.data.dtype}: {noun} takes '
+                       'float32 and float64')
+  n_member = 1
+  if ensemble_dim is not None and ensemble_dim in fvar.dims:
+    n_member = int(fvar.sizes[ensemble_dim])
+  if not members[0] <= n_member <= members[1]:
+    raise ValueError(f'{n_member} members: {noun} takes {members[0]} to '
+                     f'{members[1]}')
+  return n_member
+
+
+class ClassSumsTable(Metric):
+  """What the truth-led tables share (`CRPSTable`, `ConditionalTable`): the
+  region tables, the operands of every variable, the truth-led order of the
+  outer dims, the check on the ensemble sizes and the `region` / `term` / `bin`
+  coords.  A subclass states its `_terms`, makes its own checks and calls
+  `_tables` with the variables, n_bin(ensemble size) and
+
+    values(name, device, args, class_cols, wrow, mult)
+        one variable: [n_outer, n_region, term, bin], from the leading
+        arguments `args` of its sums (those of `engine.crps_bin_sums`)."""
+
+  ensemble_dim = _m.REALIZATION  # (a dataclass field of each subclass)
+  _terms = ()
+
+  _ensemble_size = events.ExceedanceTable._ensemble_size
+
+  def _tables(self, forecast, truth, names, region, regions, n_bin, values):
+    """(the table Dataset without its attrs, the ensemble size)."""
+    region_set = regions if regions is not None else {'region': region}
+    lat = xl.coord_values(forecast, 'latitude')
+    lon = xl.coord_values(forecast, 'longitude')
+    col_class, mult, wrow = events.column_classes(region_set, lat, lon)
+    class_cols = np.bincount(col_class, minlength=mult.shape[1])
+    out = xl.Dataset()
+    sizes = set()
+    per_var = {}
+    for name in names:
+      fvar, tvar = forecast[name], truth[name]
+      ops = events._operands(forecast, fvar, [tvar], self.ensemble_dim)
+      sizes.add(ops.n_member)
+      args = (ops.arrays[0], ops.member_stride, ops.n_member, ops.tables[0],
+              ops.arrays[1], ops.tables[1], ops.n_outer, len(lat), len(lon),
+              col_class, mult.shape[1])
+      v = values(name, ops.device, args, class_cols, wrow, mult)
+      v = v.reshape(ops.out_shape + v.shape[1:])
+      # outer dims as xarray orders the plain CRPS (truth-led)
+      order = [d for d in tvar.dims if d in ops.out_dims]
+      order += [d for d in fvar.dims if d in ops.out_dims and d not in order]
+      n_out = len(ops.out_dims)
+      axes = [ops.out_dims.index(d) for d in order] + [n_out + 1, n_out + 2]
+      if regions is not None:
+        v = np.transpose(v, [n_out] + axes)
+      else:
+        v = np.transpose(v, axes + [n_out])[..., 0]
+      per_var[name] = (tuple(order), np.ascontiguousarray(v))
+      out.coords.update(_m._result_coords(forecast, tuple(order)))
+    if len(sizes) > 1:
+      raise ValueError(f'the variables differ in ensemble size: {sizes}')
+    n_member = sizes.pop() if sizes else self._ensemble_size(forecast)
+    front = ('region',) if regions is not None else ()
+    if regions is not None:
+      out.coords['region'] = np.array(list(regions), dtype=object)
+    out.coords[TERM] = np.array(self._terms, dtype=object)
+    out.coords[BIN] = np.arange(n_bin(n_member), dtype=np.int64)
+    for name, (order, v) in per_var.items():
+      out.data_vars[name] = xl.DataArray(v, front + order + (TERM, BIN),
+                                         out.coords, name)
+    return out, n_member

@@ -43,16 +43,15 @@ import dataclasses
 import typing as t
 
 import numpy as np
-import torch
 
+from weatherbench2_amd import class_tables
 from weatherbench2_amd import engine
 from weatherbench2_amd import events
 from weatherbench2_amd import metrics as _m
 from weatherbench2_amd import xarray_lite as xl
-from weatherbench2_amd.metrics import Metric
 
 MIN_MEMBERS, MAX_MEMBERS = 1, 64  # those of wb2_crps_bins_geometry
-TERM, BIN = 'term', 'bin'
+TERM, BIN = class_tables.TERM, class_tables.BIN
 TERMS = ('alpha', 'beta', 'outlier')
 
 
@@ -88,19 +87,14 @@ def host_sums(ens: np.ndarray, member_stride: int, n_member: int, ens_slab,
   arrays instead of tensors), the same (float64 [n_outer, n_row, n_class, 2,
   M + 1], int32 [n_outer, n_row, n_class, 3]) result, the same order: per
   (row, class) one sequential chain over the columns in increasing order."""
-  ens, truth = ens.reshape(-1), truth.reshape(-1)
   slab = n_row * n_col
   cls = np.asarray(col_class, dtype=np.int64)
   sums = np.zeros((n_outer, n_row, n_class, 2, n_member + 1),
                   dtype=np.float64)
   cnt = np.zeros((n_outer, n_row, n_class, 3), dtype=np.int32)
-  at = lambda table, o: o if table is None else int(table[o])
-  for o in range(n_outer):
-    e0 = at(ens_slab, o) * slab
-    x = np.stack([ens[e0 + m * member_stride:e0 + m * member_stride + slab]
-                  for m in range(n_member)])
-    t0 = at(truth_slab, o) * slab
-    alpha, beta, below, above, bad = host_point_terms(x, truth[t0:t0 + slab])
+  for o, x, y in events.host_members(ens, member_stride, n_member, ens_slab,
+                                     truth, truth_slab, n_outer, slab):
+    alpha, beta, below, above, bad = host_point_terms(x, y)
     # [row, col, term, bin]
     v = np.stack([alpha, beta]).reshape(2, n_member + 1, n_row, n_col
                                         ).transpose(2, 3, 0, 1)
@@ -114,22 +108,14 @@ def host_sums(ens: np.ndarray, member_stride: int, n_member: int, ens_slab,
 
 def host_fold(sums: np.ndarray, cnt: np.ndarray, class_cols, wrow: np.ndarray,
               mult: np.ndarray) -> tuple:
-  """`engine.crps_bin_fold` in NumPy: s = s + float(mult[r, c]) * sums[o, i,
-  c] over the classes, then acc = acc + wrow[r, i] * s over the rows, both in
-  increasing order from 0.0; the counts (below, above, valid, invalid) as
-  `events.host_fold`."""
-  n_outer, n_row, n_class = sums.shape[:3]
-  multf = mult.astype(np.float64)
-  acc = np.zeros((n_outer, wrow.shape[0]) + sums.shape[3:], dtype=np.float64)
-  for i in range(n_row):
-    s = np.zeros_like(acc)
-    for c in range(n_class):
-      s = s + multf[None, :, c, None, None] * sums[:, None, i, c]
-    acc = acc + wrow[None, :, i, None, None] * s
+  """`engine.crps_bin_fold` in NumPy: the sums as `class_tables.host_fold`
+  (classes, then rows, in increasing order from 0.0); the counts (below,
+  above, valid, invalid) as `events.host_fold`."""
   invalid = np.asarray(class_cols, dtype=np.int32).reshape(1, 1, -1
                                                            ) - cnt[..., 2]
   cnt4 = np.concatenate([cnt, invalid[..., None].astype(np.int32)], axis=-1)
-  return acc, events.host_fold(cnt4[None], wrow, mult)[0]
+  return (class_tables.host_fold(sums, wrow, mult),
+          events.host_fold(cnt4[None], wrow, mult)[0])
 
 
 def normalize(table: np.ndarray, counts: np.ndarray, skipna: bool
@@ -155,7 +141,7 @@ def normalize(table: np.ndarray, counts: np.ndarray, skipna: bool
 # the metric
 # ---------------------------------------------------------------------------
 @dataclasses.dataclass
-class CRPSTable(Metric):
+class CRPSTable(class_tables.ClassSumsTable):
   """Per-rank-bin CRPS table of an ensemble forecast.
 
   Per common variable the result has dims (<outer dims in the order the plain
@@ -174,6 +160,7 @@ class CRPSTable(Metric):
   # one pass over the points answers every region; no windows of chunks
   _fused_regions = True
   _reads_slabs_in_place = False
+  _terms = TERMS
 
   def _result_attrs(self, forecast):
     return {'ensemble_size': int(forecast.sizes[self.ensemble_dim])}
@@ -182,64 +169,21 @@ class CRPSTable(Metric):
                     regions: t.Optional[dict] = None):
     forecast, truth = _m._inputs(forecast, truth)
     _m._get_n_ensemble(forecast, self.ensemble_dim)
-    region_set = regions if regions is not None else {'region': region}
-    lat = xl.coord_values(forecast, 'latitude')
-    lon = xl.coord_values(forecast, 'longitude')
-    col_class, mult, wrow = events.column_classes(region_set, lat, lon)
-    class_cols = np.bincount(col_class, minlength=mult.shape[1])
-    out = xl.Dataset()
-    sizes = set()
-    per_var = {}
-    for name in _m._common_vars(forecast, truth):
-      fvar, tvar = forecast[name], truth[name]
+    names = list(_m._common_vars(forecast, truth))
+    for name in names:
+      fvar = forecast[name]
       if self.ensemble_dim not in fvar.dims:
         raise ValueError(f'variable {name!r} has no {self.ensemble_dim!r} dim')
-      for da in (fvar, tvar):
-        if _m._torch_dtype_of(da.data) not in (torch.float32, torch.float64):
-          raise ValueError(f'variable {name!r} is {da.data.dtype}: the CRPS '
-                           'table takes float32 and float64')
-      n_member = int(fvar.sizes[self.ensemble_dim])
-      if not MIN_MEMBERS <= n_member <= MAX_MEMBERS:
-        raise ValueError(f'{n_member} members: the CRPS table takes '
-                         f'{MIN_MEMBERS} to {MAX_MEMBERS}')
-      ops = events._operands(forecast, fvar, [tvar], self.ensemble_dim)
-      sizes.add(ops.n_member)
-      args = (ops.arrays[0], ops.member_stride, ops.n_member, ops.tables[0],
-              ops.arrays[1], ops.tables[1], ops.n_outer, len(lat), len(lon),
-              col_class, mult.shape[1])
-      if ops.device is None:
-        table, counts = host_fold(*host_sums(*args), class_cols, wrow, mult)
-      else:
-        table, counts = engine.crps_bin_fold(*engine.crps_bin_sums(*args),
-                                             class_cols, wrow, mult)
-        engine.order_read(table)
-        engine.order_read(counts)
-        table, counts = table.cpu().numpy(), counts.cpu().numpy()
-      v = normalize(table, counts, skipna)  # [outer, R, 3, M + 1]
-      v = v.reshape(ops.out_shape + v.shape[1:])
-      # outer dims as xarray orders the plain CRPS (truth-led)
-      order = [d for d in tvar.dims if d in ops.out_dims]
-      order += [d for d in fvar.dims if d in ops.out_dims and d not in order]
-      n_out = len(ops.out_dims)
-      axes = [ops.out_dims.index(d) for d in order] + [n_out + 1, n_out + 2]
-      if regions is not None:
-        v = np.transpose(v, [n_out] + axes)
-      else:
-        v = np.transpose(v, axes + [n_out])[..., 0]
-      per_var[name] = (tuple(order), np.ascontiguousarray(v))
-      out.coords.update(_m._result_coords(forecast, tuple(order)))
-    if len(sizes) > 1:
-      raise ValueError(f'the variables differ in ensemble size: {sizes}')
-    n_member = sizes.pop() if sizes else int(
-        forecast.sizes[self.ensemble_dim])
-    front = ('region',) if regions is not None else ()
-    if regions is not None:
-      out.coords['region'] = np.array(list(regions), dtype=object)
-    out.coords[TERM] = np.array(TERMS, dtype=object)
-    out.coords[BIN] = np.arange(n_member + 1, dtype=np.int64)
-    for name, (order, v) in per_var.items():
-      out.data_vars[name] = xl.DataArray(v, front + order + (TERM, BIN),
-                                         out.coords, name)
+      class_tables.check_variable(name, fvar, truth[name], self.ensemble_dim,
+                                  'the CRPS table', (MIN_MEMBERS, MAX_MEMBERS))
+
+    def values(name, device, args, class_cols, wrow, mult):
+      table, counts = class_tables.region_sums(
+          device, args, (host_sums, host_fold),
+          (engine.crps_bin_sums, engine.crps_bin_fold), class_cols, wrow, mult)
+      return normalize(table, counts, skipna)  # [outer, R, 3, M + 1]
+    out, n_member = self._tables(forecast, truth, names, region, regions,
+                                 lambda n_member: n_member + 1, values)
     return out.assign_attrs(ensemble_size=n_member)
 
 

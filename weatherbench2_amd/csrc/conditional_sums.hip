@@ -37,12 +37,14 @@
 // (row, class, bin, term) is ONE sequential chain over its columns in
 // increasing order, whatever the tiles are.  Plain stores, no atomics of any
 // kind.
+//
+// The requests of a tile, the mask of class changes and the host side are
+// class_sums.hpp's, shared with K21 (the host side with K20 too).
 
 #include <cstdint>
 
+#include "class_sums.hpp"
 #include "common.hpp"
-#include "ensemble_kernels.hpp"
-#include "event_common.hpp"
 #include "launch_common.hpp"
 #include "trace.hpp"
 #include "wb2hip.h"
@@ -50,7 +52,6 @@
 namespace wb2 {
 namespace {
 
-constexpr int kCondMaxMember = 64;  // K20's range
 constexpr int kCondMaxEdge = kWave - 1;  // lane b owns bin b: one wave of bins
 constexpr int kCondTerm = 4;        // mu, y, s2, se
 constexpr char kCondTakes[] = "the conditional sums take";
@@ -125,22 +126,10 @@ __global__ void __launch_bounds__(kWave)
     const bool active = col0 + lane < p.n_col;
     // a lane past the end of the row reads its last column again
     const int colc = active ? col0 + lane : p.n_col - 1;
-    const int cls_v = p.col_class[colc];
-    const T y = tb[colc];
-    // every member is requested before any is looked at: the bases are
-    // wave-uniform (K3's buffer loads), a slot >= M is switched off through
-    // its descriptor and costs no memory access.  (The stride and the member
-    // count are made opaque per tile, as in K20: hipcc then keeps neither the
-    // NPAD bases nor the NPAD lane masks in SGPRs across the tile loop.)
-    long long stride = p.member_stride;
-    int Mt = M;
-    asm volatile("" : "+s"(stride), "+s"(Mt));
-    const int lane_bytes = colc * (int)sizeof(T);
-    T x[NPAD];
-#pragma unroll
-    for (int m = 0; m < NPAD; ++m)
-      x[m] = member_load<T, true>(xb + m * stride, lane_bytes,
-                                  m < Mt ? 0x7fffffff : 0);
+    int cls_v, Mt;
+    T y, x[NPAD];
+    class_tile<T, NPAD>(xb, tb, p.col_class, p.member_stride, M, colc, cls_v, y,
+                        Mt, x, [] {});
     // (a NaN member makes S, and with it every value, NaN: the point is then
     // stored with bin -1 and no lane adds it)
     bool bad = is_nan(y);
@@ -170,12 +159,7 @@ __global__ void __launch_bounds__(kWave)
     for (int k = 0; k < n_edge; ++k) bin += lane_f64(my_edge, k) <= v ? 1 : 0;
     if (!active || bad) bin = -1;
 
-    // bit j: column j opens another class than column j - 1 (bit 0: than the
-    // running sums)
-    const int c_first = __builtin_amdgcn_readlane(cls_v, 0);
-    const int cls_left = __shfl_up(cls_v, 1);
-    const unsigned long long change =
-        __ballot(lane > 0 && cls_v != cls_left) | (c_first != cur ? 1ull : 0ull);
+    const unsigned long long change = class_change(cls_v, cur, lane);
 
     // the DS operations of one wave execute in order; the fences restrain the
     // compiler
@@ -250,31 +234,12 @@ inline long long cond_lds_bytes() {
 }
 
 inline int cond_shape(int dtype, int n_member, int n_class, int n_edge) {
-  WB2_REQUIRE(dtype == WB2_F32 || dtype == WB2_F64, "unknown dtype %d", dtype);
-  WB2_REQUIRE(n_member >= 1 && n_member <= kCondMaxMember,
-              "n_member=%d: %s 1 to %d members", n_member, kCondTakes,
-              kCondMaxMember);
-  WB2_REQUIRE(n_class >= 1 && n_class <= kExceedMaxClass,
-              "n_class=%d: %s 1 to %d column classes", n_class, kCondTakes,
-              kExceedMaxClass);
+  if (const int rc = class_shape(kCondTakes, dtype, n_member, n_class))
+    return rc;
   WB2_REQUIRE(n_edge >= 0 && n_edge <= kCondMaxEdge,
               "n_edge=%d: %s 0 to %d bin edges", n_edge, kCondTakes,
               kCondMaxEdge);
   return 0;
-}
-
-template <typename T>
-void cond_launch(int n_member, dim3 grid, dim3 block, hipStream_t s,
-                 const CondParams& p) {
-#define WB2_COND_CASE(NPAD)                                                  \
-  hipLaunchKernelGGL((conditional_sums_kernel<T, NPAD>), grid, block, 0, s, p)
-  if (n_member <= 2) WB2_COND_CASE(2);
-  else if (n_member <= 4) WB2_COND_CASE(4);
-  else if (n_member <= 8) WB2_COND_CASE(8);
-  else if (n_member <= 16) WB2_COND_CASE(16);
-  else if (n_member <= 32) WB2_COND_CASE(32);
-  else WB2_COND_CASE(64);
-#undef WB2_COND_CASE
 }
 
 }  // namespace
@@ -289,17 +254,11 @@ int wb2_conditional_geometry(int dtype, int32_t n_member, int32_t n_class,
                              int64_t* lds_bytes, int32_t* max_grid_outer) {
   using namespace wb2;
   if (const int rc = cond_shape(dtype, n_member, n_class, n_edge)) return rc;
-  WB2_REQUIRE(min_member && max_member && max_edges && tile_cols &&
-              rows_per_group && lds_bytes && max_grid_outer,
-              "null pointer argument");
-  *min_member = 1;
-  *max_member = kCondMaxMember;
+  WB2_REQUIRE(max_edges && lds_bytes, "null pointer argument");
   *max_edges = kCondMaxEdge;
-  *tile_cols = kWave;
-  *rows_per_group = 1;
   *lds_bytes = cond_lds_bytes();
-  *max_grid_outer = (int32_t)kGridOuter;
-  return 0;
+  return class_geometry(min_member, max_member, tile_cols, rows_per_group,
+                        max_grid_outer);
 }
 
 int wb2_conditional_sums(int dtype, const void* ens, const int64_t* ens_slab,
@@ -314,42 +273,24 @@ int wb2_conditional_sums(int dtype, const void* ens, const int64_t* ens_slab,
   if (const int rc = cond_shape(dtype, n_member, n_class, n_edge)) return rc;
   WB2_REQUIRE(mode >= 0 && mode <= 2, "mode=%d: %s 0 (spread), 1 (forecast) "
               "or 2 (truth)", mode, kCondTakes);
-  WB2_REQUIRE(member_stride >= 0, "member_stride=%lld is negative",
-              (long long)member_stride);
-  WB2_EMPTY_OK(n_outer);
-  WB2_EMPTY_OK(n_row);
-  WB2_EMPTY_OK(n_col);
-  WB2_REQUIRE(ens && truth && col_class && sums && cnt &&
-              (edges || n_edge == 0), "null pointer argument");
-  // (a lane's byte offset into its row is an int)
-  WB2_REQUIRE((long long)n_col * 8 < (1ll << 31), "n_col=%d: the row is too "
-              "long", (int)n_col);
   CondParams p{};
-  p.ens = ens;
-  p.truth = truth;
-  p.ens_slab = reinterpret_cast<const long long*>(ens_slab);
-  p.truth_slab = reinterpret_cast<const long long*>(truth_slab);
-  p.col_class = col_class;
+  const int go = member_operands(ens, ens_slab, truth, truth_slab, n_member,
+                                 member_stride, n_outer, n_row, n_col, &p);
+  if (go <= 0) return go;
+  WB2_REQUIRE(edges || n_edge == 0, "null pointer argument");
+  if (const int rc = class_operands(col_class, sums, cnt, n_row, n_col,
+                                    n_class, &p))
+    return rc;
   p.edges = edges;
-  p.sums = sums;
-  p.cnt = cnt;
-  p.member_stride = member_stride;
-  p.n_outer = n_outer;
-  p.n_member = n_member;
-  p.n_row = n_row;
-  p.n_col = n_col;
-  p.n_class = n_class;
   p.n_edge = n_edge;
   p.mode = mode;
-  dim3 grid;
-  WB2_REQUIRE(outer_grid(n_outer, n_row, &grid),
-              "the grid does not fit: %lld outer indices of %d rows",
-              (long long)n_outer, (int)n_row);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == WB2_F32)
-    cond_launch<float>(n_member, grid, dim3(kWave), s, p);
-  else
-    cond_launch<double>(n_member, grid, dim3(kWave), s, p);
+  dim3 grid, block;
+  if (const int rc = class_grid(n_outer, n_row, &grid, &block)) return rc;
+  for_npad(dtype, n_member, [&](auto T0, auto N) {
+    hipLaunchKernelGGL(
+        (conditional_sums_kernel<decltype(T0), decltype(N)::value>), grid,
+        block, 0, static_cast<hipStream_t>(stream), p);
+  });
   WB2_HIP_OK(hipGetLastError());
   return 0;
 }

@@ -34,13 +34,17 @@
 // met it): the sum of a (row, class) is ONE sequential chain over its columns
 // in increasing order, whatever the tiles are.  The outlier counts are the
 // signs of lane 0's two terms.  Plain stores, no atomics of any kind.
+//
+// The host side is class_sums.hpp's, shared with K21 and K24.  The kernel keeps
+// its own copy of that layer's class_tile() and class_change(): with either
+// inlined the float32 64-slot form is 1.6 % slower (profiles/NOTES.md).
 
 #include <cstdint>
 #include <limits>
 
+#include "class_sums.hpp"
 #include "common.hpp"
 #include "ensemble_kernels.hpp"
-#include "event_common.hpp"
 #include "launch_common.hpp"
 #include "trace.hpp"
 #include "wb2hip.h"
@@ -48,7 +52,6 @@
 namespace wb2 {
 namespace {
 
-constexpr int kCrpsMaxMember = 64;  // lane b owns bin b: one wave of bins
 constexpr int kCrpsPitch = kWave + 1;
 constexpr int kCrpsFoldThreads = 256;  // (the sums kernel: one wave)
 constexpr char kCrpsTakes[] = "the CRPS bin sums take";
@@ -284,31 +287,6 @@ inline long long crps_lds_bytes(int dtype, int n_member) {
   return (long long)(n_member + 1) * kCrpsPitch * (dtype == WB2_F32 ? 4 : 8);
 }
 
-inline int crps_shape(int dtype, int n_member, int n_class) {
-  WB2_REQUIRE(dtype == WB2_F32 || dtype == WB2_F64, "unknown dtype %d", dtype);
-  WB2_REQUIRE(n_member >= 1 && n_member <= kCrpsMaxMember,
-              "n_member=%d: %s 1 to %d members", n_member, kCrpsTakes,
-              kCrpsMaxMember);
-  WB2_REQUIRE(n_class >= 1 && n_class <= kExceedMaxClass,
-              "n_class=%d: %s 1 to %d column classes", n_class, kCrpsTakes,
-              kExceedMaxClass);
-  return 0;
-}
-
-template <typename T>
-void crps_launch(int n_member, dim3 grid, dim3 block, size_t lds,
-                 hipStream_t s, const CrpsParams& p) {
-#define WB2_CRPS_CASE(NPAD)                                                 \
-  hipLaunchKernelGGL((crps_bin_sums_kernel<T, NPAD>), grid, block, lds, s, p)
-  if (n_member <= 2) WB2_CRPS_CASE(2);
-  else if (n_member <= 4) WB2_CRPS_CASE(4);
-  else if (n_member <= 8) WB2_CRPS_CASE(8);
-  else if (n_member <= 16) WB2_CRPS_CASE(16);
-  else if (n_member <= 32) WB2_CRPS_CASE(32);
-  else WB2_CRPS_CASE(64);
-#undef WB2_CRPS_CASE
-}
-
 }  // namespace
 }  // namespace wb2
 
@@ -319,16 +297,12 @@ int wb2_crps_bins_geometry(int dtype, int32_t n_member, int32_t n_class,
                            int32_t* tile_cols, int32_t* rows_per_group,
                            int64_t* lds_bytes, int32_t* max_grid_outer) {
   using namespace wb2;
-  if (const int rc = crps_shape(dtype, n_member, n_class)) return rc;
-  WB2_REQUIRE(min_member && max_member && tile_cols && rows_per_group &&
-              lds_bytes && max_grid_outer, "null pointer argument");
-  *min_member = 1;
-  *max_member = kCrpsMaxMember;
-  *tile_cols = kWave;
-  *rows_per_group = 1;
+  if (const int rc = class_shape(kCrpsTakes, dtype, n_member, n_class))
+    return rc;
+  WB2_REQUIRE(lds_bytes, "null pointer argument");
   *lds_bytes = crps_lds_bytes(dtype, n_member);
-  *max_grid_outer = (int32_t)kGridOuter;
-  return 0;
+  return class_geometry(min_member, max_member, tile_cols, rows_per_group,
+                        max_grid_outer);
 }
 
 int wb2_crps_bin_sums(int dtype, const void* ens, const int64_t* ens_slab,
@@ -339,39 +313,22 @@ int wb2_crps_bin_sums(int dtype, const void* ens, const int64_t* ens_slab,
                       void* stream) {
   WB2_TRACE();
   using namespace wb2;
-  if (const int rc = crps_shape(dtype, n_member, n_class)) return rc;
-  WB2_REQUIRE(member_stride >= 0, "member_stride=%lld is negative",
-              (long long)member_stride);
-  WB2_EMPTY_OK(n_outer);
-  WB2_EMPTY_OK(n_row);
-  WB2_EMPTY_OK(n_col);
-  WB2_REQUIRE(ens && truth && col_class && sums && cnt,
-              "null pointer argument");
+  if (const int rc = class_shape(kCrpsTakes, dtype, n_member, n_class))
+    return rc;
   CrpsParams p{};
-  p.ens = ens;
-  p.truth = truth;
-  p.ens_slab = reinterpret_cast<const long long*>(ens_slab);
-  p.truth_slab = reinterpret_cast<const long long*>(truth_slab);
-  p.col_class = col_class;
-  p.sums = sums;
-  p.cnt = cnt;
-  p.member_stride = member_stride;
-  p.n_outer = n_outer;
-  p.n_member = n_member;
-  p.n_row = n_row;
-  p.n_col = n_col;
-  p.n_class = n_class;
-  dim3 grid;
-  WB2_REQUIRE(outer_grid(n_outer, n_row, &grid),
-              "the grid does not fit: %lld outer indices of %d rows",
-              (long long)n_outer, (int)n_row);
-  const dim3 block(kWave);
+  const int go = member_operands(ens, ens_slab, truth, truth_slab, n_member,
+                                 member_stride, n_outer, n_row, n_col, &p);
+  if (go <= 0) return go;
+  if (const int rc = class_operands(col_class, sums, cnt, n_row, n_col,
+                                    n_class, &p))
+    return rc;
+  dim3 grid, block;
+  if (const int rc = class_grid(n_outer, n_row, &grid, &block)) return rc;
   const size_t lds = (size_t)crps_lds_bytes(dtype, n_member);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == WB2_F32)
-    crps_launch<float>(n_member, grid, block, lds, s, p);
-  else
-    crps_launch<double>(n_member, grid, block, lds, s, p);
+  for_npad(dtype, n_member, [&](auto T0, auto N) {
+    hipLaunchKernelGGL((crps_bin_sums_kernel<decltype(T0), decltype(N)::value>),
+                       grid, block, lds, static_cast<hipStream_t>(stream), p);
+  });
   WB2_HIP_OK(hipGetLastError());
   return 0;
 }

@@ -15,6 +15,8 @@
 // What a kernel does with those -- K18 counts them, K19 stores them -- is all
 // that is its own.  Host: the checks, the wide decision, the threshold batches
 // and the NT dispatch that the two entry points share.
+// The class-sums kernels (class_sums.hpp: K20, K21, K24) address their members
+// and truth likewise: exceed_slab() and member_operands() serve them too.
 #pragma once
 
 #include <cstdint>
@@ -127,24 +129,21 @@ inline int exceed_shape(const char* takes, int dtype, int n_member,
   return 0;
 }
 
-// After exceed_shape(): checks the operands that wb2_event_counts and
-// wb2_event_codes share and fills *q (thr[] and thr_slab[] are
-// exceed_batches()'s).  1: go on; 0: no points, a legal no-op; negative:
-// refused.
-inline int exceed_operands(const void* ens, const int64_t* ens_slab,
-                           const void* truth, const int64_t* truth_slab,
-                           const void* const* threshold, int n_threshold,
-                           int n_member, long long member_stride,
-                           long long n_outer, int n_row, int n_col,
-                           ExceedOperands* q) {
+// After the shape checks: checks the members and the truth and fills the
+// fields of *q that address them (any parameter struct that names them as
+// ExceedOperands does: the class-sums kernels without thresholds keep their
+// own).  1: go on; 0: no points, a legal no-op; negative: refused.
+template <class P>
+int member_operands(const void* ens, const int64_t* ens_slab,
+                    const void* truth, const int64_t* truth_slab, int n_member,
+                    long long member_stride, long long n_outer, int n_row,
+                    int n_col, P* q) {
   WB2_REQUIRE(member_stride >= 0, "member_stride=%lld is negative",
               member_stride);
   WB2_EMPTY_OK(n_outer);
   WB2_EMPTY_OK(n_row);
   WB2_EMPTY_OK(n_col);
-  WB2_REQUIRE(ens && truth && threshold, "null pointer argument");
-  for (int t = 0; t < n_threshold; ++t)
-    WB2_REQUIRE(threshold[t], "null pointer argument (threshold %d)", t);
+  WB2_REQUIRE(ens && truth, "null pointer argument");
   q->ens = ens;
   q->truth = truth;
   q->ens_slab = reinterpret_cast<const long long*>(ens_slab);
@@ -152,6 +151,23 @@ inline int exceed_operands(const void* ens, const int64_t* ens_slab,
   q->member_stride = member_stride;
   q->n_outer = n_outer;
   q->n_member = n_member;
+  return 1;
+}
+
+// member_operands() and the thresholds that wb2_event_counts, wb2_event_codes
+// and wb2_twcrps_sums share (thr[] and thr_slab[] are exceed_batches()'s).
+inline int exceed_operands(const void* ens, const int64_t* ens_slab,
+                           const void* truth, const int64_t* truth_slab,
+                           const void* const* threshold, int n_threshold,
+                           int n_member, long long member_stride,
+                           long long n_outer, int n_row, int n_col,
+                           ExceedOperands* q) {
+  const int go = member_operands(ens, ens_slab, truth, truth_slab, n_member,
+                                 member_stride, n_outer, n_row, n_col, q);
+  if (go <= 0) return go;
+  WB2_REQUIRE(threshold, "null pointer argument");
+  for (int t = 0; t < n_threshold; ++t)
+    WB2_REQUIRE(threshold[t], "null pointer argument (threshold %d)", t);
   return 1;
 }
 

@@ -38,13 +38,17 @@
 // over its columns in increasing order, whatever the tiles are.  The valid
 // counts come from the ballots of the per-threshold validity.  Plain stores,
 // no atomics of any kind.
+//
+// The requests of a tile, the mask of class changes and the host side are
+// class_sums.hpp's, shared with K24 (the host side with K20 too); the threshold
+// batches are event_common.hpp's, shared with K18 and K19.
 
 #include <cstdint>
 #include <limits>
 
+#include "class_sums.hpp"
 #include "common.hpp"
 #include "ensemble_kernels.hpp"
-#include "event_common.hpp"
 #include "launch_common.hpp"
 #include "trace.hpp"
 #include "wb2hip.h"
@@ -52,7 +56,6 @@
 namespace wb2 {
 namespace {
 
-constexpr int kTwMaxMember = 64;  // K20's range and its padded networks
 constexpr int kTwPitch = kWave + 1;
 constexpr char kTwTakes[] = "the twCRPS sums take";
 
@@ -114,25 +117,13 @@ __global__ void __launch_bounds__(kWave)
     const bool active = col0 + lane < p.n_col;
     // a lane past the end of the row reads its last column again
     const int colc = active ? col0 + lane : p.n_col - 1;
-    const int cls_v = p.col_class[colc];
-    const T y = tb[colc];
-    T hv[kExceedThr];
+    int cls_v, Mt;
+    T y, x[NPAD], hv[kExceedThr];
+    class_tile<T, NPAD>(xb, tb, p.col_class, p.member_stride, M, colc, cls_v, y,
+                        Mt, x, [&] {
 #pragma unroll
-    for (int q = 0; q < kExceedThr; ++q) hv[q] = q < nt ? hb[q][colc] : T(0);
-    // every member is requested before any is looked at: the bases are
-    // wave-uniform (K3's buffer loads), a slot >= M is switched off through
-    // its descriptor and costs no memory access.  (The stride and the member
-    // count are made opaque per tile, as in K20: hipcc then keeps neither the
-    // NPAD bases nor the NPAD lane masks in SGPRs across the tile loop.)
-    long long stride = p.member_stride;
-    int Mt = M;
-    asm volatile("" : "+s"(stride), "+s"(Mt));
-    const int lane_bytes = colc * (int)sizeof(T);
-    T x[NPAD];
-#pragma unroll
-    for (int m = 0; m < NPAD; ++m)
-      x[m] = member_load<T, true>(xb + m * stride, lane_bytes,
-                                  m < Mt ? 0x7fffffff : 0);
+      for (int q = 0; q < kExceedThr; ++q) hv[q] = q < nt ? hb[q][colc] : T(0);
+    });
     bool bad = is_nan(y);
 #pragma unroll
     for (int m = 0; m < NPAD; ++m) {
@@ -143,12 +134,7 @@ __global__ void __launch_bounds__(kWave)
       x[m] = live ? vmin(x[m], inf) : inf;
     }
     if (M > 1) sort_network<NPAD, NPAD>(x);
-    // bit j: column j opens another class than column j - 1 (bit 0: than the
-    // running sum)
-    const int c_first = __builtin_amdgcn_readlane(cls_v, 0);
-    const int cls_left = __shfl_up(cls_v, 1);
-    const unsigned long long change =
-        __ballot(lane > 0 && cls_v != cls_left) | (c_first != cur ? 1ull : 0ull);
+    const unsigned long long change = class_change(cls_v, cur, lane);
 
     // the DS operations of one wave execute in order; the fences restrain the
     // compiler
@@ -226,29 +212,9 @@ inline long long tw_lds_bytes(int nt) {
 }
 
 inline int tw_shape(int dtype, int n_member, int n_class, int n_threshold) {
-  WB2_REQUIRE(dtype == WB2_F32 || dtype == WB2_F64, "unknown dtype %d", dtype);
-  WB2_REQUIRE(n_member >= 1 && n_member <= kTwMaxMember,
-              "n_member=%d: %s 1 to %d members", n_member, kTwTakes,
-              kTwMaxMember);
-  WB2_REQUIRE(n_class >= 1 && n_class <= kExceedMaxClass,
-              "n_class=%d: %s 1 to %d column classes", n_class, kTwTakes,
-              kExceedMaxClass);
+  if (const int rc = class_shape(kTwTakes, dtype, n_member, n_class)) return rc;
   WB2_REQUIRE(n_threshold >= 1, "n_threshold=%d", n_threshold);
   return 0;
-}
-
-template <typename T>
-void tw_launch(int n_member, dim3 grid, dim3 block, size_t lds, hipStream_t s,
-               const TwParams& p) {
-#define WB2_TW_CASE(NPAD)                                                  \
-  hipLaunchKernelGGL((twcrps_sums_kernel<T, NPAD>), grid, block, lds, s, p)
-  if (n_member <= 2) WB2_TW_CASE(2);
-  else if (n_member <= 4) WB2_TW_CASE(4);
-  else if (n_member <= 8) WB2_TW_CASE(8);
-  else if (n_member <= 16) WB2_TW_CASE(16);
-  else if (n_member <= 32) WB2_TW_CASE(32);
-  else WB2_TW_CASE(64);
-#undef WB2_TW_CASE
 }
 
 }  // namespace
@@ -263,17 +229,11 @@ int wb2_twcrps_geometry(int dtype, int32_t n_member, int32_t n_class,
                         int64_t* lds_bytes, int32_t* max_grid_outer) {
   using namespace wb2;
   if (const int rc = tw_shape(dtype, n_member, n_class, n_threshold)) return rc;
-  WB2_REQUIRE(min_member && max_member && thresholds_per_launch && tile_cols &&
-              rows_per_group && lds_bytes && max_grid_outer,
-              "null pointer argument");
-  *min_member = 1;
-  *max_member = kTwMaxMember;
+  WB2_REQUIRE(thresholds_per_launch && lds_bytes, "null pointer argument");
   *thresholds_per_launch = n_threshold < kExceedThr ? n_threshold : kExceedThr;
-  *tile_cols = kWave;
-  *rows_per_group = 1;
   *lds_bytes = tw_lds_bytes(*thresholds_per_launch);
-  *max_grid_outer = (int32_t)kGridOuter;
-  return 0;
+  return class_geometry(min_member, max_member, tile_cols, rows_per_group,
+                        max_grid_outer);
 }
 
 int wb2_twcrps_sums(int dtype, const void* ens, const int64_t* ens_slab,
@@ -291,32 +251,24 @@ int wb2_twcrps_sums(int dtype, const void* ens, const int64_t* ens_slab,
                                  n_threshold, n_member, member_stride, n_outer,
                                  n_row, n_col, &p);
   if (go <= 0) return go;
-  WB2_REQUIRE(col_class && sums && cnt, "null pointer argument");
-  // (a lane's byte offset into its row is an int)
-  WB2_REQUIRE((long long)n_col * 8 < (1ll << 31), "n_col=%d: the row is too "
-              "long", (int)n_col);
-  p.col_class = col_class;
+  if (const int rc = class_operands(col_class, sums, cnt, n_row, n_col,
+                                    n_class, &p))
+    return rc;
   p.thr_cells = (long long)n_outer * n_row * n_class;
-  p.n_row = n_row;
-  p.n_col = n_col;
-  p.n_class = n_class;
   p.lower = lower != 0;
-  dim3 grid;
-  WB2_REQUIRE(outer_grid(n_outer, n_row, &grid),
-              "the grid does not fit: %lld outer indices of %d rows",
-              (long long)n_outer, (int)n_row);
-  const dim3 block(kWave);
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  dim3 grid, block;
+  if (const int rc = class_grid(n_outer, n_row, &grid, &block)) return rc;
   return exceed_batches(
       &p, threshold, thr_slab, n_threshold, kExceedThr, [&](int t0, int nt) {
         p.sums = sums + t0 * p.thr_cells * 2;
         p.cnt = cnt + t0 * p.thr_cells;
         p.nt = nt;
-        const size_t lds = (size_t)tw_lds_bytes(nt);
-        if (dtype == WB2_F32)
-          tw_launch<float>(n_member, grid, block, lds, s, p);
-        else
-          tw_launch<double>(n_member, grid, block, lds, s, p);
+        for_npad(dtype, n_member, [&](auto T0, auto N) {
+          hipLaunchKernelGGL(
+              (twcrps_sums_kernel<decltype(T0), decltype(N)::value>), grid,
+              block, (size_t)tw_lds_bytes(nt),
+              static_cast<hipStream_t>(stream), p);
+        });
       });
 }
 

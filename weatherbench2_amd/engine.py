@@ -1814,16 +1814,14 @@ def _event_slabs(table, n_outer: int, x: torch.Tensor, slab: int, extra: int,
   return table
 
 
-def _event_front(ens, member_stride, n_member, ens_slab, truth, truth_slab,
-                 thresholds, thr_slabs, n_outer, n_row, n_col):
-  """The preparation of the event front ends (K18 counts, K19 codes): the
-  operand checks, then the HOST slab tables, checked against the operands'
-  storage (`_event_slabs`) and uploaded.  ((n_threshold, n_member, n_outer,
-  n_row, n_col) as ints, the leading C arguments that wb2_event_counts and
-  wb2_event_codes share -- None where there is no point: nothing to upload)."""
-  thresholds = list(thresholds)
-  if not thresholds:
-    raise ValueError('no thresholds')
+def _member_front(ens, member_stride, n_member, ens_slab, truth, truth_slab,
+                  n_outer, n_row, n_col, thresholds=(), thr_slabs=None):
+  """The preparation of every front end that reads members against a truth
+  (K18 - K21, K24): the operand checks, then the HOST slab tables, checked
+  against the operands' storage (`_event_slabs`) and uploaded.  ((n_member,
+  member_stride, n_outer, n_row, n_col) as ints; the C arguments (dtype, ens,
+  ens_slab, truth, truth_slab) or, without a point, None; the device table of
+  the thresholds' slabs or None)."""
   _require_float(ens, truth, *thresholds)
   # (`ens` may be a view whose whole slabs its table addresses)
   _check_contiguous(ens.device, 'the device of the members', truth,
@@ -1842,9 +1840,9 @@ def _event_front(ens, member_stride, n_member, ens_slab, truth, truth_slab,
   ts = _event_slabs(truth_slab, n_outer, truth, slab, 0, 'truth')
   hs = [_event_slabs(tb, n_outer, x, slab, 0, 'threshold')
         for tb, x in zip(thr_slabs, thresholds)]
-  sizes = (len(thresholds), n_member, n_outer, n_row, n_col)
+  sizes = (n_member, member_stride, n_outer, n_row, n_col)
   if slab * n_outer == 0:
-    return sizes, None
+    return sizes, None, None
   dev = ens.device
   hs_dev = None
   if any(tb is not None for tb in hs):
@@ -1855,9 +1853,34 @@ def _event_front(ens, member_stride, n_member, ens_slab, truth, truth_slab,
                  _lib.ptr(ens), _lib.ptr(None if es is None else
                                          upload_table(es, dev)),
                  _lib.ptr(truth), _lib.ptr(None if ts is None else
-                                           upload_table(ts, dev)),
-                 _lib.ptr_array(thresholds), _lib.ptr(hs_dev), len(thresholds),
-                 n_member, member_stride, n_outer, n_row, n_col)
+                                           upload_table(ts, dev))), hs_dev
+
+
+def _event_front(ens, member_stride, n_member, ens_slab, truth, truth_slab,
+                 thresholds, thr_slabs, n_outer, n_row, n_col):
+  """`_member_front` with thresholds (K18 counts, K19 codes, K21 sums):
+  ((n_threshold, n_member, n_outer, n_row, n_col) as ints, the leading C
+  arguments that wb2_event_counts, wb2_event_codes and wb2_twcrps_sums share
+  -- None where there is no point: nothing to upload)."""
+  thresholds = list(thresholds)
+  if not thresholds:
+    raise ValueError('no thresholds')
+  (n_member, member_stride, n_outer, n_row, n_col), args, hs_dev = (
+      _member_front(ens, member_stride, n_member, ens_slab, truth, truth_slab,
+                    n_outer, n_row, n_col, thresholds, thr_slabs))
+  sizes = (len(thresholds), n_member, n_outer, n_row, n_col)
+  if args is None:
+    return sizes, None
+  return sizes, args + (_lib.ptr_array(thresholds), _lib.ptr(hs_dev),
+                        len(thresholds), n_member, member_stride, n_outer,
+                        n_row, n_col)
+
+
+def _check_members(n_member, geo: dict, takes: str) -> None:
+  """`n_member` against a geometry dict ('the CRPS bin sums take')."""
+  if not geo['min_member'] <= int(n_member) <= geo['max_member']:
+    raise ValueError(f'{int(n_member)} members: {takes} '
+                     f"{geo['min_member']} to {geo['max_member']}")
 
 
 def _column_classes(col_class, n_col: int, n_class: int) -> np.ndarray:
@@ -1899,6 +1922,42 @@ def event_counts(ens: torch.Tensor, member_stride: int, n_member: int,
   return out
 
 
+def _fold_weights(wrow, mult, n_row: int, n_class: int, class_cols=None
+                  ) -> tuple:
+  """The HOST operands of a fold as it takes them: `wrow` float64 [n_region,
+  n_row], `mult` int32 [n_region, n_class] and, where given, `class_cols`
+  int32 [n_class] (else None)."""
+  wrow = np.ascontiguousarray(wrow, dtype=np.float64)
+  mult = np.ascontiguousarray(mult, dtype=np.int32)
+  n_region = wrow.shape[0] if wrow.ndim == 2 else -1
+  if wrow.shape != (n_region, n_row) or mult.shape != (n_region, n_class):
+    raise ValueError('wrow must be [n_region, n_row] and mult [n_region, '
+                     'n_class]')
+  if class_cols is None:
+    return wrow, mult, None
+  cols = np.ascontiguousarray(class_cols, dtype=np.int32).reshape(-1)
+  if cols.size != n_class:
+    raise ValueError(f'class_cols must hold {n_class} column counts')
+  return wrow, mult, cols
+
+
+def _class_fold(label: str, sums: torch.Tensor, n_cell: int, n_slot: int,
+                table_shape: tuple, wrow: np.ndarray, mult: np.ndarray
+                ) -> torch.Tensor:
+  """One wb2_crps_bin_fold launch under the hook label `label`: float64
+  `table_shape` (n_cell x n_region x n_slot) of the class sums `sums` ([n_cell,
+  n_row, n_class, n_slot] in memory); `wrow`, `mult`: `_fold_weights`'s."""
+  dev = sums.device
+  table = torch.empty(table_shape, dtype=torch.float64, device=dev)
+  if table.numel():
+    _launch(label, 'wb2_crps_bin_fold', _lib.ptr(sums), n_cell, wrow.shape[1],
+            mult.shape[1], n_slot,
+            _lib.ptr(upload_f64_table(wrow, dev) if wrow.size else None),
+            _lib.ptr(_upload_i32(mult.reshape(-1), dev)), wrow.shape[0],
+            _lib.ptr(table), current_stream_ptr(dev))
+  return table
+
+
 def event_fold(cnt: torch.Tensor, wrow, mult) -> torch.Tensor:
   """wb2_event_fold: float64 [n_threshold, n_outer, n_region, n_code] =
   sum_i wrow[r, i] * float(sum_c mult[r, c] * cnt[.., i, c, code]), the inner
@@ -1908,12 +1967,8 @@ def event_fold(cnt: torch.Tensor, wrow, mult) -> torch.Tensor:
     raise ValueError('cnt must be a contiguous int32 [threshold, outer, row, '
                      'class, code] tensor')
   n_thr, n_outer, n_row, n_class, n_code = (int(n) for n in cnt.shape)
-  wrow = np.ascontiguousarray(wrow, dtype=np.float64)
-  mult = np.ascontiguousarray(mult, dtype=np.int32)
-  n_region = wrow.shape[0] if wrow.ndim == 2 else -1
-  if wrow.shape != (n_region, n_row) or mult.shape != (n_region, n_class):
-    raise ValueError('wrow must be [n_region, n_row] and mult [n_region, '
-                     'n_class]')
+  wrow, mult, _ = _fold_weights(wrow, mult, n_row, n_class)
+  n_region = wrow.shape[0]
   dev = cnt.device
   out = torch.empty((n_thr, n_outer, n_region, n_code), dtype=torch.float64,
                     device=dev)
@@ -1970,34 +2025,22 @@ def crps_bin_sums(ens: torch.Tensor, member_stride: int, n_member: int,
   here against the operands' storage in the same way: the kernel trusts
   them."""
   _require_float(ens, truth)
-  _check_contiguous(ens.device, 'the device of the members', truth, view=ens)
-  n_member, n_outer, n_row, n_col, member_stride, n_class = (
-      int(v) for v in (n_member, n_outer, n_row, n_col, member_stride,
-                       n_class))
-  if min(n_outer, n_row, n_col) < 0 or member_stride < 0:
-    raise ValueError('bad sizes')
-  geo = crps_bins_geometry(ens.dtype, 1, 1)
-  if not geo['min_member'] <= n_member <= geo['max_member']:
-    raise ValueError(f'{n_member} members: the CRPS bin sums take '
-                     f"{geo['min_member']} to {geo['max_member']}")
-  slab = n_row * n_col
-  es = _event_slabs(ens_slab, n_outer, ens, slab,
-                    (n_member - 1) * member_stride, 'member')
-  ts = _event_slabs(truth_slab, n_outer, truth, slab, 0, 'truth')
+  _check_members(n_member, crps_bins_geometry(ens.dtype, 1, 1),
+                 'the CRPS bin sums take')
+  (n_member, member_stride, n_outer, n_row, n_col), args, _ = _member_front(
+      ens, member_stride, n_member, ens_slab, truth, truth_slab, n_outer,
+      n_row, n_col)
+  n_class = int(n_class)
   cls = _column_classes(col_class, n_col, n_class)
   dev = ens.device
   sums = torch.empty((n_outer, n_row, n_class, 2, n_member + 1),
                      dtype=torch.float64, device=dev)
   cnt = torch.empty((n_outer, n_row, n_class, 3), dtype=torch.int32,
                     device=dev)
-  if slab * n_outer == 0:  # no points: nothing to add
+  if args is None:  # no points: nothing to add
     return sums.zero_(), cnt.zero_()
-  _launch('crps_bin_sums', 'wb2_crps_bin_sums', dtype_code(ens.dtype),
-          _lib.ptr(ens), _lib.ptr(None if es is None else
-                                  upload_table(es, dev)),
-          _lib.ptr(truth), _lib.ptr(None if ts is None else
-                                    upload_table(ts, dev)),
-          n_member, member_stride, n_outer, n_row, n_col,
+  _launch('crps_bin_sums', 'wb2_crps_bin_sums', *args, n_member,
+          member_stride, n_outer, n_row, n_col,
           _lib.ptr(_upload_i32(cls.astype(np.int32), dev)), n_class,
           _lib.ptr(sums), _lib.ptr(cnt), current_stream_ptr(dev))
   return sums, cnt
@@ -2018,26 +2061,11 @@ def crps_bin_fold(sums: torch.Tensor, cnt: torch.Tensor, class_cols, wrow,
     raise ValueError('sums must be a contiguous float64 [outer, row, class, '
                      '2, bin] tensor and cnt its int32 [outer, row, class, 3]')
   n_outer, n_row, n_class, _, n_bin = (int(n) for n in sums.shape)
-  wrow = np.ascontiguousarray(wrow, dtype=np.float64)
-  mult = np.ascontiguousarray(mult, dtype=np.int32)
-  n_region = wrow.shape[0] if wrow.ndim == 2 else -1
-  if wrow.shape != (n_region, n_row) or mult.shape != (n_region, n_class):
-    raise ValueError('wrow must be [n_region, n_row] and mult [n_region, '
-                     'n_class]')
-  cols = np.ascontiguousarray(class_cols, dtype=np.int32).reshape(-1)
-  if cols.size != n_class:
-    raise ValueError(f'class_cols must hold {n_class} column counts')
-  dev = sums.device
-  table = torch.empty((n_outer, n_region, 2, n_bin), dtype=torch.float64,
-                      device=dev)
-  if table.numel():
-    _launch('crps_bin_fold', 'wb2_crps_bin_fold', _lib.ptr(sums), n_outer,
-            n_row, n_class, 2 * n_bin,
-            _lib.ptr(upload_f64_table(wrow, dev) if wrow.size else None),
-            _lib.ptr(_upload_i32(mult.reshape(-1), dev)), n_region,
-            _lib.ptr(table), current_stream_ptr(dev))
-  invalid = _upload_i32(cols, dev)[:n_class].reshape(1, 1, n_class
-                                                      ) - cnt[..., 2]
+  wrow, mult, cols = _fold_weights(wrow, mult, n_row, n_class, class_cols)
+  table = _class_fold('crps_bin_fold', sums, n_outer, 2 * n_bin,
+                      (n_outer, wrow.shape[0], 2, n_bin), wrow, mult)
+  invalid = _upload_i32(cols, sums.device)[:n_class].reshape(
+      1, 1, n_class) - cnt[..., 2]
   cnt4 = torch.cat([cnt, invalid[..., None].to(torch.int32)], dim=-1)
   return table, event_fold(cnt4[None].contiguous(), wrow, mult)[0]
 
@@ -2074,10 +2102,7 @@ def twcrps_sums(ens: torch.Tensor, member_stride: int, n_member: int,
   n_class = int(n_class)
   thresholds = list(thresholds)
   _require_float(ens, truth, *thresholds)
-  geo = twcrps_geometry(ens.dtype)
-  if not geo['min_member'] <= int(n_member) <= geo['max_member']:
-    raise ValueError(f'{int(n_member)} members: the twCRPS sums take '
-                     f"{geo['min_member']} to {geo['max_member']}")
+  _check_members(n_member, twcrps_geometry(ens.dtype), 'the twCRPS sums take')
   (n_thr, n_member, n_outer, n_row, n_col), args = _event_front(
       ens, member_stride, n_member, ens_slab, truth, truth_slab, thresholds,
       thr_slabs, n_outer, n_row, n_col)
@@ -2113,26 +2138,11 @@ def twcrps_fold(sums: torch.Tensor, cnt: torch.Tensor, class_cols, wrow,
                      'row, class, 2] tensor and cnt its int32 [threshold, '
                      'outer, row, class, 1]')
   n_thr, n_outer, n_row, n_class, _ = (int(n) for n in sums.shape)
-  wrow = np.ascontiguousarray(wrow, dtype=np.float64)
-  mult = np.ascontiguousarray(mult, dtype=np.int32)
-  n_region = wrow.shape[0] if wrow.ndim == 2 else -1
-  if wrow.shape != (n_region, n_row) or mult.shape != (n_region, n_class):
-    raise ValueError('wrow must be [n_region, n_row] and mult [n_region, '
-                     'n_class]')
-  cols = np.ascontiguousarray(class_cols, dtype=np.int32).reshape(-1)
-  if cols.size != n_class:
-    raise ValueError(f'class_cols must hold {n_class} column counts')
-  dev = sums.device
-  table = torch.empty((n_thr, n_outer, n_region, 2), dtype=torch.float64,
-                      device=dev)
-  if table.numel():
-    _launch('twcrps_fold', 'wb2_crps_bin_fold', _lib.ptr(sums),
-            n_thr * n_outer, n_row, n_class, 2,
-            _lib.ptr(upload_f64_table(wrow, dev) if wrow.size else None),
-            _lib.ptr(_upload_i32(mult.reshape(-1), dev)), n_region,
-            _lib.ptr(table), current_stream_ptr(dev))
-  invalid = _upload_i32(cols, dev)[:n_class].reshape(1, 1, 1, n_class, 1
-                                                      ) - cnt
+  wrow, mult, cols = _fold_weights(wrow, mult, n_row, n_class, class_cols)
+  table = _class_fold('twcrps_fold', sums, n_thr * n_outer, 2,
+                      (n_thr, n_outer, wrow.shape[0], 2), wrow, mult)
+  invalid = _upload_i32(cols, sums.device)[:n_class].reshape(
+      1, 1, 1, n_class, 1) - cnt
   cnt2 = torch.cat([cnt, invalid.to(torch.int32)], dim=-1)
   return table, event_fold(cnt2.contiguous(), wrow, mult)
 
@@ -2187,40 +2197,28 @@ def conditional_sums(ens: torch.Tensor, member_stride: int, n_member: int,
   `event_counts`; all of them and the edges are checked here: the kernel
   trusts them."""
   _require_float(ens, truth)
-  _check_contiguous(ens.device, 'the device of the members', truth, view=ens)
-  n_member, n_outer, n_row, n_col, member_stride, n_class = (
-      int(v) for v in (n_member, n_outer, n_row, n_col, member_stride,
-                       n_class))
-  if min(n_outer, n_row, n_col) < 0 or member_stride < 0:
-    raise ValueError('bad sizes')
   mode = CONDITIONAL_MODES.get(mode, mode)
   if mode not in (0, 1, 2):
     raise ValueError(f'mode={mode!r}: the conditional sums take '
                      f'{", ".join(map(repr, CONDITIONAL_MODES))}')
   geo = conditional_geometry(ens.dtype)
-  if not geo['min_member'] <= n_member <= geo['max_member']:
-    raise ValueError(f'{n_member} members: the conditional sums take '
-                     f"{geo['min_member']} to {geo['max_member']}")
+  _check_members(n_member, geo, 'the conditional sums take')
   e = conditional_edges(edges, geo['max_edges'])
   n_bin = e.size + 1
-  slab = n_row * n_col
-  es = _event_slabs(ens_slab, n_outer, ens, slab,
-                    (n_member - 1) * member_stride, 'member')
-  ts = _event_slabs(truth_slab, n_outer, truth, slab, 0, 'truth')
+  (n_member, member_stride, n_outer, n_row, n_col), args, _ = _member_front(
+      ens, member_stride, n_member, ens_slab, truth, truth_slab, n_outer,
+      n_row, n_col)
+  n_class = int(n_class)
   cls = _column_classes(col_class, n_col, n_class)
   dev = ens.device
   sums = torch.empty((n_outer, n_row, n_class, n_bin, CONDITIONAL_TERMS),
                      dtype=torch.float64, device=dev)
   cnt = torch.empty((n_outer, n_row, n_class, n_bin), dtype=torch.int32,
                     device=dev)
-  if slab * n_outer == 0:  # no points: nothing to add
+  if args is None:  # no points: nothing to add
     return sums.zero_(), cnt.zero_()
-  _launch('conditional_sums', 'wb2_conditional_sums', dtype_code(ens.dtype),
-          _lib.ptr(ens), _lib.ptr(None if es is None else
-                                  upload_table(es, dev)),
-          _lib.ptr(truth), _lib.ptr(None if ts is None else
-                                    upload_table(ts, dev)),
-          n_member, member_stride, n_outer, n_row, n_col,
+  _launch('conditional_sums', 'wb2_conditional_sums', *args, n_member,
+          member_stride, n_outer, n_row, n_col,
           _lib.ptr(_upload_i32(cls.astype(np.int32), dev)), n_class, mode,
           _lib.ptr(upload_f64_table(e, dev) if e.size else None), e.size,
           _lib.ptr(sums), _lib.ptr(cnt), current_stream_ptr(dev))
@@ -2244,26 +2242,13 @@ def conditional_fold(sums: torch.Tensor, cnt: torch.Tensor, class_cols, wrow,
                      'bin, 4] tensor and cnt its int32 [outer, row, class, '
                      'bin]')
   n_outer, n_row, n_class, n_bin, _ = (int(n) for n in sums.shape)
-  wrow = np.ascontiguousarray(wrow, dtype=np.float64)
-  mult = np.ascontiguousarray(mult, dtype=np.int32)
-  n_region = wrow.shape[0] if wrow.ndim == 2 else -1
-  if wrow.shape != (n_region, n_row) or mult.shape != (n_region, n_class):
-    raise ValueError('wrow must be [n_region, n_row] and mult [n_region, '
-                     'n_class]')
-  cols = np.ascontiguousarray(class_cols, dtype=np.int32).reshape(-1)
-  if cols.size != n_class:
-    raise ValueError(f'class_cols must hold {n_class} column counts')
-  dev = sums.device
-  table = torch.empty((n_outer, n_region, n_bin, CONDITIONAL_TERMS),
-                      dtype=torch.float64, device=dev)
-  if table.numel():
-    _launch('conditional_fold', 'wb2_crps_bin_fold', _lib.ptr(sums), n_outer,
-            n_row, n_class, CONDITIONAL_TERMS * n_bin,
-            _lib.ptr(upload_f64_table(wrow, dev) if wrow.size else None),
-            _lib.ptr(_upload_i32(mult.reshape(-1), dev)), n_region,
-            _lib.ptr(table), current_stream_ptr(dev))
-  invalid = _upload_i32(cols, dev)[:n_class].reshape(1, 1, n_class
-                                                      ) - cnt.sum(dim=-1)
+  wrow, mult, cols = _fold_weights(wrow, mult, n_row, n_class, class_cols)
+  table = _class_fold('conditional_fold', sums, n_outer,
+                      CONDITIONAL_TERMS * n_bin,
+                      (n_outer, wrow.shape[0], n_bin, CONDITIONAL_TERMS), wrow,
+                      mult)
+  invalid = _upload_i32(cols, sums.device)[:n_class].reshape(
+      1, 1, n_class) - cnt.sum(dim=-1)
   codes = torch.cat([cnt, invalid[..., None].to(torch.int32)], dim=-1)
   return table, event_fold(codes[None].contiguous(), wrow, mult)[0]
 

@@ -102,25 +102,36 @@ def column_classes(regions: t.Mapping[str, t.Any], latitude, longitude):
 # ---------------------------------------------------------------------------
 # the host path: same integers, same fold order
 # ---------------------------------------------------------------------------
+def host_slab(x: np.ndarray, table, o: int, slab: int) -> np.ndarray:
+  """Slab `o` of the flat host array `x` (`table`: None = identity)."""
+  first = (o if table is None else int(table[o])) * slab
+  return x[first:first + slab]
+
+
+def host_members(ens: np.ndarray, member_stride: int, n_member: int, ens_slab,
+                 truth: np.ndarray, truth_slab, n_outer: int, slab: int):
+  """The slab addressing of the host paths, from the leading arguments of
+  `engine.event_counts` (host arrays): yields (outer index, members [n_member,
+  slab], truth [slab])."""
+  ens, truth = ens.reshape(-1), truth.reshape(-1)
+  for o in range(n_outer):
+    x = np.stack([host_slab(ens[m * member_stride:], ens_slab, o, slab)
+                  for m in range(n_member)])
+    yield o, x, host_slab(truth, truth_slab, o, slab)
+
+
 def host_exceedance(ens: np.ndarray, member_stride: int, n_member: int,
                     ens_slab, truth: np.ndarray, truth_slab, thresholds,
                     thr_slabs, n_outer: int, slab: int):
   """The per-point definition on the host, from the leading arguments of
   `engine.event_counts` (host arrays): yields (threshold index, outer index,
   k, obs, bad) over the `slab` points of every slab."""
-  ens, truth = ens.reshape(-1), truth.reshape(-1)
   thr_slabs = thr_slabs if thr_slabs is not None else [None] * len(thresholds)
-  at = lambda table, o: o if table is None else int(table[o])
-  for o in range(n_outer):
-    e0 = at(ens_slab, o) * slab
-    x = np.stack([ens[e0 + m * member_stride:e0 + m * member_stride + slab]
-                  for m in range(n_member)])
-    t0 = at(truth_slab, o) * slab
-    tv = truth[t0:t0 + slab]
+  for o, x, tv in host_members(ens, member_stride, n_member, ens_slab, truth,
+                               truth_slab, n_outer, slab):
     bad = np.isnan(tv) | np.isnan(x).any(axis=0)
     for ti, (thr, table) in enumerate(zip(thresholds, thr_slabs)):
-      h0 = at(table, o) * slab
-      hv = thr.reshape(-1)[h0:h0 + slab]
+      hv = host_slab(thr.reshape(-1), table, o, slab)
       with np.errstate(invalid='ignore'):
         k, obs = (x > hv[None]).sum(axis=0), tv > hv
       yield ti, o, k, obs, bad

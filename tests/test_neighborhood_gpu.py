@@ -396,3 +396,152 @@ def test_fractions_table_in_the_generic_evaluation_loop():
   mean = metric.compute_regions(f_dev, t_dev, regions)
   np.testing.assert_array_equal(np.asarray(res[NAME].values)[0],
                                 mean[NAME].values)
+
+
+# ---------------------------------------------------------------------------
+# 5. wb2_fss_sums where the LDS budget splits the launches
+# ---------------------------------------------------------------------------
+FSS_THREADS = 256  # the workgroup of fss_sums_kernel: one row, all columns
+
+
+def _widest_row(n_class, n_window=1):
+  """The largest n_col that `engine.fss_sums_geometry` admits: bisection over
+  the geometry call (the LDS bytes grow with n_col)."""
+  from weatherbench2_amd import _lib
+
+  def fits(n_col):
+    try:
+      engine.fss_sums_geometry(n_col, n_class, n_window)
+      return True
+    except _lib.Wb2HipError as e:
+      assert 'LDS budget' in str(e)
+      return False
+  lo, hi = 1, 1 << 20
+  assert fits(lo) and not fits(hi)
+  while hi - lo > 1:
+    mid = (lo + hi) // 2
+    lo, hi = (mid, hi) if fits(mid) else (lo, mid)
+  return lo
+
+
+def _sums_both(code, windows, n_member, cls, n_class):
+  got = engine.fss_sums(_dev(code), windows, n_member, cls, n_class)
+  want = nb.host_sums(code, windows, n_member, cls, n_class)
+  assert got.dtype == torch.int64 and tuple(got.shape) == want.shape
+  return got.cpu().numpy(), want
+
+
+def test_window_batches_that_the_budget_splits():
+  # five windows at two per launch: fss_sums_kernel<2>, <2> and <1>, each with
+  # its own offset into the sums of the call
+  n_row, n_col, n_member, n_class = 3, 5000, 50, 10
+  windows = (1, 3, 9, 33, 255)
+  geo = engine.fss_sums_geometry(n_col, n_class, len(windows))
+  assert geo['windows_per_launch'] == 2
+  code = cases.code_plane(2, n_row, n_col, n_member, seed=21)
+  cls = cases.classes(n_col, n_class)
+  got, want = _sums_both(code, windows, n_member, cls, n_class)
+  for wi, n in enumerate(windows):
+    np.testing.assert_array_equal(got[:, wi], want[:, wi], err_msg=str(n))
+  assert all(want[:, wi].any() for wi in range(len(windows)))
+  # the first 64 columns of the same plane as a call of their own (the
+  # windows that such a row takes), against the loop from the definition
+  small = np.ascontiguousarray(code[:, :, :64])
+  fit = tuple(n for n in windows if n <= 64)
+  assert fit == windows[:4]
+  np.testing.assert_array_equal(
+      engine.fss_sums(_dev(small), fit, n_member, cls[:64], n_class
+                      ).cpu().numpy(),
+      nnp.sums_loop(small, fit, n_member, cls[:64], n_class))
+
+
+def test_more_than_32_columns_per_thread():
+  # 33 columns per thread: the mask of a thread's invalid centres is shifted
+  # by up to 32
+  n_row, n_col, n_member, n_class = 3, 8200, 50, 10
+  windows = (3, 17)
+  per = -(-n_col // FSS_THREADS)
+  assert per == 33
+  geo = engine.fss_sums_geometry(n_col, n_class, len(windows))
+  assert geo['windows_per_launch'] == 1
+  code = cases.code_plane(2, n_row, n_col, n_member, seed=22, invalid=1 / 3)
+  # columns 32 and 33 counted from the start of several threads' runs
+  for t in (0, 1, 63, 64, 127, 200, 247):
+    for j in (per * t + 32, per * t + 33):
+      assert j < n_col
+      code[:, :, j] = 0x200
+  # ... and a thread whose only invalid centre is its column 32
+  t = 100
+  keep = code[0, 1, per * t:per * (t + 1)]
+  keep[keep == 0x200] = 3
+  keep[32] = 0x200
+  cls = cases.classes(n_col, n_class)
+  got, want = _sums_both(code, windows, n_member, cls, n_class)
+  np.testing.assert_array_equal(got, want)
+  share = (code == 0x200).mean()
+  assert 0.3 < share < 0.4
+  # (the valid centres counted, per row: what the mask decides)
+  np.testing.assert_array_equal(got[..., 5].sum(axis=-1)[:, 0],
+                                (code != 0x200).sum(axis=-1))
+
+
+def test_the_widest_row_that_fits_and_the_refusal_one_column_later():
+  from weatherbench2_amd import _lib
+  n_row, n_member = 2, 7
+  widest = _widest_row(1)
+  assert widest == 13638
+  geo = engine.fss_sums_geometry(widest, 1, 1)
+  assert geo['lds_bytes'] == 163832 and -(-widest // FSS_THREADS) == 54
+  wide10 = _widest_row(10)
+  assert wide10 < widest
+  for n_col, n_class in ((widest, 1), (wide10, 10)):
+    code = cases.code_plane(1, n_row, n_col, n_member, seed=n_class)
+    cls = cases.classes(n_col, n_class)  # (10 classes: not contiguous)
+    for windows in ((1,), (255,)):
+      got, want = _sums_both(code, windows, n_member, cls, n_class)
+      np.testing.assert_array_equal(got, want,
+                                    err_msg=str((n_col, n_class, windows)))
+    # one column more: refused by the entry point, before any launch (the
+    # hook's bracket stays open: no 'end')
+    over = _dev(np.zeros((1, n_row, n_col + 1), np.uint16))
+    calls = []
+    old = engine.set_launch_hook(lambda *a: calls.append(a))
+    try:
+      with pytest.raises(_lib.Wb2HipError, match='LDS budget'):
+        engine.fss_sums(over, (1,), n_member, np.zeros(n_col + 1, np.int32),
+                        n_class)
+    finally:
+      engine.set_launch_hook(old)
+    assert calls == [('begin', 'fss_sums')]
+
+
+def _assert_cells(got, want, n_cell, axis):
+  for cell in (0, 32767, 32768, n_cell - 1):
+    np.testing.assert_array_equal(np.take(got, cell, axis=axis),
+                                  np.take(want, cell, axis=axis),
+                                  err_msg=f'cell {cell}')
+  np.testing.assert_array_equal(got, want)
+
+
+def test_cells_beyond_one_grid_row():
+  geo = engine.fss_sums_geometry(3, 1, 1)
+  n_cell = geo['max_grid_outer'] + 1
+  assert n_cell > 32768
+  # wb2_fss_sums: every cell its own codes
+  n_member = 5
+  code = cases.code_plane(n_cell, 1, 3, n_member, seed=23, invalid=0.2)
+  code[:, 0, 0] = np.arange(n_cell) % (n_member + 1)  # (valid, cell by cell)
+  code[-1, 0, 2] = 0x200
+  cls = np.array([0, 1, 0], np.int32)
+  got, want = _sums_both(code, (1, 3), n_member, cls, 2)
+  _assert_cells(got, want, n_cell, 0)
+  assert (want[-1] != want[0]).any() and (want[32768] != want[32767]).any()
+  # wb2_event_codes: one member, one threshold, the same outer count
+  rs = np.random.RandomState(24)
+  ens = np.round(rs.normal(size=(1, n_cell, 1, 3)), 1).astype(np.float32)
+  truth = np.round(rs.normal(size=(n_cell, 1, 3)), 1).astype(np.float32)
+  thr = np.round(rs.normal(size=(n_cell, 1, 3)) * 0.5, 1).astype(np.float32)
+  truth[-1, 0, 2] = ens[0, 32768, 0, 0] = np.nan
+  dev, host = _both_codes(ens, truth, [thr])
+  _assert_cells(dev, host, n_cell, 1)
+  assert host[0, -1, 0, 2] == 0x200 and host[0, 32768, 0, 0] == 0x200

@@ -2131,6 +2131,85 @@ int wb2_conditional_geometry(int dtype, int32_t n_member, int32_t n_class,
                              int32_t* tile_cols, int32_t* rows_per_group,
                              int64_t* lds_bytes, int32_t* max_grid_outer);
 
+/*
+ * K25: the zonal cross-spectrum of forecast and truth, the sufficient
+ * statistic of scale-dependent verification (coherence, spectral correlation,
+ * amplitude ratio, phase error, error spectrum, effective resolution).  The
+ * reference has the spectrum of one field (ZonalEnergySpectrum) and no
+ * counterpart.
+ *
+ * Per outer index o, row i and member m, with N = n_col, NB = N / 2 + 1,
+ * F_m = rfft(member row, norm='forward'), T = rfft(truth row, norm='forward'),
+ * s_0 = 1 and s_k = 2 otherwise (the Nyquist bin is doubled too, as
+ * wb2_zonal_spectrum has it) and C_i = circumference[i]:
+ *   sums[o][i][0][k] = power_forecast = sum_m s_k C_i |F_m[k]|^2
+ *   sums[o][i][1][k] = power_truth    =       s_k C_i |T[k]|^2
+ *   sums[o][i][2][k] = cospectrum     = sum_m s_k C_i Re(F_m[k] conj T[k])
+ *   sums[o][i][3][k] = quadrature     = sum_m s_k C_i Im(F_m[k] conj T[k])
+ * SIGN: a forecast that is the truth displaced EASTWARD by d degrees has
+ * atan2(quadrature, cospectrum) = -2 pi k d / 360 (mod 2 pi).
+ * Arithmetic: the transform (K4f's: N / 2 complex points, the plan's twiddle
+ * tables, fft_core.hpp) and the products x x + y y, F.x T.x + F.y T.y and
+ * F.y T.x - F.x T.y are in the row dtype (whether the compiler contracts them
+ * is not pinned); each product is widened to float64 and multiplied once by
+ * s_k C_i; the member terms are added in STORAGE order, the first term
+ * starting the chain.  The sums are NOT divided by n_member.
+ * A row is INVALID iff the truth row or any member row holds a non-finite
+ * value (NaN or +-inf): all four terms of the row are +0.0 then.
+ *   cnt[o][i][0..1] (DEV int32, every element written) = (1, 0) for a valid
+ *   row, (0, 1) for an invalid one.
+ *
+ * wb2_cross_spectrum_rows: `plan` is a wb2_spectrum_plan_create plan of the
+ * same dtype and n_lon = n_col (any n_rows), whose twiddle tables are used;
+ * K20's operands and slab-table convention (ens, ens_slab, truth, truth_slab,
+ * n_member, member_stride, n_outer; tables DEV int64, null = identity; every
+ * table value the caller's to check), slabs of n_row x n_col elements;
+ * circumference DEV float64[n_row]; sums DEV float64 [n_outer][n_row][4][NB],
+ * every element written.
+ * One WAVE owns one row (o, i): it transforms the truth row into an LDS slab
+ * of its own (pass 0 straight from memory with non-temporal loads), then every
+ * member row into a second slab, recombines both for the bin pairs (k, N / 2 -
+ * k) from one pair of LDS reads each and forms the products.  The finiteness
+ * test rides on the pass-0 loads (one comparison per loaded value, one wave
+ * ballot).  The member sums are kept in the lane's registers and stored once,
+ * except for the long rows whose transform leaves no registers for them
+ * (float32: N >= 2560; float64: N >= 1800), which keep them in the lane's own
+ * elements of `sums`: the same chain, the same bits.  Plain stores, no
+ * atomics: two runs are bit-equal.  waves_per_group is fixed per (length,
+ * dtype): the most of 4, 2 and 1 whose two slabs per wave and the twq table
+ * fit 160 KiB; a launch has at most max_grid_outer workgroups, whose waves
+ * stride over the rows.
+ * Checked before anything is enqueued, in this order: the dtype ("unknown
+ * dtype"), an n_col that is not instantiated ("not instantiated", with the
+ * list of lengths: the 22 of wb2_zonal_spectrum's one-kernel path),
+ * 1 <= n_member <= 128 ("n_member="), a negative member_stride, negative
+ * sizes, the alignment of the pass-0 loads (ens and truth on 8 bytes for
+ * float32 and 16 for float64, an even member_stride: "aligned"), null
+ * pointers ("null pointer"), the grid ("the grid does not fit": more than
+ * 2^40 rows) and a plan of another dtype or length ("the plan").  Zero n_outer
+ * or n_row is a no-op whatever the pointers are.
+ *
+ * wb2_cross_spectrum_geometry: supported = 1 for an instantiated n_col (else
+ * 0, and the other extents are 0), waves_per_group,
+ *   lds_bytes = complex size * ((N / 4 + 2) + waves_per_group * 2 * slab),
+ * slab = the complex slots of K4f's padded slab (N / 2 without padding; 840
+ * for N = 1440), max_grid_outer = the most workgroups of a launch.  The same
+ * checks of dtype and n_member.
+ *
+ * The fold: the sums go through wb2_crps_bin_fold (n_class = 1, n_slot = 4
+ * NB, mult = 1), the flags through wb2_event_fold (n_code = 2).
+ */
+int wb2_cross_spectrum_rows(void* plan, int dtype, const void* ens,
+                            const int64_t* ens_slab, const void* truth,
+                            const int64_t* truth_slab, int32_t n_member,
+                            int64_t member_stride, int64_t n_outer,
+                            int32_t n_row, int32_t n_col,
+                            const double* circumference, double* sums,
+                            int32_t* cnt, void* stream);
+int wb2_cross_spectrum_geometry(int dtype, int32_t n_col, int32_t n_member,
+                                int32_t* supported, int32_t* waves_per_group,
+                                int64_t* lds_bytes, int32_t* max_grid_outer);
+
 #ifdef __cplusplus
 }
 #endif

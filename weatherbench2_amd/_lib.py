@@ -293,6 +293,12 @@ _SIGNATURES = {
         _int, _i32, _i32, _i32, _c.POINTER(_i32), _c.POINTER(_i32),
         _c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i32),
         _c.POINTER(_i64), _c.POINTER(_i32)]),
+    'wb2_cross_spectrum_rows': (_int, [
+        _vp, _int, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp,
+        _vp, _vp]),
+    'wb2_cross_spectrum_geometry': (_int, [
+        _int, _i32, _i32, _c.POINTER(_i32), _c.POINTER(_i32),
+        _c.POINTER(_i64), _c.POINTER(_i32)]),
 }
 
 _lib = None

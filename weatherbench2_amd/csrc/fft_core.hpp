@@ -303,6 +303,13 @@ WB2_FFT_PLAN(1440, 12, 12, 10, 0, 0)   // 2880
 WB2_FFT_PLAN(1800, 10, 12, 15, 0, 0)   // 3600
 #undef WB2_FFT_PLAN
 
+// every N2 with a plan above (cross_spectrum.hip and the host checks
+// instantiate them all; spectrum_fused.hip keeps its own list, WB2_FUSED_SIZES)
+#define WB2_FFT_PLAN_SIZES(X)                                                 \
+  X(32) X(64) X(120) X(128) X(180) X(256) X(360) X(512) X(720) X(48)           \
+  X(144) X(160) X(192) X(240) X(320) X(384) X(640) X(900) X(1024)       \
+  X(1280) X(1440) X(1800)
+
 // ---- one Stockham pass of radix R; NS = product of the radices already done ---
 // Butterfly j (0 <= j < T = N2 / R), k = j mod NS:
 //   inputs   v[r] = src[j + r T] * exp(-2 pi i k r / (NS R))      r = 0..R-1
@@ -456,6 +463,22 @@ WB2_HD void recombine_pair(C a, C b, C wq, scalar_t<C> half_inv_n,
   const C x2 = vfma(splat<C>(half_inv_n), u, -wv);
   p1 = x1.x * x1.x + x1.y * x1.y;
   p2 = x2.x * x2.x + x2.y * x2.y;
+}
+
+// recombine_pair()'s sibling for the cross-spectrum (K25, cross_spectrum.hip):
+// the same operations in the same order, but the two bins come back as complex
+// numbers, x1 = X[k] and x2 = X[N2 - k] (the conjugate recombine_pair() squares
+// away is taken: an exact sign flip), so that |x1|^2 and |x2|^2 formed as
+// x*x + y*y are recombine_pair()'s p1 and p2.
+template <typename C>
+WB2_HD void recombine_pair_complex(C a, C b, C wq, scalar_t<C> half_inv_n,
+                                   C& x1, C& x2) {
+  const C u = vfma(b, C{1, -1}, a);  // a + conj b
+  const C v = vfma(b, C{-1, 1}, a);  // a - conj b
+  const C wv = cmul(v, wq);
+  x1 = vfma(splat<C>(half_inv_n), u, wv);
+  const C e = vfma(splat<C>(half_inv_n), u, -wv);
+  x2 = C{e.x, -e.y};
 }
 
 // The two tables a plan keeps (evaluated in fp64, rounded once):

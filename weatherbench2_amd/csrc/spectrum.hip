@@ -221,6 +221,16 @@ int make_fft_plan(SpectrumPlan* p, bool own_work_area) {
 }
 
 }  // namespace
+
+// cross_spectrum.hip (K25): the twiddle tables `plan` owns, with the dtype and
+// row length they were made for; null for a plan without the one-kernel path.
+void* spectrum_plan_tables(void* plan, int* dtype, int* n_lon) {
+  auto* p = static_cast<SpectrumPlan*>(plan);
+  *dtype = p->dtype;
+  *n_lon = p->n_lon;
+  return p->fused ? p->tables : nullptr;
+}
+
 }  // namespace wb2
 
 extern "C" {

@@ -2253,6 +2253,113 @@ def conditional_fold(sums: torch.Tensor, cnt: torch.Tensor, class_cols, wrow,
   return table, event_fold(codes[None].contiguous(), wrow, mult)[0]
 
 
+CROSS_TERMS = 4  # power_forecast, power_truth, cospectrum, quadrature
+
+
+def cross_spectrum_geometry(dtype: torch.dtype, n_col: int,
+                            n_member: int = 1) -> dict:
+  """Extents of the K25 rows kernel for rows of `n_col` points: `supported`
+  (1: the length is instantiated), the `waves_per_group` (= rows in flight per
+  workgroup), the `lds_bytes` of a workgroup (the twq table and two slabs per
+  wave) and `max_grid_outer`, the most workgroups of a launch (waves stride
+  over the rows beyond)."""
+  return _geometry('wb2_cross_spectrum_geometry',
+                   (dtype_code(dtype), int(n_col), int(n_member)),
+                   [('supported', _I32), ('waves_per_group', _I32),
+                    ('lds_bytes', ctypes.c_int64), ('max_grid_outer', _I32)])
+
+
+def _aligned_members(ens, member_stride, n_member, ens_slab, n_outer, slab):
+  """(ens, member_stride, ens_slab) with every row on the 2-element boundary
+  the pass-0 loads of K25 need: the operands themselves where they are, else
+  the addressed slabs gathered into one contiguous [n_outer, n_member, slab]
+  copy (identity addressing of that copy)."""
+  if ens.data_ptr() % (2 * ens.element_size()) == 0 and member_stride % 2 == 0:
+    return ens, member_stride, ens_slab
+  table = _event_slabs(ens_slab, n_outer, ens, slab,
+                       (max(n_member, 1) - 1) * member_stride, 'member')
+  first = np.arange(n_outer, dtype=np.int64) if table is None else table
+  start = (first * slab)[:, None] + np.arange(
+      n_member, dtype=np.int64)[None] * member_stride
+  dev = ens.device
+  index = torch.as_tensor(start, device=dev)[..., None] + torch.arange(
+      slab, dtype=torch.int64, device=dev)
+  dense = ens.as_strided((_reach(ens),), (1,))[index]
+  return dense, slab, (np.arange(n_outer, dtype=np.int64) * n_member
+                       if n_member != 1 else None)
+
+
+def cross_spectrum_rows(ens: torch.Tensor, member_stride: int, n_member: int,
+                        ens_slab, truth: torch.Tensor, truth_slab,
+                        n_outer: int, n_row: int, n_col: int, circumference
+                        ) -> tuple:
+  """K25, wb2_cross_spectrum_rows: (float64 [n_outer, n_row, 4, n_col // 2 +
+  1] row terms -- power_forecast, power_truth, cospectrum, quadrature, the
+  three forecast terms summed over the members in storage order --, int32
+  [n_outer, n_row, 2] valid / invalid flags) of every row.  The operands and
+  the HOST slab tables are those of `event_counts`, checked here against the
+  operands' storage in the same way: the kernel trusts them.  `circumference`
+  is a HOST float64 [n_row].  A row length that is not instantiated is a
+  ValueError (there is no other path); operands whose rows miss the alignment
+  of the kernel's loads are copied once."""
+  _require_float(ens, truth)
+  n_member, n_outer, n_row, n_col, member_stride = (
+      int(v) for v in (n_member, n_outer, n_row, n_col, member_stride))
+  geo = cross_spectrum_geometry(ens.dtype, n_col, max(1, min(n_member, 128)))
+  if not geo['supported']:
+    raise ValueError(f'n_col={n_col}: the cross-spectrum has no kernel for '
+                     'this row length')
+  if not 1 <= n_member <= 128:
+    raise ValueError(f'{n_member} members: the cross-spectrum takes 1 to 128')
+  circ = np.ascontiguousarray(circumference, dtype=np.float64).reshape(-1)
+  if circ.size != n_row:
+    raise ValueError(f'circumference must hold {n_row} values')
+  if min(n_outer, n_row) >= 0 and member_stride >= 0 and n_outer * n_row:
+    ens, member_stride, ens_slab = _aligned_members(
+        ens, member_stride, n_member, ens_slab, n_outer, n_row * n_col)
+    if truth.data_ptr() % (2 * truth.element_size()):
+      truth = truth.clone()
+  (n_member, member_stride, n_outer, n_row, n_col), args, _ = _member_front(
+      ens, member_stride, n_member, ens_slab, truth, truth_slab, n_outer,
+      n_row, n_col)
+  dev = ens.device
+  n_bin = n_col // 2 + 1
+  sums = torch.empty((n_outer, n_row, CROSS_TERMS, n_bin),
+                     dtype=torch.float64, device=dev)
+  cnt = torch.empty((n_outer, n_row, 2), dtype=torch.int32, device=dev)
+  if args is None:  # no rows: nothing to transform
+    return sums.zero_(), cnt.zero_()
+  handle, _ = _SPECTRUM_PLANS.get(args[0], n_col, 1)
+  _launch('cross_spectrum_rows', 'wb2_cross_spectrum_rows', handle, *args,
+          n_member, member_stride, n_outer, n_row, n_col,
+          _lib.ptr(upload_f64_table(circ, dev)), _lib.ptr(sums), _lib.ptr(cnt),
+          current_stream_ptr(dev))
+  return sums, cnt
+
+
+def cross_spectrum_fold(sums: torch.Tensor, cnt: torch.Tensor, wrow) -> tuple:
+  """(float64 [n_outer, n_region, 4, n_bin], float64 [n_outer, n_region, 2]):
+  wb2_crps_bin_fold of the row terms (one class of multiplicity 1, n_slot = 4
+  n_bin: acc = acc + wrow[r, i] * sums[o, i] over the rows in increasing order,
+  plain float64) and wb2_event_fold of the valid / invalid flags.  `wrow`
+  (float64 [n_region, n_row]) is a HOST array."""
+  if (sums.dtype != torch.float64 or sums.dim() != 4 or
+      sums.shape[2] != CROSS_TERMS or not sums.is_contiguous() or
+      cnt.dtype != torch.int32 or tuple(cnt.shape) != tuple(sums.shape[:2]) +
+      (2,) or not cnt.is_contiguous() or cnt.device != sums.device):
+    raise ValueError('sums must be a contiguous float64 [outer, row, 4, bin] '
+                     'tensor and cnt its int32 [outer, row, 2]')
+  n_outer, n_row, _, n_bin = (int(n) for n in sums.shape)
+  wrow = np.ascontiguousarray(wrow, dtype=np.float64)
+  ones = np.ones((wrow.shape[0] if wrow.ndim == 2 else 0, 1), dtype=np.int32)
+  wrow, mult, _ = _fold_weights(wrow, ones, n_row, 1)
+  table = _class_fold('cross_spectrum_fold', sums, n_outer,
+                      CROSS_TERMS * n_bin,
+                      (n_outer, wrow.shape[0], CROSS_TERMS, n_bin), wrow, mult)
+  counts = event_fold(cnt.reshape(1, n_outer, n_row, 1, 2), wrow, mult)[0]
+  return table, counts
+
+
 POOL_KINDS = {'mean': 0, 'max': 1}  # WB2_POOL_MEAN, WB2_POOL_MAX
 
 

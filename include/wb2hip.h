@@ -2210,6 +2210,85 @@ int wb2_cross_spectrum_geometry(int dtype, int32_t n_col, int32_t n_member,
                                 int32_t* supported, int32_t* waves_per_group,
                                 int64_t* lds_bytes, int32_t* max_grid_outer);
 
+/*
+ * K26: the joint frequency table of forecast and truth CATEGORIES (Murphy &
+ * Winkler 1987), the sufficient statistic of distributions-oriented
+ * verification: the multi-category scores (proportion correct, Heidke, Peirce,
+ * Gerrity), both marginal histograms and the two factorisations.  The
+ * reference has no counterpart, and K18's per-threshold 2 x 2 tables cannot
+ * give the cross terms (truth below edge 1 AND forecast above edge 2).
+ *
+ * With E = n_edge edges, B = E + 1 categories (the outer two open-ended):
+ *   side 0 (right):  bin(v) = #{k : edges[k] <= v}  (searchsorted side=
+ *                    'right': a value on an edge belongs to the upper
+ *                    category; K24's rule)
+ *   side 1 (left):   bin(v) = #{k : edges[k] <  v}  (being above edge k is
+ *                    K18's event v > edges[k])
+ * IEEE comparisons in float64 after an exact widening; +-inf are ordinary
+ * values and land in the outer categories.  The point is invalid iff the truth
+ * or any member is NaN (K18's rule).  One set of edges serves both.
+ *
+ * wb2_joint_counts: K20's operands and slab-table convention (ens, ens_slab,
+ * truth, truth_slab, n_member, member_stride, n_outer; tables DEV int64, null
+ * = identity; col_class DEV int32[n_col] with values in [0, n_class); every
+ * table value the caller's to check) and edges, a DEV float64[n_edge], finite
+ * and strictly increasing (the caller's to check; null is allowed for n_edge =
+ * 0).  n_code = B * B + 1 and
+ *   cnt[o][i][c][code] (DEV int32, every element written): over the columns j
+ *   with col_class[j] == c in row i of outer index o,
+ *     code = bin(y) * B + bin(x_m)  gets +1 PER MEMBER m of a valid point,
+ *     code = B * B                  gets +1 per invalid point.
+ *   The valid codes of a (row, class) sum to n_member x its valid points.
+ * A workgroup of 256 threads owns rows_per_group adjacent rows of one outer
+ * index and walks that contiguous run: 16-byte lanes where `ens` and `truth`
+ * are 16-byte aligned and n_col and member_stride are whole lanes (4 float32,
+ * 2 float64), one element per access otherwise; the bits are the same.  The
+ * edges are wave-uniform: each is read once per workgroup by a uniform load
+ * and kept in a register (those past n_edge are NaN).  side 1 is turned into
+ * side 0 there: for a finite e, e < v exactly where succ(e) <= v, succ = the
+ * next float64 up.  A point's validity is known only after its last member, so
+ * nothing reaches the histogram before: per point and edge k a thread keeps g_k
+ * = the members at or above edge k (<= 128: packed 8-bit counters, every index
+ * a compile-time constant); category b then holds g_{b-1} - g_b members (g_{-1}
+ * = n_member, g_B = 0) and the non-zero ones are added to an LDS histogram
+ * [row][class][code] with workgroup-scope integer atomics.  The members are
+ * requested four at a time before any is compared; each element is read ONCE,
+ * (n_member + 1) elements per point.  After a barrier the histogram is stored
+ * with plain stores.  Integer adds commute: two runs are bit-equal.  No global
+ * atomics, no float atomics.  The kernel is instantiated for 4, 8, 12, 16, 24
+ * and 32 edge slots; a call takes the least that holds n_edge.
+ * Checked before anything is enqueued, in this order: the dtype ("unknown
+ * dtype"), 1 <= n_member <= 128 ("n_member="), 1 <= n_class <= 64
+ * ("n_class="), 0 <= n_edge <= 31 ("n_edge="), the histogram of one row
+ * against the budget ("LDS budget"), side ("side="), a negative
+ * member_stride, negative sizes, null pointers ("null pointer"), a row group
+ * of 2^30 elements or more ("too long") and the grid.  Zero n_outer, n_row or
+ * n_col is a no-op whatever the pointers are.
+ *
+ * wb2_joint_counts_geometry: rows_per_group = the most of 4, 2, 1 whose
+ * histogram fits 65536 bytes (K18's budget),
+ *   lds_bytes = rows_per_group * n_class * (B * B + 1) * 4,
+ * max_edges = 31, max_grid_outer outer indices per grid row.  `wide` (16-byte
+ * lanes) changes none of them.  The same checks of dtype, n_member, n_class,
+ * n_edge and the budget, with the same error text.
+ *
+ * The fold: wb2_event_fold with n_code = B * B + 1,
+ *   table[o][r][code] = sum_i wrow[r][i] *
+ *                       (double)(sum_c mult[r][c] * cnt[o][i][c][code]),
+ * the inner sum in int64, the rows in increasing order.  The caller divides
+ * the B * B valid codes by their total, n_member x the valid mass.
+ */
+int wb2_joint_counts(int dtype, const void* ens, const int64_t* ens_slab,
+                     const void* truth, const int64_t* truth_slab,
+                     int32_t n_member, int64_t member_stride, int64_t n_outer,
+                     int32_t n_row, int32_t n_col, const int32_t* col_class,
+                     int32_t n_class, const double* edges, int32_t n_edge,
+                     int side, int32_t* cnt, void* stream);
+int wb2_joint_counts_geometry(int dtype, int32_t n_member, int32_t n_class,
+                              int32_t n_edge, int wide,
+                              int32_t* rows_per_group, int64_t* lds_bytes,
+                              int32_t* max_edges, int32_t* max_grid_outer);
+
 #ifdef __cplusplus
 }
 #endif

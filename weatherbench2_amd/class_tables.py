@@ -94,8 +94,15 @@ class ClassSumsTable(Metric):
 
   _ensemble_size = events.ExceedanceTable._ensemble_size
 
-  def _tables(self, forecast, truth, names, region, regions, n_bin, values):
-    """(the table Dataset without its attrs, the ensemble size)."""
+  def _tables(self, forecast, truth, names, region, regions, n_bin, values,
+              trailing=None):
+    """(the table Dataset without its attrs, the ensemble size).  `trailing`
+    (ensemble size) -> {dim: coord} names the last two dims where they are not
+    ('term', 'bin') (`distribution.JointTable`); `n_bin` is not asked then."""
+    if trailing is None:
+      trailing = lambda n_member: {
+          TERM: np.array(self._terms, dtype=object),
+          BIN: np.arange(n_bin(n_member), dtype=np.int64)}
     region_set = regions if regions is not None else {'region': region}
     lat = xl.coord_values(forecast, 'latitude')
     lon = xl.coord_values(forecast, 'longitude')
@@ -130,9 +137,9 @@ class ClassSumsTable(Metric):
     front = ('region',) if regions is not None else ()
     if regions is not None:
       out.coords['region'] = np.array(list(regions), dtype=object)
-    out.coords[TERM] = np.array(self._terms, dtype=object)
-    out.coords[BIN] = np.arange(n_bin(n_member), dtype=np.int64)
+    tail = trailing(n_member)
+    out.coords.update(tail)
     for name, (order, v) in per_var.items():
-      out.data_vars[name] = xl.DataArray(v, front + order + (TERM, BIN),
+      out.data_vars[name] = xl.DataArray(v, front + order + tuple(tail),
                                          out.coords, name)
     return out, n_member

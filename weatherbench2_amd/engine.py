@@ -2253,6 +2253,85 @@ def conditional_fold(sums: torch.Tensor, cnt: torch.Tensor, class_cols, wrow,
   return table, event_fold(codes[None].contiguous(), wrow, mult)[0]
 
 
+JOINT_SIDES = {'right': 0, 'left': 1}
+
+
+def joint_geometry(dtype: torch.dtype, n_member: int = 1, n_class: int = 1,
+                   n_edge: int = 0, wide: bool = False) -> dict:
+  """Extents of the K26 counting kernel: a workgroup owns `rows_per_group`
+  rows of one outer index, the histogram takes `lds_bytes` of LDS, at most
+  `max_edges` bin edges (one category more), `max_grid_outer` outer indices
+  per grid row.  A histogram that does not fit is refused here as in
+  `joint_counts`."""
+  return _geometry('wb2_joint_counts_geometry',
+                   (dtype_code(dtype), int(n_member), int(n_class),
+                    int(n_edge), int(wide)),
+                   [('rows_per_group', _I32), ('lds_bytes', ctypes.c_int64),
+                    ('max_edges', _I32), ('max_grid_outer', _I32)])
+
+
+def joint_edges(edges) -> np.ndarray:
+  """`edges` as the float64 [n_edge] array the K26 kernel compares against:
+  finite, strictly increasing, at most the kernel's `max_edges` (ValueError
+  otherwise)."""
+  cap = joint_geometry(torch.float32)['max_edges']
+  e = np.ascontiguousarray(edges, dtype=np.float64)
+  if e.ndim == 1 and e.size > cap:
+    raise ValueError(f'{e.size} bin edges: the joint counts take 0 to {cap}')
+  return conditional_edges(e, cap)
+
+
+def joint_counts(ens: torch.Tensor, member_stride: int, n_member: int,
+                 ens_slab, truth: torch.Tensor, truth_slab, n_outer: int,
+                 n_row: int, n_col: int, col_class, n_class: int, edges,
+                 side='right') -> torch.Tensor:
+  """K26, wb2_joint_counts: int32 [n_outer, n_row, n_class, B * B + 1] counts
+  of every (row, column class): code = bin(truth) * B + bin(member) gets +1 per
+  member of a valid point, code = B * B +1 per invalid point (truth or a member
+  is NaN); B = len(edges) + 1.  `side` is 'right' (bin = #{k : edge_k <= v}) or
+  'left' (#{k : edge_k < v}), or 0 / 1; `edges` is a HOST sequence of finite,
+  strictly increasing values.  The operands, the HOST slab tables and
+  `col_class` are those of `event_counts`; all of them and the edges are
+  checked here: the kernel trusts them."""
+  _require_float(ens, truth)
+  side = JOINT_SIDES.get(side, side)
+  if side not in (0, 1):
+    raise ValueError(f'side={side!r}: the joint counts take '
+                     f'{", ".join(map(repr, JOINT_SIDES))}')
+  e = joint_edges(edges)
+  n_class = int(n_class)
+  if not 1 <= int(n_member) <= 128:  # (wb2_joint_counts' own limits)
+    raise ValueError(f'{int(n_member)} members: the joint counts take 1 to 128')
+  # (the classes and the LDS budget: refused here)
+  joint_geometry(ens.dtype, n_member, n_class, e.size)
+  n_code = (e.size + 1) ** 2 + 1
+  (n_member, member_stride, n_outer, n_row, n_col), args, _ = _member_front(
+      ens, member_stride, n_member, ens_slab, truth, truth_slab, n_outer,
+      n_row, n_col)
+  cls = _column_classes(col_class, n_col, n_class)
+  dev = ens.device
+  cnt = torch.empty((n_outer, n_row, n_class, n_code), dtype=torch.int32,
+                    device=dev)
+  if args is None:  # no points: nothing to count
+    return cnt.zero_()
+  _launch('joint_counts', 'wb2_joint_counts', *args, n_member, member_stride,
+          n_outer, n_row, n_col,
+          _lib.ptr(_upload_i32(cls.astype(np.int32), dev)), n_class,
+          _lib.ptr(upload_f64_table(e, dev) if e.size else None), e.size, side,
+          _lib.ptr(cnt), current_stream_ptr(dev))
+  return cnt
+
+
+def joint_fold(cnt: torch.Tensor, wrow, mult) -> torch.Tensor:
+  """float64 [n_outer, n_region, n_code]: wb2_event_fold of the joint counts
+  (int32 [n_outer, n_row, n_class, n_code]).  `wrow` (float64 [n_region,
+  n_row]) and `mult` (int32 [n_region, n_class]) are HOST arrays."""
+  if cnt.dtype != torch.int32 or cnt.dim() != 4 or not cnt.is_contiguous():
+    raise ValueError('cnt must be a contiguous int32 [outer, row, class, code] '
+                     'tensor')
+  return event_fold(cnt[None], wrow, mult)[0]
+
+
 CROSS_TERMS = 4  # power_forecast, power_truth, cospectrum, quadrature
 
 

@@ -2289,6 +2289,110 @@ int wb2_joint_counts_geometry(int dtype, int32_t n_member, int32_t n_class,
                               int32_t* rows_per_group, int64_t* lds_bytes,
                               int32_t* max_edges, int32_t* max_grid_outer);
 
+/*
+ * K27: the structure functions of forecast and truth and the variogram score
+ * (Scheuerer & Hamill 2015): the verification of the DIFFERENCES between grid
+ * points, which the pointwise tables and the energy score (Pinson & Tastu
+ * 2013) are nearly blind to.  The reference has no counterpart.
+ *
+ * A lag is a pair of grid offsets (a, b): a >= 0 in rows, counted in the order
+ * the rows are handed over, b in columns (may be negative), (a, b) != (0, 0).
+ * The partner of the anchor (i, j) is (i + a, (j + b) mod n_col): the columns
+ * are cyclic.  The pair exists iff i + a < n_row.  The offsets are in GRID
+ * POINTS, the same count in every row (the convention of K19 and K22).
+ * One existing pair with truth y, y' and the members x_m, x'_m in STORAGE
+ * order, all arithmetic in float64 after an exact widening, no fused
+ * multiply-add, every product rounded before it is added:
+ *   g(d) = |d|            (order_code 1: order 1)
+ *        = d * d          (order_code 2: order 2)
+ *        = sqrt_rn(|d|)   (order_code 0: order 0.5, the correctly rounded root)
+ *   gy = g(y - y')
+ *   G = g(x_0 - x'_0);  G = G + g(x_m - x'_m)  (m = 1 .. M-1);  gf = G / (double)M
+ *   s = gy - gf;  sc = s * s
+ * The pair is invalid iff any of y, y', x_m, x'_m is NaN (K18's rule, at both
+ * ends).  Pairs that hold +-inf are not pinned.  A pair that does not exist is
+ * neither valid nor invalid.
+ *
+ * wb2_variogram_sums: K20's operands and slab-table convention (ens, ens_slab,
+ * truth, truth_slab, n_member, member_stride, n_outer; tables DEV int64, null
+ * = identity; col_class DEV int32[n_col] with values in [0, n_class); every
+ * table value the caller's to check) and lags, a HOST int32[n_lag][2] of (a,
+ * b) pairs, read before the call returns.
+ *   sums[o][i][c][l][0..2] (DEV float64, every element written) = the sums of
+ *     gy, gf and sc over the valid pairs of lag l whose anchor lies in row i of
+ *     outer index o, in a column j with col_class[j] == c,
+ *   cnt[o][i][c][l][0..1] (DEV int32, every element written) = the number of
+ *     valid and of invalid pairs among them.
+ * THE ORDER OF THE SUM of one (o, i, c, l, term): one sequential float64 chain
+ * s = s + v from +0.0 over the columns of the class in INCREASING COLUMN
+ * ORDER, where a pair that is invalid or does not exist enters as +0.0.  A
+ * chain started at +0.0 never holds -0.0, so that +0.0 changes no bit: the
+ * chain is the one over the valid pairs.  It does not depend on the tile, on
+ * the other classes or lags or on the launch: two runs are bit-equal, and a
+ * host loop over the columns reproduces the bits.
+ * Weighting is the caller's: a pair carries the weight of its ANCHOR, so a
+ * region owns the pairs whose anchor it holds, wherever the partner lies.
+ * One wave (a workgroup of its own: rows_per_group = 1) owns one anchor row of
+ * one outer index and walks it in tiles of tile_cols = 64 columns.  The truth
+ * ("member -1") and the members go through wave-private LDS strips, four items
+ * at a time: per item and per DISTINCT row offset among the lags (0 always)
+ * the wave requests the tile's 64 columns of that row and the halo that the
+ * lags of that row offset reach to the left and to the right, the index
+ * wrapped at the seam; the four items of up to five row offsets are requested
+ * before any is stored.  A strip holds 64 + 2 * max_col_offset = 128 columns.
+ * Column-shifted partners are read from the strips, never from memory again: a
+ * lane issues 1 + (distinct non-zero row offsets the row reaches) requests per
+ * member, plus the halos' share, not 1 + n_lag.  Each lane keeps gy, G and one
+ * invalid bit per lag in registers, every index a compile-time constant; the
+ * kernel is instantiated per dtype and order for 4, 8 and 16 lag slots and a
+ * call takes the least that holds n_lag.  After the last member the lane
+ * stores gy, gf, sc of every lag -- +0.0 where the pair is invalid or absent --
+ * and a word of the pairs' states into an LDS tile [point][3 n_lag | 1] that
+ * takes the strips' place.  Then lane s < 3 n_lag takes slot s = 3 l + term and
+ * adds the points of the tile in column order, eight LDS reads in flight (K24's
+ * walk); lanes 3 l and 3 l + 1 count the valid and the invalid pairs.  Where
+ * the class of the column changes (wave-uniform) the lane stores its sum and
+ * takes up the new class's -- read back from `sums` and `cnt` if the row met
+ * the class before, 0 otherwise.  Plain stores; no atomics at all.
+ * Checked before anything is enqueued, in this order: the dtype ("unknown
+ * dtype"), 1 <= n_member <= 128 ("n_member="), 1 <= n_class <= 64
+ * ("n_class="), 1 <= n_lag <= 16 ("n_lag="), the order code ("order_code="),
+ * a null `lags` ("null pointer"), per lag 0 <= a <= 16 ("row offset"), |b| <=
+ * 32 ("column offset"), |b| < n_col ("below n_col"; not where n_col = 0) and
+ * (a, b) != (0, 0) ("(0, 0)"), the strips and the tile against the budget of
+ * 65536 bytes ("LDS budget"), a negative member_stride, negative sizes, null
+ * pointers ("null pointer"), a row of 2^28 elements or more ("too long") and
+ * the grid.  Zero n_outer, n_row or n_col is a no-op whatever the pointers are.
+ *
+ * wb2_variogram_geometry: min_member = 1, max_member = 128, max_lags = 16,
+ * max_row_offset = 16, max_col_offset = 32, tile_cols = 64, rows_per_group =
+ * 1,
+ *   lds_bytes = max(4 * n_off * 128 * sizeof(dtype), 64 * (3 n_lag | 1) * 8)
+ *               + 256   (n_off = the distinct row offsets of `lags`, 0 among
+ *               them; the 256 bytes are the states of the 64 points),
+ * max_grid_outer outer indices per grid row.  The same checks of dtype,
+ * n_member, n_class, n_lag, the order code, the lags (but for |b| < n_col) and
+ * the budget, with the same error text: float64 lags with 16 or more distinct
+ * row offsets do not fit.
+ *
+ * The fold: the sums go through wb2_crps_bin_fold (n_slot = 3 n_lag), the
+ * counts through wb2_event_fold (n_code = 2 n_lag: per lag valid, invalid).
+ */
+int wb2_variogram_sums(int dtype, const void* ens, const int64_t* ens_slab,
+                       const void* truth, const int64_t* truth_slab,
+                       int32_t n_member, int64_t member_stride,
+                       int64_t n_outer, int32_t n_row, int32_t n_col,
+                       const int32_t* col_class, int32_t n_class,
+                       int order_code, const int32_t* lags, int32_t n_lag,
+                       double* sums, int32_t* cnt, void* stream);
+int wb2_variogram_geometry(int dtype, int32_t n_member, int32_t n_class,
+                           int order_code, const int32_t* lags, int32_t n_lag,
+                           int32_t* min_member, int32_t* max_member,
+                           int32_t* max_lags, int32_t* max_row_offset,
+                           int32_t* max_col_offset, int32_t* tile_cols,
+                           int32_t* rows_per_group, int64_t* lds_bytes,
+                           int32_t* max_grid_outer);
+
 #ifdef __cplusplus
 }
 #endif

@@ -305,6 +305,14 @@ _SIGNATURES = {
     'wb2_joint_counts_geometry': (_int, [
         _int, _i32, _i32, _i32, _int, _c.POINTER(_i32), _c.POINTER(_i64),
         _c.POINTER(_i32), _c.POINTER(_i32)]),
+    'wb2_variogram_sums': (_int, [
+        _int, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _i32,
+        _int, _vp, _i32, _vp, _vp, _vp]),
+    'wb2_variogram_geometry': (_int, [
+        _int, _i32, _i32, _int, _vp, _i32, _c.POINTER(_i32), _c.POINTER(_i32),
+        _c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i32),
+        _c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i64),
+        _c.POINTER(_i32)]),
 }
 
 _lib = None

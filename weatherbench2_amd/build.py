@@ -17,7 +17,8 @@ SOURCES = ('common.cpp', 'comm.cpp', 'staging.cpp', 'program.cpp', 'stream_reduc
            'climatology_quantile.hip', 'slab_scatter.hip', 'box_gather.hip',
            'event_table.hip', 'neighborhood.hip', 'crps_bins.hip',
            'twcrps.hip', 'pool.hip', 'resample_means.hip',
-           'conditional_sums.hip', 'cross_spectrum.hip', 'joint_counts.hip')
+           'conditional_sums.hip', 'cross_spectrum.hip', 'joint_counts.hip',
+           'variogram.hip')
 # compiled once per member count listed in sort3_networks.inc (WB2_SORT3_SIZES)
 EXACT_SOURCE = 'ensemble_exact.hip'
 

@@ -2332,6 +2332,144 @@ def joint_fold(cnt: torch.Tensor, wrow, mult) -> torch.Tensor:
   return event_fold(cnt[None], wrow, mult)[0]
 
 
+VARIOGRAM_ORDERS = {0.5: 0, 1.0: 1, 2.0: 2}  # order -> wb2_variogram_sums' code
+VARIOGRAM_TERMS = 3  # gy, gf, sc
+
+
+def variogram_order(order) -> int:
+  """The order code (0, 1, 2) of the order 0.5, 1 or 2 (ValueError
+  otherwise)."""
+  try:
+    return VARIOGRAM_ORDERS[float(order)]
+  except (KeyError, TypeError, ValueError):
+    raise ValueError(f'order={order!r}: the variogram sums take 0.5, 1 and '
+                     '2') from None
+
+
+def variogram_lags(lags) -> np.ndarray:
+  """`lags` as the HOST int32 [n_lag, 2] array of (row offset a >= 0, column
+  offset b) pairs that wb2_variogram_sums takes: whole numbers, no (0, 0), no
+  pair twice (ValueError otherwise; the kernel's own limits are its to
+  check)."""
+  try:
+    given = np.asarray(lags)
+    arr = np.ascontiguousarray(given, dtype=np.int64)
+    ok = (arr.ndim == 2 and arr.shape[1] == 2 and arr.shape[0] >= 1 and
+          given.dtype != bool and
+          bool(np.all(np.asarray(given, dtype=np.float64) == arr)))
+  except (TypeError, ValueError, OverflowError):
+    ok = False
+  if not ok:
+    raise ValueError('the lags must be a non-empty sequence of (row offset, '
+                     'column offset) pairs of whole numbers')
+  if (arr[:, 0] < 0).any():
+    raise ValueError('a lag\'s row offset must be >= 0 (take the opposite '
+                     'lag: it pairs the same points)')
+  if ((arr[:, 0] == 0) & (arr[:, 1] == 0)).any():
+    raise ValueError('the lag (0, 0) pairs a point with itself')
+  if len({tuple(p) for p in arr.tolist()}) != arr.shape[0]:
+    raise ValueError('the lags must differ: a lag is given twice')
+  if np.abs(arr).max() >= 2 ** 31:
+    raise ValueError('the lags are out of range')
+  return np.ascontiguousarray(arr, dtype=np.int32)
+
+
+def variogram_geometry(dtype: torch.dtype, n_member: int = 1,
+                       n_class: int = 1, order=0.5, lags=((0, 1),)) -> dict:
+  """Extents of the K27 sums kernel: the member counts it takes (`min_member`
+  .. `max_member`), `max_lags`, the largest row offset `max_row_offset` and
+  column offset `max_col_offset` of a lag, the `tile_cols` columns a wave
+  walks at a time, `rows_per_group` = 1 (a row is one wave, a workgroup of its
+  own), the `lds_bytes` of the strips and the tile of THESE lags,
+  `max_grid_outer` outer indices per grid row.  Lags past the limits or over
+  the LDS budget are refused here as in `variogram_sums`."""
+  lg = variogram_lags(lags)
+  return _geometry('wb2_variogram_geometry',
+                   (dtype_code(dtype), int(n_member), int(n_class),
+                    variogram_order(order), lg.ctypes.data, lg.shape[0]),
+                   [('min_member', _I32), ('max_member', _I32),
+                    ('max_lags', _I32), ('max_row_offset', _I32),
+                    ('max_col_offset', _I32), ('tile_cols', _I32),
+                    ('rows_per_group', _I32), ('lds_bytes', ctypes.c_int64),
+                    ('max_grid_outer', _I32)])
+
+
+def variogram_sums(ens: torch.Tensor, member_stride: int, n_member: int,
+                   ens_slab, truth: torch.Tensor, truth_slab, n_outer: int,
+                   n_row: int, n_col: int, col_class, n_class: int, order,
+                   lags) -> tuple:
+  """K27, wb2_variogram_sums: (float64 [n_outer, n_row, n_class, n_lag, 3] sums
+  of gy, gf and sc over the valid pairs, int32 [n_outer, n_row, n_class,
+  n_lag, 2] counts of the valid and the invalid pairs) of every (anchor row,
+  anchor's column class, lag).  `order` is 0.5, 1 or 2; `lags` is a HOST
+  sequence of (a, b) pairs in grid points, a >= 0, longitude cyclic.  The
+  operands, the HOST slab tables and `col_class` are those of `event_counts`;
+  all of them and the lags are checked here: the kernel trusts the tables."""
+  _require_float(ens, truth)
+  code = variogram_order(order)
+  lg = variogram_lags(lags)
+  n_lag = lg.shape[0]
+  n_class = int(n_class)
+  geo = variogram_geometry(ens.dtype)
+  _check_members(n_member, geo, 'the variogram sums take')
+  if n_lag > geo['max_lags']:
+    raise ValueError(f'{n_lag} lags: the variogram sums take 1 to '
+                     f"{geo['max_lags']}")
+  if lg[:, 0].max() > geo['max_row_offset']:
+    raise ValueError(f'row offset {int(lg[:, 0].max())}: the variogram sums '
+                     f"take 0 to {geo['max_row_offset']}")
+  reach = int(np.abs(lg[:, 1]).max())
+  if reach > geo['max_col_offset'] or (int(n_col) > 0 and reach >= int(n_col)):
+    raise ValueError(f'column offset of size {reach}: the variogram sums take '
+                     f"up to {geo['max_col_offset']}, below n_col={int(n_col)}")
+  # (the classes and the LDS budget of these lags: refused here)
+  variogram_geometry(ens.dtype, n_member, n_class, order, lg)
+  (n_member, member_stride, n_outer, n_row, n_col), args, _ = _member_front(
+      ens, member_stride, n_member, ens_slab, truth, truth_slab, n_outer,
+      n_row, n_col)
+  cls = _column_classes(col_class, n_col, n_class)
+  dev = ens.device
+  sums = torch.empty((n_outer, n_row, n_class, n_lag, VARIOGRAM_TERMS),
+                     dtype=torch.float64, device=dev)
+  cnt = torch.empty((n_outer, n_row, n_class, n_lag, 2), dtype=torch.int32,
+                    device=dev)
+  if args is None:  # no points: no pairs
+    return sums.zero_(), cnt.zero_()
+  _launch('variogram_sums', 'wb2_variogram_sums', *args, n_member,
+          member_stride, n_outer, n_row, n_col,
+          _lib.ptr(_upload_i32(cls.astype(np.int32), dev)), n_class, code,
+          lg.ctypes.data, n_lag, _lib.ptr(sums), _lib.ptr(cnt),
+          current_stream_ptr(dev))
+  return sums, cnt
+
+
+def variogram_fold(sums: torch.Tensor, cnt: torch.Tensor, class_cols, wrow,
+                   mult) -> tuple:
+  """(float64 [n_outer, n_region, n_lag, 3], float64 [n_outer, n_region, n_lag,
+  2]): wb2_crps_bin_fold of the sums (n_slot = 3 n_lag) -- sum_i wrow[r, i] *
+  (sum_c float(mult[r, c]) * sums[o, i, c]), classes then rows in increasing
+  order, plain float64 -- and wb2_event_fold of the counts (n_code = 2 n_lag:
+  per lag the valid and the invalid pairs).  `wrow` (float64 [n_region,
+  n_row]) and `mult` (int32 [n_region, n_class]) are HOST arrays; `class_cols`
+  is not needed (absent pairs are no invalid ones) and only checked."""
+  if (sums.dtype != torch.float64 or sums.dim() != 5 or
+      sums.shape[4] != VARIOGRAM_TERMS or not sums.is_contiguous() or
+      cnt.dtype != torch.int32 or
+      tuple(cnt.shape) != tuple(sums.shape[:4]) + (2,) or
+      not cnt.is_contiguous() or cnt.device != sums.device):
+    raise ValueError('sums must be a contiguous float64 [outer, row, class, '
+                     'lag, 3] tensor and cnt its int32 [outer, row, class, '
+                     'lag, 2]')
+  n_outer, n_row, n_class, n_lag, _ = (int(n) for n in sums.shape)
+  wrow, mult, _ = _fold_weights(wrow, mult, n_row, n_class, class_cols)
+  table = _class_fold('crps_bin_fold', sums, n_outer, VARIOGRAM_TERMS * n_lag,
+                      (n_outer, wrow.shape[0], n_lag, VARIOGRAM_TERMS), wrow,
+                      mult)
+  codes = cnt.reshape(1, n_outer, n_row, n_class, 2 * n_lag)
+  return table, event_fold(codes, wrow, mult)[0].reshape(
+      n_outer, wrow.shape[0], n_lag, 2)
+
+
 CROSS_TERMS = 4  # power_forecast, power_truth, cospectrum, quadrature
 
 

@@ -2393,6 +2393,98 @@ int wb2_variogram_geometry(int dtype, int32_t n_member, int32_t n_class,
                            int32_t* rows_per_group, int64_t* lds_bytes,
                            int32_t* max_grid_outer);
 
+/*
+ * K28: the sums behind the verification of QUANTILE forecasts: the pinball
+ * (quantile) loss, the forecast quantile, and how often the truth lies below
+ * or on it -- the quantile score, quantile reliability and the coverage, width
+ * and interval score (Winkler 1972) of central prediction intervals are host
+ * arithmetic on them.  The reference has no counterpart.
+ *
+ * One point, truth y, level l, all arithmetic in float64 after an exact
+ * widening, no fused multiply-add, every product rounded before it is added:
+ *   mode 0 (sorted ensemble): the M members sorted x_0 <= ... <= x_{M-1};
+ *     d = x_hi[l] - x_lo[l] in the DATA's dtype;
+ *     q = x_lo + d t[l]             (t[l] < 1/2)
+ *       = x_hi - d (1 - t[l])       (otherwise: K12's interpolation)
+ *   mode 1 (direct): the M "members" are quantile values in STORAGE order;
+ *     q = x_lo[l]; nothing is sorted, nothing interpolated; lo == hi
+ *   u = y - q;  pinball = tau[l] u (u >= 0), one_minus_tau[l] (-u) (otherwise)
+ *   below = y < q;  tie = y == q   (IEEE compares: -0.0 ties with +0.0)
+ * The point is invalid iff the truth or any member is NaN (K18's rule).
+ * Points that hold +-inf are not pinned.  The kernel knows no quantile method:
+ * lo, hi, t, tau and one_minus_tau are HOST tables of n_level entries, read
+ * before the call returns.
+ *
+ * wb2_quantile_score_sums: K20's operands and slab-table convention (ens,
+ * ens_slab, truth, truth_slab, n_member, member_stride, n_outer; tables DEV
+ * int64, null = identity; col_class DEV int32[n_col] with values in [0,
+ * n_class); every table value the caller's to check).
+ *   sums[o][i][c][l][0..1] (DEV float64, every element written) = the sums of
+ *     pinball and q over the valid points of row i of outer index o in the
+ *     columns j with col_class[j] == c,
+ *   cnt[o][i][c][l][0..1] (DEV int32, every element written) = the number of
+ *     those points with `below` and with `tie`,
+ *   valid[o][i][c][0..1] (DEV int32, every element written) = the number of
+ *     valid and of invalid points of the (row, class).
+ * THE ORDER OF THE SUM of one (o, i, c, l, term): one sequential float64 chain
+ * s = s + v from +0.0 over the columns of the class in INCREASING COLUMN
+ * ORDER, where an invalid point enters as +0.0.  A chain started at +0.0
+ * never holds -0.0, so that +0.0 changes no bit.  It does not depend on the
+ * tile, on the other classes or levels or on the launch: two runs are
+ * bit-equal, and a host loop over the columns reproduces the bits.
+ * One wave (a workgroup of its own: rows_per_group = 1) owns one row of one
+ * outer index and walks it in tiles of tile_cols = 64 columns.  A lane
+ * requests its point's class, truth and members, all before any is looked at,
+ * sorts the members in registers (mode 0; the networks padded to 2, 4, ..,
+ * 64) and stores them in a wave-private LDS tile [M][64]; per level it reads
+ * x_lo and x_hi back at the wave-uniform rows lo[l], hi[l] and keeps q,
+ * pinball and the flags under compile-time indices (instantiated per dtype and
+ * padded member count for 4, 8 and 16 level slots; a call takes the least that
+ * holds n_level).  The values -- +0.0 where the point is invalid -- go into an
+ * LDS tile [point][2 n_level | 1] that takes the members' place, the flags as
+ * one word per point.  Then lane s < 2 n_level takes slot s = 2 l + term and
+ * adds the points in column order, eight LDS reads in flight (K24's walk);
+ * lane 2 l counts below, lane 2 l + 1 tie; the valid and invalid counts come
+ * from two ballots.  At a class change (wave-uniform) the lane stores its sum
+ * and takes up the new class's -- read back if the row met the class before, 0
+ * otherwise.  Plain stores; no atomics at all.
+ * Checked before anything is enqueued, in this order: the dtype ("unknown
+ * dtype"), 1 <= n_member <= 64 ("n_member="), 1 <= n_class <= 64
+ * ("n_class="), the mode ("mode="), 1 <= n_level <= 16 ("n_level="), the tile
+ * against the budget of 65536 bytes ("LDS budget"), null tables ("null
+ * pointer"), per level 0 <= lo <= hi < n_member and, in mode 1, lo == hi
+ * ("positions"), a negative member_stride, negative sizes, null pointers
+ * ("null pointer"), a row of 2^28 elements or more ("too long") and the grid.
+ * Zero n_outer, n_row or n_col is a no-op whatever the pointers are.
+ *
+ * wb2_quantile_score_geometry: min_member = 1, max_member = 64, max_levels =
+ * 16, tile_cols = 64, rows_per_group = 1,
+ *   lds_bytes = max(n_member * 64 * sizeof(dtype), 64 * (2 n_level | 1) * 8)
+ *               + 256   (the 256 bytes are the flag words of the 64 points),
+ * max_grid_outer outer indices per grid row.  The same checks of dtype,
+ * n_member, n_class, mode, n_level and the budget, with the same error text.
+ *
+ * The fold: the sums go through wb2_crps_bin_fold (n_slot = 2 n_level), the
+ * counts through wb2_event_fold (n_code = 2 n_level + 2: per level below, tie,
+ * then valid, invalid).
+ */
+int wb2_quantile_score_sums(int dtype, const void* ens, const int64_t* ens_slab,
+                            const void* truth, const int64_t* truth_slab,
+                            int32_t n_member, int64_t member_stride,
+                            int64_t n_outer, int32_t n_row, int32_t n_col,
+                            const int32_t* col_class, int32_t n_class, int mode,
+                            int32_t n_level, const int32_t* lo,
+                            const int32_t* hi, const double* t,
+                            const double* tau, const double* one_minus_tau,
+                            double* sums, int32_t* cnt, int32_t* valid,
+                            void* stream);
+int wb2_quantile_score_geometry(int dtype, int32_t n_member, int32_t n_class,
+                                int mode, int32_t n_level,
+                                int32_t* min_member, int32_t* max_member,
+                                int32_t* max_levels, int32_t* tile_cols,
+                                int32_t* rows_per_group, int64_t* lds_bytes,
+                                int32_t* max_grid_outer);
+
 #ifdef __cplusplus
 }
 #endif

@@ -313,6 +313,13 @@ _SIGNATURES = {
         _c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i32),
         _c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i64),
         _c.POINTER(_i32)]),
+    'wb2_quantile_score_sums': (_int, [
+        _int, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _i32,
+        _int, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'wb2_quantile_score_geometry': (_int, [
+        _int, _i32, _i32, _int, _i32, _c.POINTER(_i32), _c.POINTER(_i32),
+        _c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i32),
+        _c.POINTER(_i64), _c.POINTER(_i32)]),
 }
 
 _lib = None

@@ -18,7 +18,7 @@ SOURCES = ('common.cpp', 'comm.cpp', 'staging.cpp', 'program.cpp', 'stream_reduc
            'event_table.hip', 'neighborhood.hip', 'crps_bins.hip',
            'twcrps.hip', 'pool.hip', 'resample_means.hip',
            'conditional_sums.hip', 'cross_spectrum.hip', 'joint_counts.hip',
-           'variogram.hip')
+           'variogram.hip', 'quantile_score.hip')
 # compiled once per member count listed in sort3_networks.inc (WB2_SORT3_SIZES)
 EXACT_SOURCE = 'ensemble_exact.hip'
 

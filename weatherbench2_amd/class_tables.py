@@ -7,9 +7,9 @@ class) in one fixed order and fold the classes and rows in another
 fold, the choice between the host and the device path, the checks of a
 variable, and the truth-led (<outer dims>, 'term', 'bin') table that `CRPSTable`
 and `ConditionalTable` are (`ThresholdWeightedCRPS`, forecast-led and with
-thresholds, is an `events.ExceedanceTable`).  `distribution.JointTable` (K26)
-and `structure.VariogramTable` (K27) are `ClassSumsTable`s that name their own
-trailing dims.
+thresholds, is an `events.ExceedanceTable`).  `distribution.JointTable` (K26),
+`structure.VariogramTable` (K27) and `quantile_scores.QuantileScoreTable` (K28)
+are `ClassSumsTable`s that name their own trailing dims.
 """
 from __future__ import annotations
 

@@ -2470,6 +2470,203 @@ def variogram_fold(sums: torch.Tensor, cnt: torch.Tensor, class_cols, wrow,
       n_outer, wrow.shape[0], n_lag, 2)
 
 
+QUANTILE_SCORE_METHODS = ('linear', 'hazen', 'weibull')
+QUANTILE_SCORE_TERMS = 2  # pinball, q
+# those of wb2_quantile_score_geometry, and the levels of a table
+QUANTILE_SCORE_MAX_MEMBER = 64
+QUANTILE_SCORE_LAUNCH_LEVELS = 16
+QUANTILE_SCORE_MAX_LEVELS = 64
+
+
+def quantile_score_levels(levels, n_member: int, method: str = 'linear',
+                          direct: bool = False) -> tuple:
+  """The HOST tables of wb2_quantile_score_sums for `levels` and `n_member`
+  sorted members: (int32 lo, int32 hi, float64 t, float64 tau, float64 1 -
+  tau), each [n_level].  The 0-based position of level tau is v = tau (M - 1)
+  ('linear'), M tau - 1/2 ('hazen') or (M + 1) tau - 1 ('weibull'), clamped to
+  [0, M - 1], all in float64; lo = floor(v), t = v - lo, hi = min(lo + 1, M -
+  1).  `direct`: the members ARE the quantile forecasts of the levels, in
+  their order: lo = hi = the level's index, t = 0, and `method` is not asked.
+  Checked (ValueError): the method, 1 to 64 members, levels that are a
+  non-empty 1-D sequence of finite numbers in [0, 1], strictly increasing, at
+  most 64 (direct: at most 16, and as many as members).  Needs no GPU."""
+  if not direct and method not in QUANTILE_SCORE_METHODS:
+    raise ValueError(f'method={method!r}: the quantile score takes '
+                     f'{", ".join(map(repr, QUANTILE_SCORE_METHODS))}')
+  try:
+    tau = np.ascontiguousarray(levels, dtype=np.float64)
+  except (TypeError, ValueError):
+    raise ValueError('the levels must be numbers') from None
+  if tau.ndim != 1 or tau.size == 0:
+    raise ValueError('the levels must be a non-empty 1-D sequence')
+  if not np.isfinite(tau).all():
+    raise ValueError('the levels must be finite')
+  if tau.min() < 0.0 or tau.max() > 1.0:
+    raise ValueError('the levels must lie within [0, 1]')
+  if tau.size > 1 and not (tau[1:] > tau[:-1]).all():
+    raise ValueError('the levels must be strictly increasing')
+  most = QUANTILE_SCORE_LAUNCH_LEVELS if direct else QUANTILE_SCORE_MAX_LEVELS
+  if tau.size > most:
+    raise ValueError(f'{tau.size} levels: the quantile score takes 1 to {most}'
+                     + (' quantile forecasts' if direct else ''))
+  n_member = int(n_member)
+  if not 1 <= n_member <= QUANTILE_SCORE_MAX_MEMBER:
+    raise ValueError(f'{n_member} members: the quantile score takes 1 to '
+                     f'{QUANTILE_SCORE_MAX_MEMBER}')
+  if direct:
+    if tau.size != n_member:
+      raise ValueError(f'{tau.size} levels for {n_member} quantile forecasts')
+    lo = np.arange(n_member, dtype=np.int32)
+    return lo, lo.copy(), np.zeros(n_member), tau, 1.0 - tau
+  m = float(n_member)
+  if method == 'linear':
+    v = tau * (m - 1.0)
+  elif method == 'hazen':
+    v = m * tau - 0.5
+  else:
+    v = (m + 1.0) * tau - 1.0
+  v = np.minimum(np.maximum(v, 0.0), m - 1.0)
+  lo = np.floor(v)
+  t = v - lo
+  lo = lo.astype(np.int32)
+  hi = np.minimum(lo + 1, n_member - 1).astype(np.int32)
+  return lo, hi, t, tau, 1.0 - tau
+
+
+def _quantile_score_tables(tables, n_member: int, direct: bool) -> tuple:
+  """`tables` (those of `quantile_score_levels`) as the contiguous arrays the
+  kernel reads, checked against `n_member`: it trusts them."""
+  try:
+    lo, hi, t, tau, omt = tables
+  except (TypeError, ValueError):
+    raise ValueError('the level tables must be (lo, hi, t, tau, 1 - tau)'
+                     ) from None
+  lo = np.ascontiguousarray(lo, dtype=np.int32)
+  hi = np.ascontiguousarray(hi, dtype=np.int32)
+  t, tau, omt = (np.ascontiguousarray(a, dtype=np.float64)
+                 for a in (t, tau, omt))
+  n_level = lo.size
+  if n_level < 1 or any(a.shape != (n_level,) for a in (lo, hi, t, tau, omt)):
+    raise ValueError('the level tables must be non-empty 1-D arrays of one '
+                     'length')
+  if (lo < 0).any() or (lo > hi).any() or (hi >= int(n_member)).any():
+    raise ValueError('the level tables need 0 <= lo <= hi < n_member='
+                     f'{int(n_member)}')
+  if direct and (lo != hi).any():
+    raise ValueError('direct quantiles need lo == hi')
+  if not (np.isfinite(t).all() and (t >= 0).all() and (t < 1).all()):
+    raise ValueError('the level tables need 0 <= t < 1')
+  return lo, hi, t, tau, omt
+
+
+def quantile_score_geometry(dtype: torch.dtype, n_member: int = 1,
+                            n_class: int = 1, n_level: int = 1,
+                            direct: bool = False) -> dict:
+  """Extents of the K28 sums kernel: the member counts it takes (`min_member`
+  .. `max_member`), the `max_levels` of one launch, the `tile_cols` columns a
+  wave walks at a time, `rows_per_group` = 1 (a row is one wave, a workgroup
+  of its own), the `lds_bytes` of the tile of THESE members and levels,
+  `max_grid_outer` outer indices per grid row.  Sizes past the limits or over
+  the LDS budget are refused here as in `quantile_score_sums`."""
+  return _geometry('wb2_quantile_score_geometry',
+                   (dtype_code(dtype), int(n_member), int(n_class),
+                    int(bool(direct)), int(n_level)),
+                   [('min_member', _I32), ('max_member', _I32),
+                    ('max_levels', _I32), ('tile_cols', _I32),
+                    ('rows_per_group', _I32), ('lds_bytes', ctypes.c_int64),
+                    ('max_grid_outer', _I32)])
+
+
+def quantile_score_sums(ens: torch.Tensor, member_stride: int, n_member: int,
+                        ens_slab, truth: torch.Tensor, truth_slab,
+                        n_outer: int, n_row: int, n_col: int, col_class,
+                        n_class: int, tables, direct: bool = False) -> tuple:
+  """K28, wb2_quantile_score_sums: (float64 [n_outer, n_row, n_class, n_level,
+  2] sums of pinball and q, int32 [n_outer, n_row, n_class, n_level, 2] counts
+  of `below` and `tie`, int32 [n_outer, n_row, n_class, 2] counts of the valid
+  and the invalid points) of every (row, column class, level).  `tables` are
+  the HOST tables of `quantile_score_levels`; `direct`: the members are the
+  quantile forecasts themselves (at most 16).  More than 16 levels become
+  further launches of up to 16, each with its own read and sort of the
+  members.  The operands, the HOST slab tables and `col_class` are those of
+  `event_counts`; all of them and the tables are checked here: the kernel
+  trusts them."""
+  _require_float(ens, truth)
+  direct = bool(direct)
+  geo = quantile_score_geometry(ens.dtype)
+  _check_members(n_member, geo, 'the quantile score sums take')
+  lo, hi, t, tau, omt = _quantile_score_tables(tables, n_member, direct)
+  n_level = lo.size
+  per = geo['max_levels']
+  if n_level > (per if direct else QUANTILE_SCORE_MAX_LEVELS):
+    raise ValueError(f'{n_level} levels: the quantile score sums take 1 to '
+                     f'{per if direct else QUANTILE_SCORE_MAX_LEVELS}')
+  n_class = int(n_class)
+  # (the classes and the LDS budget: refused here)
+  quantile_score_geometry(ens.dtype, n_member, n_class, min(n_level, per),
+                          direct)
+  (n_member, member_stride, n_outer, n_row, n_col), args, _ = _member_front(
+      ens, member_stride, n_member, ens_slab, truth, truth_slab, n_outer,
+      n_row, n_col)
+  cls = _column_classes(col_class, n_col, n_class)
+  dev = ens.device
+  shape = (n_outer, n_row, n_class)
+  valid = torch.empty(shape + (2,), dtype=torch.int32, device=dev)
+  if args is None:  # no points: nothing to add
+    return (torch.zeros(shape + (n_level, QUANTILE_SCORE_TERMS),
+                        dtype=torch.float64, device=dev),
+            torch.zeros(shape + (n_level, 2), dtype=torch.int32, device=dev),
+            valid.zero_())
+  cls_dev = _upload_i32(cls.astype(np.int32), dev)
+  parts = []
+  for l0 in range(0, n_level, per):
+    nl = min(per, n_level - l0)
+    sums = torch.empty(shape + (nl, QUANTILE_SCORE_TERMS), dtype=torch.float64,
+                       device=dev)
+    cnt = torch.empty(shape + (nl, 2), dtype=torch.int32, device=dev)
+    part = [np.ascontiguousarray(a[l0:l0 + nl]) for a in (lo, hi, t, tau, omt)]
+    _launch('quantile_score_sums', 'wb2_quantile_score_sums', *args, n_member,
+            member_stride, n_outer, n_row, n_col, _lib.ptr(cls_dev), n_class,
+            int(direct), nl, *[a.ctypes.data for a in part], _lib.ptr(sums),
+            _lib.ptr(cnt), _lib.ptr(valid), current_stream_ptr(dev))
+    parts.append((sums, cnt))
+  if len(parts) == 1:
+    return parts[0][0], parts[0][1], valid
+  return (torch.cat([s for s, _ in parts], dim=3),
+          torch.cat([c for _, c in parts], dim=3), valid)
+
+
+def quantile_score_fold(sums: torch.Tensor, cnt: torch.Tensor,
+                        valid: torch.Tensor, class_cols, wrow, mult) -> tuple:
+  """(float64 [n_outer, n_region, n_level, 2], float64 [n_outer, n_region, 2
+  n_level + 2]): wb2_crps_bin_fold of the sums (n_slot = 2 n_level) -- sum_i
+  wrow[r, i] * (sum_c float(mult[r, c]) * sums[o, i, c]), classes then rows in
+  increasing order, plain float64 -- and wb2_event_fold of the counts (per
+  level below, tie; then valid, invalid).  `wrow` (float64 [n_region, n_row])
+  and `mult` (int32 [n_region, n_class]) are HOST arrays; `class_cols` is not
+  needed (the kernel counts the invalid points itself) and only checked."""
+  if (sums.dtype != torch.float64 or sums.dim() != 5 or
+      sums.shape[4] != QUANTILE_SCORE_TERMS or not sums.is_contiguous() or
+      cnt.dtype != torch.int32 or
+      tuple(cnt.shape) != tuple(sums.shape[:4]) + (2,) or
+      not cnt.is_contiguous() or cnt.device != sums.device or
+      valid.dtype != torch.int32 or
+      tuple(valid.shape) != tuple(sums.shape[:3]) + (2,) or
+      not valid.is_contiguous() or valid.device != sums.device):
+    raise ValueError('sums must be a contiguous float64 [outer, row, class, '
+                     'level, 2] tensor, cnt its int32 [outer, row, class, '
+                     'level, 2] and valid its int32 [outer, row, class, 2]')
+  n_outer, n_row, n_class, n_level, _ = (int(n) for n in sums.shape)
+  wrow, mult, _ = _fold_weights(wrow, mult, n_row, n_class, class_cols)
+  table = _class_fold('crps_bin_fold', sums, n_outer,
+                      QUANTILE_SCORE_TERMS * n_level,
+                      (n_outer, wrow.shape[0], n_level, QUANTILE_SCORE_TERMS),
+                      wrow, mult)
+  codes = torch.cat([cnt.reshape(n_outer, n_row, n_class, 2 * n_level), valid],
+                    dim=-1)
+  return table, event_fold(codes[None].contiguous(), wrow, mult)[0]
+
+
 CROSS_TERMS = 4  # power_forecast, power_truth, cospectrum, quadrature
 
 
